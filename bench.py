@@ -2,8 +2,19 @@
 """Driver benchmark.  Default = the headline: DP-IPD forward throughput on BASELINE config 2
 (4 mics, 257 bins x 300 frames, 32 utterances = 192 mic pairs per GPU, fp32).
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run (no --full) is lean: set up, W warm-up steps, K timed steps, the outputs of the last timed step to DIR if
+--dump-outputs is given, and the one JSON line with the contract keys (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` = wall time of the K timed steps / K, ...), `config` and `cluster_fallbacks`.  Everything else
+described below — the instrumented per-kernel pass, roofline, fp32-MFMA calibration, A/B legs, CPU baseline + parity,
+strong-scaling efficiency, the nested `other_configs`, the detail file — runs only with --full.
+
+--dump-outputs DIR: after the timed steps, what the timed path returned in its LAST step, as DIR/<name>.npy in float32
+(configs 2, 3, 5: `dp_ipd`, the network output; config 4: `loss` and `params`, the flat parameter vector after the
+step), rank 0's, at most 64 MB in all (a larger output is cut to a fixed, seeded sample of its flat entries, `dump_outputs`).
+Inputs and weights are seeded, so the same arguments give the same inputs in every run.
 
 --config picks the BASELINE.json configuration (configs[1] = 2 is the metric the headline is quoted on; 1 is the
 reference's own CPU case and only a parity test):
@@ -14,17 +25,17 @@ reference's own CPU case and only a parity test):
 
 A "step" is one pass of the hot path over one synthetic batch already resident in HBM.  Every rank runs the same
 per-GPU batch (weak scaling; utterances are independent: no data-path collective, config 4 has the one gradient
-all-reduce) — or, with --scaling strong (config 2), an even share of the configuration's GLOBAL batch, and the line
-then carries `strong_scaling.efficiency` against one rank running the whole batch in the same run.  K steps are timed
+all-reduce) — or, with --scaling strong (config 2), an even share of the configuration's GLOBAL batch, and a --full
+line then carries `strong_scaling.efficiency` against one rank running the whole batch in the same run.  K steps are timed
 between barrier + synchronize, max over ranks; rank 0 prints ONE JSON line (compact: < 4 KB, `compact_line`) whose `value`
-is utterance-frames per second over all ranks; the FULL record goes to --detail (default gpurun_out/bench_detail.json).
-The default run (no flags) also measures config 2's 'M' pairing and is_online=False variants ("2M", "2off"), the
+is utterance-frames per second over all ranks; with --full the FULL record goes to --detail (default: see --detail).
+The --full run of the default shape also measures config 2's 'M' pairing and is_online=False variants ("2M", "2off"), the
 reference's real predict shape — ONE 4-mic utterance, whole ("2b1") and streamed in 12-frame chunks ("2s") — and configs
 3, 4, 5: the stdout line carries {value, ms_per_step, roofline_frac, cpu_baseline, parity_ok} of each under
 `other_configs`, the detail file their full lines (own roofline / cpu_baseline / parity).  Every line carries
 `cluster_fallbacks` (LSTM launches of the timed region whose cluster-resident kernel gave up and were recomputed by the
-guarded fallback kernels: must be 0, else `value` is null) and `peak_mem_gb` (of that configuration alone).
-stdout line:
+guarded fallback kernels: must be 0, else `value` is null); a --full line also `peak_mem_gb` (of that configuration alone).
+stdout line of a --full run:
   roofline     : the dominant kernel against its roof {bound, kernel, achieved, peak, frac, traffic, launches, avg_ms,
                  flop_per_launch}, timed with HIP events on the launch stream inside the timed region — only that kernel
                  is bracketed there (fnssl_timing_select); peak_measured / peak_measured_sustained = this device's own
@@ -58,7 +69,7 @@ PEAK_HBM_GBS = 8000.0
 FLOP_PER_TF_POINT = {True: 4997120, False: 4210688}   # LSTM matmuls only, by is_online
 TRAFFIC_JSON = os.path.join("profiles", "r06", "hbm_traffic.json")     # per roofline kernel: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes
 TRAFFIC_JSON_R03 = os.path.join("profiles", "r03", "hbm_traffic_lstm_h256.json")
-# same-process A/B legs of the default run: (label, environment of the B leg).  A = the shipped default.
+# same-process A/B legs of the --full run: (label, environment of the B leg).  A = the shipped default.
 AB_KNOBS = [
     # round 6: four hidden slices per pass with an LDS-DMA weight ring (lstm_static4.h) against the two-slice operand-ring kernel
     ("four_slices_per_pass_vs_two", {"FNSSL_NO_STATIC4": "1"}),
@@ -216,6 +227,9 @@ class FnsslForward:
         nseg = (self.chunk or self.nt) // 12
         assert tuple(out.shape) == (self.nb * self.n_pairs, nseg, 512) and bool(torch.isfinite(out).all())
 
+    def outputs(self, out):
+        return {"dp_ipd": out}
+
     def config(self):
         a = self.args
         return {"workload": "BASELINE configs[1]: FN-SSL (%s) DP-IPD forward, waveform->STFT->features->"
@@ -346,6 +360,9 @@ class IpdnetForward:
     def check(self, out):
         assert tuple(out.shape) == (self.nb, self.nt // 12, 512, self.mics - 1, 2) and bool(torch.isfinite(out.float()).all())
 
+    def outputs(self, out):
+        return {"dp_ipd": out}
+
     def config(self):
         return {"workload": "BASELINE configs[2]: IPDnet fixed-array %d-mic (input 16 ch, hidden 256, online, 2 tracks) "
                             "DP-IPD forward, waveform->STFT->array features->2x(full-band BiLSTM + narrow-band LSTM, "
@@ -464,6 +481,14 @@ class FnsslTrain:
 
     def check(self, out):
         assert bool(torch.isfinite(out).all())
+
+    def outputs(self, out):
+        """The step's loss and the parameters it left behind (the fused engine keeps them in one flat vector)."""
+        if self.ag is not None:
+            params = torch.cat([p.detach().reshape(-1) for p in self.ag["net"].parameters()])
+        else:
+            params = self.eng.theta
+        return {"loss": out, "params": params}
 
     def config(self):
         return {"workload": "BASELINE configs[3]: FN-SSL (online) training step, global batch %d two-mic utterances = %d per "
@@ -623,6 +648,9 @@ class Ipdnet2Forward:
 
     def check(self, out):
         assert tuple(out.shape) == (self.nb, self.nt // 5, 512, 4, 2) and bool(torch.isfinite(out).all())
+
+    def outputs(self, out):
+        return {"dp_ipd": out}
 
     def config(self):
         return {"workload": "BASELINE configs[4]: IPDnet2 OnlineSpatialNet (8 layers, hidden 96, mamba(16,4)), 15-mic "
@@ -836,6 +864,39 @@ def write_detail(full, path):
         return None
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6      # --dump-outputs: all files together, .npy headers included
+DUMP_SEED = 20240601
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES):
+    """Write ``{name: tensor or array}`` as ``out_dir/<name>.npy`` in float32 (float64 stays float64).  If the data
+    would exceed ``limit`` bytes, every array is cut to the same fraction of its flat entries, chosen by a fixed seed
+    (sorted indices), so two runs with the same shapes sample the same entries.  Returns {name: (shape, entries written)}."""
+    host = {}
+    for name, a in arrays.items():
+        if torch.is_tensor(a):
+            a = a.detach()
+            a = (a if a.dtype == torch.float64 else a.float()).cpu().numpy()
+        a = np.asarray(a)
+        host[name] = np.ascontiguousarray(a if a.dtype == np.float64 else a.astype(np.float32, copy=False))
+    budget = limit - 4096 * len(host)                                   # np.save headers are < 4 KB each
+    total = sum(a.nbytes for a in host.values())
+    frac = 1.0 if total <= budget else budget / float(total)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in host.items():
+        flat = a.reshape(-1)
+        keep = flat.size if frac >= 1.0 else int(flat.size * frac)
+        if keep < flat.size:
+            idx = np.sort(np.random.RandomState(DUMP_SEED).choice(flat.size, keep, replace=False))
+            flat = flat[idx]
+            log("--dump-outputs: %s %s cut to a seeded sample of %d of its %d entries" % (name, a.shape, keep, a.size))
+        out = a if keep == a.size else flat
+        np.save(os.path.join(out_dir, name + ".npy"), out)
+        written[name] = (tuple(a.shape), int(out.size))
+    return written
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -866,10 +927,13 @@ def self_launch(args):
     sys.exit(subprocess.call(cmd, env=env))
 
 
-def run_workload(args, cfg, dev, rank, world, dist, backend, steps, warmup):
-    """Warm up, instrumented pass, timed region (barrier + synchronize on both sides, max over ranks), CPU baseline +
-    parity (rank 0, N = 1).  Returns (line dict on rank 0 / None elsewhere, parity_failed)."""
+def run_workload(args, cfg, dev, rank, world, dist, backend, steps, warmup, dump_dir=None):
+    """Warm up, timed region (barrier + synchronize on both sides, max over ranks), the last step's outputs to
+    ``dump_dir`` (rank 0).  With ``args.full`` also: the instrumented pass before the timed region, the roofline kernel
+    bracketed inside it, and the evidence legs after it (calibration, A/B, strong scaling, CPU baseline + parity).
+    Returns (line dict on rank 0 / None elsewhere, failed)."""
     from fnssl import ops
+    full = bool(getattr(args, "full", False))
     wl = WORKLOADS[cfg](args, dev, rank, world)
 
     def sync_all():
@@ -878,64 +942,78 @@ def run_workload(args, cfg, dev, rank, world, dist, backend, steps, warmup):
             dist.barrier()
             torch.cuda.synchronize()
 
-    torch.cuda.reset_peak_memory_stats(dev)      # peak_mem_gb is THIS configuration's, not the process's
+    if full:
+        torch.cuda.reset_peak_memory_stats(dev)      # peak_mem_gb is THIS configuration's, not the process's
     out = None
     for _ in range(warmup):
         out = wl.step()
     sync_all()
-    # Per-kernel breakdown: an instrumented pass of its own (every launch bracketed by HIP events), outside the timed
-    # region — two event records per launch cost a 106-launch step (IPDnet2) 10 % of its time.  The timed region
-    # below brackets only the roofline kernel, which is what `roofline.achieved` is computed from.
-    probe_steps = max(1, min(3, steps))
-    probe_env = getattr(wl, "probe_env", {})      # e.g. config 3: the instrumented pass runs on ONE stream (kernels alone)
-    saved_env = {k: os.environ.get(k) for k in probe_env}
-    os.environ.update(probe_env)
-    ops._lib.refresh_tuning()       # FNSSL_* knobs are parsed by fnssl/_lib.py, not by the library: re-read them
-    ops.timing_select(None)
-    ops.timing_enable(True)
-    for _ in range(probe_steps):
-        out = wl.step()
-    sync_all()
-    ops.timing_enable(False)
-    for k, v in saved_env.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = v
-    ops._lib.refresh_tuning()
-    kern_all = ops.timing_collect()
-    roof_probe = wl.roofline(kern_all)
-    roof_name = roof_probe.get("name") if roof_probe else None
-    ops.timing_select(roof_name)
-    ops.timing_enable(roof_name is not None)     # HIP events on the launch stream around the roofline kernel only
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+    probe_steps, probe_env, kern_all, roof_probe, roof_name, ev = 0, {}, {}, None, None, []
+    if full:
+        # Per-kernel breakdown: an instrumented pass of its own (every launch bracketed by HIP events), outside the timed
+        # region — two event records per launch cost a 106-launch step (IPDnet2) 10 % of its time.  The timed region
+        # below brackets only the roofline kernel, which is what `roofline.achieved` is computed from.
+        probe_steps = max(1, min(3, steps))
+        probe_env = getattr(wl, "probe_env", {})      # e.g. config 3: the instrumented pass runs on ONE stream (kernels alone)
+        saved_env = {k: os.environ.get(k) for k in probe_env}
+        os.environ.update(probe_env)
+        ops._lib.refresh_tuning()       # FNSSL_* knobs are parsed by fnssl/_lib.py, not by the library: re-read them
+        ops.timing_select(None)
+        ops.timing_enable(True)
+        for _ in range(probe_steps):
+            out = wl.step()
+        sync_all()
+        ops.timing_enable(False)
+        for k, v in saved_env.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        ops._lib.refresh_tuning()
+        kern_all = ops.timing_collect()
+        roof_probe = wl.roofline(kern_all)
+        roof_name = roof_probe.get("name") if roof_probe else None
+        ops.timing_select(roof_name)
+        ops.timing_enable(roof_name is not None)     # HIP events on the launch stream around the roofline kernel only
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
     # cluster-resident kernels that give up on a hand-off are recomputed by guarded fallback kernels (correct, slow): the
     # device counter every LSTM call carries is zeroed here and read after the timed region — it must still be 0
     ops.cluster_fallbacks(dev, reset=True)
     sync_all()
     t0 = time.perf_counter()
     for i in range(steps):
-        ev[i][0].record()
+        if ev:
+            ev[i][0].record()
         out = wl.step()
-        ev[i][1].record()
+        if ev:
+            ev[i][1].record()
     sync_all()
     dt_local = time.perf_counter() - t0
-    ops.timing_enable(False)
-    ops.timing_select(None)
-    kern = ops.timing_collect()
-    step_ms = sorted(a.elapsed_time(b) for a, b in ev)
-    log("config %d rank %d: timed %d steps in %.3f s (median step %.3f ms by HIP events)"
-        % (cfg, rank, steps, dt_local, step_ms[len(step_ms) // 2]))
+    assert out is not None
+    if full:
+        ops.timing_enable(False)
+        ops.timing_select(None)
+    if dump_dir and rank == 0:           # before anything else runs a step: `out` may live in a reused buffer
+        written = dump_outputs(wl.outputs(out), dump_dir)
+        log("config %d: outputs of the last timed step -> %s %s" % (cfg, dump_dir, written))
+    kern, step_ms = {}, []
+    if full:
+        kern = ops.timing_collect()
+        step_ms = sorted(a.elapsed_time(b) for a, b in ev)
+        log("config %d rank %d: timed %d steps in %.3f s (median step %.3f ms by HIP events)"
+            % (cfg, rank, steps, dt_local, step_ms[len(step_ms) // 2]))
+    else:
+        log("config %d rank %d: timed %d steps in %.3f s" % (cfg, rank, steps, dt_local))
     dt, per_rank = dt_local, [round(dt_local / steps * 1e3, 3)]
     if dist is not None:
         cdev = dev if backend == "nccl" else torch.device("cpu")
         tmax = torch.tensor([dt_local], dtype=torch.float64, device=cdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-        allt = [torch.zeros(1, dtype=torch.float64, device=cdev) for _ in range(world)]
-        dist.all_gather(allt, torch.tensor([dt_local], dtype=torch.float64, device=cdev))
-        per_rank = [round(float(t.item()) / steps * 1e3, 3) for t in allt]
-    assert out is not None
+        if full:
+            allt = [torch.zeros(1, dtype=torch.float64, device=cdev) for _ in range(world)]
+            dist.all_gather(allt, torch.tensor([dt_local], dtype=torch.float64, device=cdev))
+            per_rank = [round(float(t.item()) / steps * 1e3, 3) for t in allt]
     wl.check(out)
     fallbacks = ops.cluster_fallbacks(dev)
     if dist is not None:
@@ -943,8 +1021,7 @@ def run_workload(args, cfg, dev, rank, world, dist, backend, steps, warmup):
         fb = torch.tensor([fallbacks], dtype=torch.int64, device=cdev)
         dist.all_reduce(fb, op=dist.ReduceOp.SUM)
         fallbacks = int(fb.item())
-    peak_mem_gb = round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1)
-
+    peak_mem_gb = round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1) if full else None
     value = wl.frames_per_step * steps * world / dt
     roof = wl.roofline(kern) if roof_name else None      # from the events recorded inside the timed region
     if roof is not None:
@@ -957,7 +1034,7 @@ def run_workload(args, cfg, dev, rank, world, dist, backend, steps, warmup):
     breakdown = {k: {"ms_per_step": round(v["ms"] / probe_steps, 3), "launches_per_step": v["count"] / probe_steps,
                      "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] > 0 and v["flops"] else None}
                  for k, v in sorted(kern_all.items())}
-    extra = wl.extra(value, kern_all, probe_steps)
+    extra = wl.extra(value, kern_all, probe_steps) if full else {}
 
     # ---- evidence legs, after the timed region (never inside it) ---------------------------------------------
     # (a) the box's own fp32-MFMA ceiling: a 2 % difference between two boxes must not hide or fake a 2 % kernel gain
@@ -981,7 +1058,7 @@ def run_workload(args, cfg, dev, rank, world, dist, backend, steps, warmup):
     # (b) same-process A/B of the kernels this and the previous round changed (A = the shipped default, B = the knob):
     # alternating legs of a few steps each, so that box-to-box differences cancel
     ab = None
-    if args.ab_steps > 0 and hasattr(wl, "ab_knobs") and world == 1:
+    if full and args.ab_steps > 0 and hasattr(wl, "ab_knobs") and world == 1:
         ab = {}
         for label, env in wl.ab_knobs():
             legs = {"A": [], "B": []}
@@ -1013,7 +1090,7 @@ def run_workload(args, cfg, dev, rank, world, dist, backend, steps, warmup):
             log("A/B %s: A %s ms, B %s ms" % (label, legs["A"], legs["B"]))
     # (c) strong scaling: the same GLOBAL batch on one rank, same run, so that the line carries its own efficiency
     strong = None
-    if args.scaling == "strong" and hasattr(wl, "global_nb"):
+    if full and args.scaling == "strong" and hasattr(wl, "global_nb"):
         t1 = None
         if world > 1:
             if rank == 0:
@@ -1038,7 +1115,7 @@ def run_workload(args, cfg, dev, rank, world, dist, backend, steps, warmup):
                       "how": "value / (n_gpus x frames/s of ONE rank running the whole global batch in the same run)"}
 
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, parity = wl.cpu_baseline()
     failed = (parity is not None and not parity["ok"]) or fallbacks != 0
     if fallbacks:
@@ -1050,13 +1127,17 @@ def run_workload(args, cfg, dev, rank, world, dist, backend, steps, warmup):
             "metric": wl.metric, "value": None if failed else round(value, 2), "unit": "frames/s", "n_gpus": world,
             "steps": steps, "warmup": warmup, "ms_per_step": round(dt / steps * 1e3, 3),
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": wl.dtype, "data": "synthetic",
-            "config": wl.config(), "roofline": roof, "cpu_baseline": cpu, "parity": parity,
+            "config": wl.config(), "cluster_fallbacks": fallbacks,
+        }
+    if rank == 0 and full:
+        line.update({
+            "roofline": roof, "cpu_baseline": cpu, "parity": parity,
             "ms_per_step_median_hip_events": round(step_ms[len(step_ms) // 2], 3), "ms_per_step_per_rank": per_rank,
             "rccl_world_size": (dist.get_world_size() if backend == "nccl" else 0) if dist is not None else 1,
             "backend": backend if dist is not None else None,
-            "cluster_fallbacks": fallbacks, "peak_mem_gb": peak_mem_gb, "kernels": breakdown,
+            "peak_mem_gb": peak_mem_gb, "kernels": breakdown,
             "kernels_source": "separate instrumented pass of %d steps (every launch bracketed); the timed region brackets only the roofline kernel" % probe_steps,
-        }
+        })
         line.update(extra)
         if ab:
             line["ab"] = ab
@@ -1081,10 +1162,17 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", type=int, default=2, choices=sorted(WORKLOADS), help="BASELINE.json configuration")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: instrumented per-kernel pass and roofline, fp32-MFMA "
+                         "calibration, A/B legs, CPU baseline + parity, strong-scaling efficiency, nested other "
+                         "configurations, the detail file (default: off, a lean timed run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--other-configs", default=None,
-                    help="comma-separated configurations measured AFTER the primary one and nested under 'other_configs' "
-                         "of the same JSON line (default: 3,4,5 when the primary is the default config-2 headline run; "
-                         "'' = none); each runs its own BASELINE batch for at most --other-steps steps")
+                    help="--full: comma-separated configurations measured AFTER the primary one and nested under "
+                         "'other_configs' of the same JSON line (default: 2M,2off,2b1,2s,3,4,5 when the primary is the "
+                         "default config-2 headline run; '' = none); each runs its own BASELINE batch for at most "
+                         "--other-steps steps")
     ap.add_argument("--other-steps", type=int, default=8)
     ap.add_argument("--nb", type=int, default=0, help="utterances per GPU (default: the configuration's batch)")
     ap.add_argument("--nch", type=int, default=4)
@@ -1103,24 +1191,31 @@ def main():
                     help="config 4: the step through torch.autograd.Function + torch.optim.Adam (+ DDP with N > 1): the reference's own loop")
     ap.add_argument("--features-in", action="store_true",
                     help="config 5: start from features [B, 30, 256, T] already in HBM (round-2 behaviour) instead of waveforms")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline + parity legs")
     ap.add_argument("--cpu-utts", type=int, default=1, help="utterances in the bounded CPU sample (config 2)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target CPU time of the bounded sample (config 2)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank runs the configuration's batch (default); strong: the configuration's batch is the "
                          "GLOBAL batch, split evenly over the ranks (config 2; the line then carries strong_scaling.efficiency)")
     ap.add_argument("--ab-steps", type=int, default=-1,
-                    help="steps per leg of the same-process A/B legs run after the timed region (config 2; default 3 in the "
-                         "plain default run, else 0)")
+                    help="--full: steps per leg of the same-process A/B legs run after the timed region (config 2; default 3 "
+                         "in the --full run of the default shape, else 0)")
     ap.add_argument("--sustained-seconds", type=float, default=-1.0,
-                    help="length of the sustained fp32-MFMA calibration after the timed region (roofline.peak_measured_sustained; "
+                    help="--full: length of the sustained fp32-MFMA calibration after the timed region (roofline.peak_measured_sustained; "
                          "default 2 s for the primary configuration of a one-rank run, 0 = off)")
     ap.add_argument("--detail", default=os.path.join("gpurun_out", "bench_detail.json"),
-                    help="where the FULL record of the run goes (per-kernel tables, A/B legs, nested configurations in full); "
+                    help="--full: where the FULL record of the run goes (per-kernel tables, A/B legs, nested configurations in full); "
                          "stdout carries the compact line (< 4 KB) only.  Relative paths are taken from the repo root")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        asked = [flag for flag, on in (("--other-configs", bool(args.other_configs)), ("--ab-steps", args.ab_steps > 0),
+                                       ("--sustained-seconds", args.sustained_seconds > 0)) if on]
+        if asked:
+            raise SystemExit("%s: measured only with --full" % ", ".join(asked))
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)           # does not return
@@ -1156,19 +1251,20 @@ def main():
                                                              dist.get_world_size()))
 
     others = args.other_configs
-    plain = not (args.nb or args.offline or args.bf16 or args.frames != 300 or args.nch != 4 or args.ch_mode != "MM"
-                 or args.chunk_pairs or args.stream_chunk) and args.scaling == "weak" and args.config == 2
+    headline_shape = not (args.nb or args.offline or args.bf16 or args.frames != 300 or args.nch != 4 or args.ch_mode != "MM"
+                          or args.chunk_pairs or args.stream_chunk) and args.scaling == "weak" and args.config == 2
     if others is None:
-        others = "2M,2off,2b1,2s,3,4,5" if plain else ""
+        others = "2M,2off,2b1,2s,3,4,5" if (headline_shape and args.full) else ""
     if args.ab_steps < 0:
-        args.ab_steps = 3 if plain else 0
+        args.ab_steps = 3 if (headline_shape and args.full) else 0
     if args.sustained_seconds < 0:
         args.sustained_seconds = 2.0
     if args.scaling == "strong" and args.config != 2:
         raise SystemExit("--scaling strong is defined for config 2 (the fixed global batch of the headline)")
     other_ids = [c.strip() for c in others.split(",") if c.strip()]
 
-    line, failed = run_workload(args, args.config, dev, rank, world, dist, backend, args.steps, args.warmup)
+    line, failed = run_workload(args, args.config, dev, rank, world, dist, backend, args.steps, args.warmup,
+                                dump_dir=args.dump_outputs)
     nested = {}
     for key in other_ids:
         # "2M" / "2off": SURVEY 8d's secondary reports of config 2 — 'M' pairing (np = 3) and is_online=False — as their
@@ -1208,7 +1304,9 @@ def main():
             line["other_configs"] = nested
         # the full record (per-kernel tables, A/B legs, prose) goes to the detail file; stdout gets the compact line only:
         # the driver keeps ~10 KB of stdout, and a line it cannot parse is an unmeasured round
-        detail = write_detail(line, args.detail if os.path.isabs(args.detail) else os.path.join(ROOT, args.detail))
+        detail = None
+        if args.full:
+            detail = write_detail(line, args.detail if os.path.isabs(args.detail) else os.path.join(ROOT, args.detail))
         small = compact_line(line, os.path.relpath(detail, ROOT) if detail else None)
         log("headline: %s frames/s, %.3f ms/step, roofline frac %s, cpu_baseline %s; detail -> %s"
             % (small["value"], small["ms_per_step"], (small.get("roofline") or {}).get("frac"),

@@ -275,7 +275,7 @@ def test_bench_self_launches_n_ranks(tmp_path):
     env["FNSSL_BENCH_SHARED_GPU"] = "1"
     for cfg, extra in ((2, ["--nb", "2", "--frames", "24"]), (4, ["--nb", "2", "--frames", "24"])):
         res = subprocess.run([sys.executable, bench, "--gpus", "2", "--config", str(cfg), "--steps", "2", "--warmup", "1",
-                              "--other-configs", ""] + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                              "--full", "--other-configs", ""] + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                              text=True, timeout=900)
         assert res.returncode == 0, res.stderr[-2000:]
         lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -291,7 +291,7 @@ def test_bench_self_launches_n_ranks(tmp_path):
     # strong scaling: the configuration's batch is the GLOBAL batch, split over the ranks; the line carries its
     # own efficiency against one rank running the whole batch in the same run
     res = subprocess.run([sys.executable, bench, "--gpus", "2", "--config", "2", "--scaling", "strong", "--steps", "2", "--warmup", "1",
-                          "--nb", "2", "--frames", "24"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+                          "--full", "--nb", "2", "--frames", "24"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.strip()][0])
     assert line["scaling"] == "strong" and line["n_gpus"] == 2 and "other_configs" not in line
@@ -299,3 +299,42 @@ def test_bench_self_launches_n_ranks(tmp_path):
     assert abs(line["value"] - 2 * 24 / (line["ms_per_step"] * 1e-3)) <= 1e-3 * line["value"] + 0.01
     ss = line["strong_scaling"]
     assert ss["global_batch"] == 2 and ss["utterances_per_rank"] == 1 and 0.0 < ss["efficiency"] < 4.0
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (no --full) times exactly K steps and prints the contract keys
+    without the --full legs (roofline, CPU baseline + parity, nested configurations, detail file); --dump-outputs DIR
+    writes the last timed step's output as float32 DIR/dp_ipd.npy, and a second run with the same arguments (same
+    seeded inputs and weights) writes the same values."""
+    import json
+    import subprocess
+    if not torch.cuda.is_available():
+        pytest.fail("-m gpu tests need a ROCm device")
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "FNSSL_BENCH_SHARED_GPU"):
+        env.pop(k, None)
+    bench = os.path.join(ROOT, "bench.py")
+    dumps = []
+    for run in range(2):
+        out_dir = str(tmp_path / ("run%d" % run))
+        res = subprocess.run([sys.executable, bench, "--gpus", "1", "--steps", "3", "--warmup", "1", "--nb", "2",
+                              "--frames", "24", "--dump-outputs", out_dir], env=env, stdout=subprocess.PIPE,
+                             stderr=subprocess.PIPE, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, res.stdout[-500:]
+        line = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+            assert k in line, k
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["dtype"] == "f32"
+        assert line["unit"] == "frames/s" and line["higher_is_better"] is True and line["cluster_fallbacks"] == 0
+        assert line["value"] > 0 and line["ms_per_step"] > 0
+        assert abs(line["value"] - 2 * 24 / (line["ms_per_step"] * 1e-3)) <= 1e-3 * line["value"] + 0.01
+        assert line.get("roofline") is None and line.get("cpu_baseline") is None and line.get("parity") is None
+        assert "other_configs" not in line and "detail" not in line and "ab_gain_pct" not in line
+        assert "timed 3 steps" in res.stderr
+        assert sorted(os.listdir(out_dir)) == ["dp_ipd.npy"]
+        got = np.load(os.path.join(out_dir, "dp_ipd.npy"))
+        assert got.dtype == np.float32 and got.shape == (2 * 6, 2, 512) and np.isfinite(got).all()
+        dumps.append(got)
+    assert_close(dumps[1], dumps[0], 1e-5, 1e-6, "second run's dump")

@@ -410,6 +410,52 @@ def test_bench_stdout_line_is_compact_and_carries_the_contract(tmp_path):
     assert small["roofline"]["peak_measured_sustained"] == 151.3 and small["roofline"]["slowest_xcd_mhz"] == 2238.1
 
 
+def test_bench_dump_outputs_float32_capped_and_seeded(tmp_path):
+    """bench.py --dump-outputs: every output lands as <name>.npy in float32 (float64 kept); when the outputs exceed the
+    cap, each is cut to the same share of its flat entries, picked by a fixed seed — two dumps sample the same entries —
+    and the files together stay under the cap."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("fnssl_bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    import torch
+    a = torch.arange(6 * 5, dtype=torch.float16).reshape(6, 5)
+    b = np.linspace(0.0, 1.0, 7)
+    info = bench.dump_outputs({"a": a, "b": b}, str(tmp_path / "small"))
+    assert info == {"a": ((6, 5), 30), "b": ((7,), 7)}
+    got_a, got_b = np.load(str(tmp_path / "small" / "a.npy")), np.load(str(tmp_path / "small" / "b.npy"))
+    assert got_a.dtype == np.float32 and got_b.dtype == np.float64
+    np.testing.assert_array_equal(got_a, a.float().numpy())
+    np.testing.assert_array_equal(got_b, b)
+    big = {"x": np.arange(200000, dtype=np.float32).reshape(400, 500), "y": -np.arange(100000, dtype=np.float32)}
+    limit = 8192 + 4 * 150000
+    sampled = []
+    for run in range(2):
+        d = tmp_path / ("big%d" % run)
+        info = bench.dump_outputs(big, str(d), limit=limit)
+        assert sum(os.path.getsize(str(d / f)) for f in os.listdir(str(d))) <= limit
+        assert info["x"][0] == (400, 500) and 0 < info["x"][1] < 200000 and 0 < info["y"][1] < 100000
+        x = np.load(str(d / "x.npy"))
+        assert x.ndim == 1 and (np.diff(x) > 0).all()            # sorted, distinct entries of the flat output
+        sampled.append((x, np.load(str(d / "y.npy"))))
+    np.testing.assert_array_equal(sampled[0][0], sampled[1][0])
+    np.testing.assert_array_equal(sampled[0][1], sampled[1][1])
+
+
+def test_bench_full_only_options_need_full():
+    """The legs beyond the headline run only with --full: asking a plain run for them is an error, not a silent no-op."""
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    for extra in (["--ab-steps", "3"], ["--other-configs", "3"], ["--sustained-seconds", "2"]):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + extra, env=env,
+                             stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+        assert res.returncode != 0 and res.stdout.strip() == "", (extra, res.returncode)
+        assert "only with --full" in res.stderr, res.stderr[-500:]
+
+
 def test_launch_planner_picks_the_cheapest_rounds():
     """The launch planner of fnssl_lstm_forward (host logic, queried without a GPU): a round costs one wave-time per
     wave on its fullest SIMD, so config 2's full-band layers (57 600 sequences x 2 directions = 7 200 wave tasks on 256

@@ -7,9 +7,9 @@ if [ "$1" != "quick" ]; then
   timeout 1500 python -m pytest tests -q -m gpu -p no:cacheprovider 2>&1 | tail -4 > $O/pytest.log
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 fi
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench.err
 export TMPDIR=/tmp; cd /tmp
-timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r1 -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --ab-steps 0 > $O/prof.log 2>&1
+timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r1 -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --ab-steps 0 > $O/prof.log 2>&1
 cp $(ls $O/prof/*kernel_stats.csv | head -1) $O/kernel_stats_bench_default_steps3.csv; rm -rf $O/prof
 for cfg in 2 3 4 5; do
   for c in FETCH_SIZE WRITE_SIZE; do

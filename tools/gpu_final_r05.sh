@@ -7,10 +7,10 @@ if [ "$1" != "quick" ]; then
   timeout 1500 python -m pytest tests -q -m gpu -p no:cacheprovider 2>&1 | tail -4 > $O/pytest.log
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 fi
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench.err
 timeout 300 python tools/latency_bench.py --json $O/latency.json > $O/latency.txt 2>&1
 export TMPDIR=/tmp; cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r1 -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --ab-steps 0 > $O/prof.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r1 -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --ab-steps 0 > $O/prof.log 2>&1
 cp $(ls $O/prof/*kernel_stats.csv | head -1) $O/kernel_stats_bench_default_steps3.csv; rm -rf $O/prof
 PAT="lstm_static3|lstm_bf16c_kernel<256|lstm_bwd2_kernel<256|sn_mamba_scan|lstm_f32c_kernel<256|lstm_f32c_kernel<128"
 pmc() {  # tag, bench arguments

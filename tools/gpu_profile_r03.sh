@@ -2,9 +2,9 @@
 # default bench line, rocprofv3 kernel stats of the SAME command, HBM-side traffic of the H = 256 LSTM kernel (FETCH_SIZE and
 # WRITE_SIZE in SEPARATE --pmc passes, MI355X_MICROARCH.md "rocprofv3 PMC slots"), SQ counters of the training kernels.
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/final3; mkdir -p $O; cd $R
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 export TMPDIR=/tmp; cd /tmp
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r1 -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/prof.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r1 -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $O/prof.log 2>&1
 cp $(ls $O/prof/*kernel_stats.csv | head -1) $O/kernel_stats_bench_default_steps3.csv; rm -rf $O/prof
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 300 rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -o p -- python $R/bench.py --config 2 --steps 1 --warmup 1 --no-cpu-baseline --other-configs "" > $O/pmc_$c.log 2>&1

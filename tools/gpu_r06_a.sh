@@ -6,7 +6,7 @@ if [ "$1" != "quick" ]; then
   timeout 1500 python -m pytest tests -q -m gpu -p no:cacheprovider -x 2>&1 | tail -15 > $O/pytest.log
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 fi
-timeout 900 python bench.py --steps 20 --warmup 5 --detail gpurun_out/r06a/bench_detail.json > $O/bench_default.json 2> $O/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 --detail $O/bench_detail.json > $O/bench_default.json 2> $O/bench.err
 wc -c $O/bench_default.json
 export TMPDIR=/tmp; cd /tmp
 PAT="lstm_bf16c_kernel|conv3x3_bf16|lstm_bf16"
