@@ -12,8 +12,9 @@ constructor arguments, ``forward`` signatures, return shapes and ``state_dict`` 
 
 Against the reference's dataflow nothing is concatenated or permuted in memory: the concat skips
 (:34, :38) are a second operand segment of the consuming LSTM / conv kernel, the permutes are strides.
-``nn.LSTM`` / ``nn.Conv2d`` sub-modules only hold parameters.  Forward-only (``eval()``), ROCm tensors
-only.  fp32 by default; after ``net.bfloat16()`` (BASELINE config 3: bf16 weights, fp32 accumulate) the LSTM
+``nn.LSTM`` / ``nn.Conv2d`` sub-modules only hold parameters.  ROCm tensors only.  ``IPDnet.forward`` also trains:
+in ``train()`` mode, at ``hidden_size=256`` in fp32, it returns a tensor with a ``grad_fn`` (fnssl/ipdnet_train.py);
+every other entry, and every other configuration in train mode, is forward-only (``eval()``).  fp32 by default; after ``net.bfloat16()`` (BASELINE config 3: bf16 weights, fp32 accumulate) the LSTM
 layers run on bf16 MFMAs — weights and the [x | h] operands rounded to bf16, gates / cell state / every
 tensor in HBM fp32 — and the conv head uses the bf16-rounded weights; inputs of either dtype are accepted and
 the output comes back in the input's dtype.
@@ -28,7 +29,7 @@ _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
-from fnssl import ops                                               # noqa: E402
+from fnssl import ipdnet_train, ops                                 # noqa: E402
 from Model import _lstm_streams, _param_key, _require_eval          # noqa: E402
 
 
@@ -297,6 +298,8 @@ class IPDnet(nn.Module):
 
     @ops.on_device
     def forward(self, x, offline_inference=False):
+        if self.training and ipdnet_train.supported(self, offline_inference):
+            return ipdnet_train.train_forward(self, x)             # autograd route (fnssl/ipdnet_train.py)
         _require_eval(self)
         in_dtype = x.dtype
         x = x.float()                                               # tensors in HBM are fp32 in both precisions

@@ -39,7 +39,9 @@ struct ConvParams {
 // blocks, then 4-channel remainder blocks).  One k-step = NR records (NR = NT/4; one record =
 // float4 per lane = the A operands of 4 output-channel tiles); records are grouped in quads of 4,
 // a remainder k-step occupies a whole quad.
-template <int NT, int NW, int M>
+// ANTI: the anti-causal twin the input gradient runs on (conv_train.hip): tap dt reads time t + 2 - dt, zero past the
+// last frame; with the transposed, bin-flipped weight stream of fnssl_conv3x3_pack_backward_data it computes dX.
+template <int NT, int NW, int M, bool ANTI = false>
 __global__ void __launch_bounds__(NW * 64) conv3x3_kernel(const ConvParams p) {
   static_assert(NT == 4 || NT == 8, "4 or 8 output-channel tiles");
   constexpr int NR = NT / 4;
@@ -80,8 +82,8 @@ __global__ void __launch_bounds__(NW * 64) conv3x3_kernel(const ConvParams p) {
       const bool frow = ff >= 0 && ff < p.nf;          // wave-uniform: zero padding in frequency
       const int fc = frow ? ff : f;
       for (int dt = 0; dt < 3; ++dt) {
-        int ts = tpos + dt - 2;                          // source time of this lane
-        const bool live = frow && ts >= 0;               // zero padding on the causal side
+        int ts = ANTI ? tpos + 2 - dt : tpos + dt - 2;   // source time of this lane
+        const bool live = frow && (ANTI ? ts < p.nt : ts >= 0);   // zero padding on the causal side
         ts = ts < 0 ? 0 : (ts >= p.nt ? p.nt - 1 : ts);
         const unsigned offa = (unsigned)(((long long)fc * p.a_sf + (long long)ts * p.a_st) * 4) + 16 * g;
         const unsigned offb = (unsigned)(((long long)fc * p.b_sf + (long long)ts * p.b_st) * 4);
@@ -414,13 +416,13 @@ int fnssl_conv3x3_pack_bf16(const float* w, int cout, int ca, int cb, float* pac
   return FNSSL_OK;
 }
 
-static int conv_run(int bf, const float* xa, long long a_sb, long long a_sf, long long a_st, int ca, const float* xb,
+static int conv_run(int bf, bool anti, const float* xa, long long a_sb, long long a_sf, long long a_st, int ca, const float* xb,
                     long long b_sb, long long b_sf, long long b_st, int cb, const float* wpack, int cout, int nb,
                     int nf, int nt, int act, float* out, int cout_stride, void* stream) {
   FNSSL_REQUIRE(xa && wpack && out, "conv3x3: null pointer");
   FNSSL_REQUIRE(nb > 0 && nf > 0 && nt > 0, "conv3x3: empty problem");
   FNSSL_REQUIRE((bf ? fnssl_conv3x3_packed_floats_bf16(cout, ca, cb) : fnssl_conv3x3_packed_floats(cout, ca, cb)) > 0 &&
-                    ca > 0,
+                    (ca > 0 || anti),
                 "conv3x3: unsupported channel counts");
   FNSSL_REQUIRE(cb == 0 || xb, "conv3x3: segment B missing");
   FNSSL_REQUIRE(cout_stride >= cout && cout_stride % 4 == 0 && act >= 0 && act <= 2, "conv3x3: bad output spec");
@@ -466,7 +468,7 @@ static int conv_run(int bf, const float* xa, long long a_sb, long long a_sf, lon
   p.passes = (groups + nwg - 1) / nwg;
   const size_t lds = (size_t)2 * p.chq * 4096;
   const double flops = 2.0 * 9 * (ca + cb) * (double)cout * nb * nf * (double)nt;
-  fnssl::TimedLaunch tl(bf ? "conv3x3_bf16" : "conv3x3", fnssl::as_stream(stream), flops);
+  fnssl::TimedLaunch tl(bf ? "conv3x3_bf16" : (anti ? "conv3x3_dgrad" : "conv3x3"), fnssl::as_stream(stream), flops);
   if (bf == 2) {
     if (NT == 8) {
       auto k = conv3x3_bf16_kernel<8, NW, M, true>;
@@ -491,6 +493,11 @@ static int conv_run(int bf, const float* xa, long long a_sb, long long a_sf, lon
         FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, fnssl::as_stream(stream), p);
     }
+  } else if (anti) {
+    auto k = NT == 8 ? conv3x3_kernel<8, NW, M, true> : conv3x3_kernel<4, NW, M, true>;
+    if (lds > 48 * 1024)
+      FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, fnssl::as_stream(stream), p);
   } else if (NT == 8) {
     auto k = conv3x3_kernel<8, NW, M>;
     if (lds > 48 * 1024)
@@ -509,14 +516,14 @@ static int conv_run(int bf, const float* xa, long long a_sb, long long a_sf, lon
 int fnssl_conv3x3_causal(const float* xa, long long a_sb, long long a_sf, long long a_st, int ca, const float* xb,
                          long long b_sb, long long b_sf, long long b_st, int cb, const float* wpack, int cout,
                          int nb, int nf, int nt, int act, float* out, int cout_stride, void* stream) {
-  return conv_run(0, xa, a_sb, a_sf, a_st, ca, xb, b_sb, b_sf, b_st, cb, wpack, cout, nb, nf, nt, act, out,
+  return conv_run(0, false, xa, a_sb, a_sf, a_st, ca, xb, b_sb, b_sf, b_st, cb, wpack, cout, nb, nf, nt, act, out,
                   cout_stride, stream);
 }
 
 int fnssl_conv3x3_causal_bf16(const float* xa, long long a_sb, long long a_sf, long long a_st, int ca, const float* xb,
                               long long b_sb, long long b_sf, long long b_st, int cb, const float* wpack, int cout,
                               int nb, int nf, int nt, int act, float* out, int cout_stride, void* stream) {
-  return conv_run(1, xa, a_sb, a_sf, a_st, ca, xb, b_sb, b_sf, b_st, cb, wpack, cout, nb, nf, nt, act, out,
+  return conv_run(1, false, xa, a_sb, a_sf, a_st, ca, xb, b_sb, b_sf, b_st, cb, wpack, cout, nb, nf, nt, act, out,
                   cout_stride, stream);
 }
 
@@ -524,9 +531,24 @@ int fnssl_conv3x3_causal_bf16a(const void* xa_bf16, long long a_sb, long long a_
                                const float* xb, long long b_sb, long long b_sf, long long b_st, int cb,
                                const float* wpack, int cout, int nb, int nf, int nt, int act, float* out,
                                int cout_stride, void* stream) {
-  return conv_run(2, static_cast<const float*>(xa_bf16), a_sb, a_sf, a_st, ca, xb, b_sb, b_sf, b_st, cb, wpack, cout, nb, nf,
+  return conv_run(2, false, static_cast<const float*>(xa_bf16), a_sb, a_sf, a_st, ca, xb, b_sb, b_sf, b_st, cb, wpack, cout, nb, nf,
                   nt, act, out, cout_stride, stream);
 }
+
+}  // extern "C"
+
+namespace fnssl {
+// The anti-causal fp32 conv (input gradient of fnssl_conv3x3_causal, driven by conv_train.hip): same validation and
+// launch geometry as the forward, output channels = the input channels that receive a gradient.
+int conv3x3_anticausal_f32(const float* xa, long long a_sb, long long a_sf, long long a_st, int ca, const float* xb,
+                           long long b_sb, long long b_sf, long long b_st, int cb, const float* wpack, int cout, int nb,
+                           int nf, int nt, float* out, int cout_stride, void* stream) {
+  return conv_run(0, true, xa, a_sb, a_sf, a_st, ca, xb, b_sb, b_sf, b_st, cb, wpack, cout, nb, nf, nt, 0, out,
+                  cout_stride, stream);
+}
+}  // namespace fnssl
+
+extern "C" {
 
 int fnssl_avgpool_time(const float* x, int rows, int nt, int c, int k, float* y, void* stream) {
   FNSSL_REQUIRE(x && y && rows > 0 && nt > 0 && c > 0 && c % 4 == 0 && k > 0, "avgpool_time: bad arguments");

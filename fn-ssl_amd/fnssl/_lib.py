@@ -48,6 +48,8 @@ SYMBOLS = [
     "fnssl_conv3x3_causal_bf16", "fnssl_conv3x3_causal_bf16a",
     "fnssl_conv3x3_packed_bytes_bf16x", "fnssl_conv3x3_pack_bf16x", "fnssl_conv3x3_causal_bf16x",
     "fnssl_avgpool_time_bf16",
+    "fnssl_conv3x3_packed_floats_backward_data", "fnssl_conv3x3_pack_backward_data", "fnssl_conv3x3_act_pool_backward",
+    "fnssl_conv3x3_causal_backward_data", "fnssl_conv3x3_weight_grads_workspace_bytes", "fnssl_conv3x3_weight_grads",
     "fnssl_lstm_reserve_bytes", "fnssl_lstm_bwd_packed_floats", "fnssl_lstm_pack_bwd", "fnssl_lstm_bwd_workspace_bytes",
     "fnssl_lstm_backward", "fnssl_lstm_backward_plan", "fnssl_lstm_backward_status", "fnssl_lstm_weight_grads_workspace_bytes", "fnssl_lstm_weight_grads", "fnssl_lstm_packed_floats_bf16", "fnssl_lstm_pack_bf16", "fnssl_train_combine", "fnssl_dropout_scale", "fnssl_head_backward_workspace_bytes",
     "fnssl_head_backward", "fnssl_mse_loss", "fnssl_adam_step",
@@ -265,6 +267,15 @@ def load():
     lib.fnssl_conv3x3_pack_bf16x.argtypes = [vp, i, i, i, vp]
     lib.fnssl_conv3x3_causal_bf16x.argtypes = [vp, ll, ll, ll, i, vp, ll, ll, ll, i, vp, i, i, i, i, i, i, i, vp, i, vp]
     lib.fnssl_avgpool_time_bf16.argtypes = [vp, i, i, i, i, vp, vp]
+    lib.fnssl_conv3x3_packed_floats_backward_data.argtypes = [i, i, i]
+    lib.fnssl_conv3x3_packed_floats_backward_data.restype = sz
+    lib.fnssl_conv3x3_pack_backward_data.argtypes = [vp, i, i, i, vp]
+    lib.fnssl_conv3x3_act_pool_backward.argtypes = [vp, vp, i, i, i, i, i, i, vp, vp]
+    lib.fnssl_conv3x3_causal_backward_data.argtypes = [vp, ll, ll, ll, i, vp, i, i, i, i, vp, i, vp]
+    lib.fnssl_conv3x3_weight_grads_workspace_bytes.argtypes = [i, i, i, i, i, i]
+    lib.fnssl_conv3x3_weight_grads_workspace_bytes.restype = sz
+    lib.fnssl_conv3x3_weight_grads.argtypes = [vp, ll, ll, ll, i, vp, ll, ll, ll, i, vp, ll, ll, ll, i, i, i, i, vp, vp, sz,
+                                               vp]
     lib.fnssl_forward_workspace_bytes.argtypes = [i, i, i, i, i]
     lib.fnssl_forward_workspace_bytes.restype = sz
     lib.fnssl_forward.argtypes = [C.POINTER(Net), vp, i, i, i, vp, vp, sz, i, vp]

@@ -781,6 +781,94 @@ def avgpool_time(x, k: int, bf16_out: bool = False):
     return y
 
 
+def pack_conv3x3_backward_data(weight, cin_g: int, device) -> torch.Tensor:
+    """Pack a Conv2d weight [cout, cin, 3, 3] (transposed, bin-flipped) for ``conv3x3_causal_backward_data`` — the
+    gradient of the first ``cin_g`` input channels."""
+    w = np.ascontiguousarray(weight.detach().float().cpu().numpy() if isinstance(weight, torch.Tensor) else weight,
+                             dtype=np.float32)
+    if w.ndim != 4 or w.shape[2:] != (3, 3):
+        raise RuntimeError("fnssl.pack_conv3x3_backward_data: weight shape %s is not [cout, cin, 3, 3]" % (w.shape,))
+    cout, cin = w.shape[:2]
+    lib = _lib.load()
+    n = lib.fnssl_conv3x3_packed_floats_backward_data(cout, cin, cin_g)
+    if n == 0:
+        raise RuntimeError("fnssl.pack_conv3x3_backward_data: unsupported sizes cout=%d cin=%d cin_g=%d" % (cout, cin, cin_g))
+    out = np.empty(n, dtype=np.float32)
+    check(lib.fnssl_conv3x3_pack_backward_data(w.ctypes.data_as(C.c_void_p), cout, cin, cin_g,
+                                               out.ctypes.data_as(C.c_void_p)), "conv3x3_pack_backward_data")
+    return torch.from_numpy(out).to(device)
+
+
+def _chlast(t, what):
+    """A logical [nb, nf, nt, C] fp32 device tensor with a contiguous channel dimension, 16-byte aligned, strides
+    multiples of 4 floats (else a copy: plumbing only)."""
+    if t.dim() != 4 or t.dtype != torch.float32:
+        raise RuntimeError("fnssl.%s: expected a 4-D float32 tensor, got %s %s" % (what, tuple(t.shape), t.dtype))
+    return _conform(t)
+
+
+@on_device
+def conv3x3_act_pool_backward(dp, y, k: int, act: str):
+    """Activation + AvgPool2d((1, k)) backward of one CausCnnBlock stage: y [nb, nf, nt, C] (saved post-activation
+    output), dp [nb, nf, nt // k, C] -> dz [nb, nf, nt, C] (pre-activation gradient), all channels-last."""
+    _need_dev(dp, y)
+    y, dp = y.contiguous(), dp.contiguous()
+    nb, nf, nt, c = y.shape
+    if tuple(dp.shape) != (nb, nf, nt // k, c):
+        raise RuntimeError("fnssl.conv3x3_act_pool_backward: dp %s does not match y %s pooled by %d"
+                           % (tuple(dp.shape), tuple(y.shape), k))
+    dz = torch.empty_like(y)
+    check(_lib.load().fnssl_conv3x3_act_pool_backward(_ptr(dp), _ptr(y), nb, nf, nt, c, k,
+                                                      {"none": 0, "relu": 1, "tanh": 2}[act], _ptr(dz), _stream()),
+          "conv3x3_act_pool_backward")
+    return dz
+
+
+@on_device
+def conv3x3_causal_backward_data(dz, packed, cin_g: int, out=None):
+    """Input gradient of ``conv3x3_causal`` for its first ``cin_g`` input channels.  dz: the pre-activation gradient,
+    logical [nb, nf, nt, cout] (any batch / bin / time strides); ``packed`` from ``pack_conv3x3_backward_data``.
+    Returns (or writes into ``out``, a contiguous [nb, nf, nt, >= cin_g] tensor) dx [nb, nf, nt, cin_g]."""
+    _need_dev(dz, packed, out)
+    dz = _chlast(dz, "conv3x3_causal_backward_data")
+    nb, nf, nt, cout = dz.shape
+    if out is None:
+        out = torch.empty((nb, nf, nt, cin_g), dtype=torch.float32, device=dz.device)
+    if tuple(out.shape[:3]) != (nb, nf, nt) or out.shape[3] < cin_g or not out.is_contiguous():
+        raise RuntimeError("fnssl.conv3x3_causal_backward_data: out must be a contiguous [%d, %d, %d, >= %d] tensor"
+                           % (nb, nf, nt, cin_g))
+    s = dz.stride()
+    check(_lib.load().fnssl_conv3x3_causal_backward_data(_ptr(dz), s[0], s[1], s[2], cout, _ptr(packed), cin_g, nb, nf,
+                                                         nt, _ptr(out), out.shape[3], _stream()),
+          "conv3x3_causal_backward_data")
+    return out
+
+
+@on_device
+def conv3x3_weight_grads(dz, xa, xb, grad):
+    """grad [cout, ca + cb, 3, 3] += the weight gradient of ``conv3x3_causal(xa, xb, ...)`` given its pre-activation
+    gradient dz [nb, nf, nt, cout]; xa / xb / dz logical [nb, nf, nt, C] with any batch / bin / time strides."""
+    _need_dev(dz, xa, xb, grad)
+    dz = _chlast(dz, "conv3x3_weight_grads")
+    xa = _chlast(xa, "conv3x3_weight_grads")
+    xb = _chlast(xb, "conv3x3_weight_grads") if xb is not None else None
+    nb, nf, nt, cout = dz.shape
+    ca = xa.shape[3]
+    cb = 0 if xb is None else xb.shape[3]
+    if tuple(xa.shape[:3]) != (nb, nf, nt) or (xb is not None and tuple(xb.shape[:3]) != (nb, nf, nt)):
+        raise RuntimeError("fnssl.conv3x3_weight_grads: xa / xb must match dz's [nb, nf, nt]")
+    if tuple(grad.shape) != (cout, ca + cb, 3, 3) or not grad.is_contiguous() or grad.dtype != torch.float32:
+        raise RuntimeError("fnssl.conv3x3_weight_grads: grad must be a contiguous fp32 [%d, %d, 3, 3]" % (cout, ca + cb))
+    lib = _lib.load()
+    ws = _workspace(lib.fnssl_conv3x3_weight_grads_workspace_bytes(nb, nf, nt, cout, ca, cb), dz.device, "conv_wgrad")
+    sz, sa = dz.stride(), xa.stride()
+    sb_ = xb.stride() if xb is not None else (0, 0, 0, 1)
+    check(lib.fnssl_conv3x3_weight_grads(_ptr(dz), sz[0], sz[1], sz[2], cout, _ptr(xa), sa[0], sa[1], sa[2], ca,
+                                         _ptr(xb) if xb is not None else None, sb_[0], sb_[1], sb_[2], cb, nb, nf, nt,
+                                         _ptr(grad), _ptr(ws), ws.numel(), _stream()), "conv3x3_weight_grads")
+    return grad
+
+
 @on_device
 def lstm_weight_grads(da, x0, x2, h, hidden: int, ndir: int, nsteps: int, g_wih, g_whh, g_bih, g_bhh):
     """Accumulate one LSTM layer's weight gradients (``fnssl_lstm_weight_grads``, csrc/wgrad.hip): g_wih[d] [4H, c0+c2]

@@ -671,6 +671,42 @@ int fnssl_conv3x3_causal_bf16x(const void* xa_bf16, long long a_sb, long long a_
 int fnssl_avgpool_time_bf16(const float* x, int rows, int nt, int c, int k, void* y_bf16, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Backward of the IPDnet conv head (training; csrc/conv_train.hip)           */
+/* ------------------------------------------------------------------------- */
+
+/* Floats of the input-gradient weight stream of Conv2d(cin -> cout, 3x3) for the first cin_g input channels;
+ * 0 if unsupported (4 <= cout, cout % 4 == 0, 0 < cin_g <= cin, cin_g % 4 == 0). */
+size_t fnssl_conv3x3_packed_floats_backward_data(int cout, int cin, int cin_g);
+
+/* Host-only: pack W [cout, cin, 3, 3] transposed and bin-flipped (one stream per 128 input channels) for
+ * fnssl_conv3x3_causal_backward_data. */
+int fnssl_conv3x3_pack_backward_data(const float* w, int cout, int cin, int cin_g, float* packed);
+
+/* Activation + AvgPool2d((1, k)) backward of one CausCnnBlock stage, all contiguous channels-last:
+ * dz[b, f, t, :] = act'(y[b, f, t, :]) * (t < k * (nt / k) ? dp[b, f, t / k, :] / k : 0)
+ *   y [nb, nf, nt, c] = the post-activation output saved by the forward, dp [nb, nf, nt / k, c];
+ *   act: 0 none, 1 ReLU (y > 0), 2 tanh (1 - y^2);  k = 1: no pooling;  c % 4 == 0. */
+int fnssl_conv3x3_act_pool_backward(const float* dp, const float* y, int nb, int nf, int nt, int c, int k, int act,
+                                    float* dz, void* stream);
+
+/* Input gradient of fnssl_conv3x3_causal for its first cin_g input channels:
+ * dx[b, f, t, i] = sum_{df, dt, co} W[co, i, df, dt] * dz[b, f+1-df, t+2-dt, co]   (zero outside the tensor),
+ * dz = the pre-activation gradient [nb, nf, nt, cout] (element (b, f, t, c) at dz[b*z_sb + f*z_sf + t*z_st + c]),
+ * dx [nb, nf, nt, dx_stride] contiguous, channels 0 .. cin_g - 1 written (overwritten).  fp32 MFMA. */
+int fnssl_conv3x3_causal_backward_data(const float* dz, long long z_sb, long long z_sf, long long z_st, int cout,
+                                       const float* wpack, int cin_g, int nb, int nf, int nt, float* dx, int dx_stride,
+                                       void* stream);
+
+/* Weight gradient of fnssl_conv3x3_causal: dw[co, c, df, dt] += sum_{b, f, t} dz[b, f, t, co] * x[b, f+df-1, t+dt-2, c]
+ * with x = [xa | xb] (strided channels-last, as in the forward) and dw the PyTorch layout [cout, ca + cb, 3, 3].
+ * Split-K fp32 MFMA; the slabs are added in a fixed order (deterministic).  cout, ca, cb multiples of 4. */
+size_t fnssl_conv3x3_weight_grads_workspace_bytes(int nb, int nf, int nt, int cout, int ca, int cb);
+int fnssl_conv3x3_weight_grads(const float* dz, long long z_sb, long long z_sf, long long z_st, int cout,
+                               const float* xa, long long a_sb, long long a_sf, long long a_st, int ca,
+                               const float* xb, long long b_sb, long long b_sf, long long b_st, int cb,
+                               int nb, int nf, int nt, float* dw, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Whole network (replaces FN_SSL.forward, FN-SSL/Model.py:72-90)             */
 /* ------------------------------------------------------------------------- */
 
