@@ -41,7 +41,8 @@ extern template int launch_split_h<256>(int, const LstmParams&, int, int, hipStr
 int forward_save(LstmParams p, int H, int mode, hipStream_t st);   // lstm_train.hip
 int forward_bf16(LstmParams p, int H, hipStream_t st);             // lstm_bf16.hip
 bool f32c_handles(const LstmParams& p, int H, int mode);           // lstm_f32c.hip
-int forward_f32c(LstmParams p, int H, int mode, hipStream_t st);          // FNSSL_OK, kNoCluster (not co-resident: caller takes the rounds) or an error
+// FNSSL_OK, kNoCluster (not co-resident: caller takes the rounds) or an error; cluster_bytes = the size of p.cluster_ws
+int forward_f32c(LstmParams p, int H, int mode, size_t cluster_bytes, hipStream_t st);
 }  // namespace fnssl_lstm
 
 // ---- launch planner (host) -------------------------------------------------------------------------------------
@@ -147,22 +148,22 @@ int fnssl_lstm_pack(const float* w_ih, const float* w_hh, const float* b_ih, con
   return FNSSL_OK;
 }
 
-// bytes of cell-state scratch at the front of the workspace (a multiple of 256)
+// ---- the forward workspace -------------------------------------------------------------------------------------------
+// cell state at the front (a multiple of 256 bytes): one float4 per (lane, slice) per wave; the tail workgroup is padded to a
+// whole workgroup (<= 16 waves), which the kSpareTasks spare slots per direction cover for every variant (cell_record)
 static size_t cell_scratch_bytes(int nseq, int hidden, int ndir) {
-  // one float4 per (lane, slice) per wave; the tail workgroup is padded to a whole workgroup (<= 16 waves), so every
-  // variant fits
-  const size_t tasks = (size_t)(nseq + 15) / 16 + 16;
+  const size_t tasks = (size_t)(nseq + 15) / 16 + kSpareTasks;
   return tasks * ndir * (size_t)(hidden / 16) * 64 * 16 + 256;
 }
-// the pair-interleaved copy of a weight stream (lstm_static3.h) lives behind the cell state: room for the largest
-// stream of the hidden size (c0 + c2 <= 272 channels) per direction
+// the pair- / quad-interleaved copy of a weight stream (lstm_static3.h, lstm_static4.h): room for the largest stream of the
+// hidden size (c0 + c2 <= 272 channels) per direction
 static size_t pair_stream_bytes(int hidden, int ndir) {
   return hidden == 256 ? (size_t)ndir * (hidden / 16) * quads_per_slice(256, 16, hidden) * 4096 : 0;
 }
 
-// the hand-off area of the cluster-resident bf16 kernel (lstm_bf16c.h) lives behind that: status word, tags, operand records
-// (bf16 "wide" calls: tags + two parities of operand records, ~513 B per sequence; fp32 calls: the cluster kernel of
-//  lstm_f32c.h hands h_t over through the output tensor and needs the status word + one tag word per member (H / 16) per
+// the hand-off area of the cluster-resident kernels: status word, tags, operand records
+// (bf16 "wide" calls, lstm_bf16c.h: tags + two parities of operand records, ~513 B per sequence; fp32 calls: the cluster kernel
+//  of lstm_f32c.h hands h_t over through the output tensor and needs the status word + one tag word per member (H / 16) per
 //  16-sequence group and direction, rounded up per cluster: 2 - 4 B per sequence)
 static size_t cluster_bytes(int nseq, int hidden, int ndir, int precision) {
   if (hidden != 256 && hidden != 128) return 0;
@@ -177,11 +178,27 @@ static size_t cluster_bytes(int nseq, int hidden, int ndir, int precision) {
   return 256 + (groups + 512) * ndir * (hidden / 16) * sizeof(unsigned);   // one tag word per (group, member); +512: the last cluster's groups are rounded up
 }
 
-// ... and behind that, for the one shape whose STREAMING calls (carry_state) the cluster-resident fp32 kernel takes (H = 256,
-// one direction): a snapshot of the carried cell state.  lstm_f32c_kernel updates c in place every step, so a launch that gives
-// up has already overwritten c_{-1}; the guarded fallback of the same call restarts from the snapshot (restore_cell_kernel).
-static size_t carry_backup_bytes(int nseq, int hidden, int ndir, int precision) {
-  return (precision == FNSSL_PRECISION_FP32 && hidden == 256 && ndir == 1) ? cell_scratch_bytes(nseq, hidden, ndir) : 0;
+// The regions of the workspace, front to back; a region the call does not use has 0 bytes.  The one description behind the
+// size (fnssl_lstm_workspace_bytes_ex), the carve-up (lstm_forward_impl) and the status read (fnssl_lstm_cluster_status).
+struct LstmWsLayout {
+  WsRegion cell;      // cell state (cell_record): what a streaming caller carries from one call to the next
+  WsRegion stream;    // H = 256: the interleaved copy of the weight stream
+  WsRegion cluster;   // hand-off area of the cluster-resident kernels; its first word is the status word
+  // fp32, H = 256, one direction — the one shape whose STREAMING calls (carry_state) the cluster-resident fp32 kernel takes: a
+  // snapshot of the carried cell state.  lstm_f32c_kernel updates c in place every step, so a launch that gives up has already
+  // overwritten c_{-1}; the guarded fallback of the same call restarts from the snapshot (restore_cell_kernel).
+  WsRegion carry;
+  size_t total;
+};
+
+static LstmWsLayout lstm_ws_layout(int nseq, int hidden, int ndir, int precision) {
+  LstmWsLayout L;
+  L.cell = {0, cell_scratch_bytes(nseq, hidden, ndir)};
+  L.stream = {L.cell.end(), pair_stream_bytes(hidden, ndir)};
+  L.cluster = {L.stream.end(), cluster_bytes(nseq, hidden, ndir, precision)};
+  L.carry = {L.cluster.end(), (precision == FNSSL_PRECISION_FP32 && hidden == 256 && ndir == 1) ? L.cell.bytes : 0};
+  L.total = L.carry.end();
+  return L;
 }
 
 int fnssl_lstm_plan_rounds(int hidden, int nseq, int ndir, int ncu, int* waves_per_wg, int cap) {
@@ -196,12 +213,13 @@ int fnssl_lstm_plan_rounds(int hidden, int nseq, int ndir, int ncu, int* waves_p
 
 size_t fnssl_lstm_workspace_bytes_ex(int nseq, int hidden, int ndir, int precision) {
   if (nseq <= 0 || hidden <= 0 || ndir <= 0) return 0;
-  return cell_scratch_bytes(nseq, hidden, ndir) + pair_stream_bytes(hidden, ndir) + cluster_bytes(nseq, hidden, ndir, precision) +
-         carry_backup_bytes(nseq, hidden, ndir, precision);
+  return lstm_ws_layout(nseq, hidden, ndir, precision).total;
 }
 
 size_t fnssl_lstm_workspace_bytes(int nseq, int hidden, int ndir) {   // sufficient for every precision
-  return fnssl_lstm_workspace_bytes_ex(nseq, hidden, ndir, FNSSL_PRECISION_BF16W);
+  return std::max({fnssl_lstm_workspace_bytes_ex(nseq, hidden, ndir, FNSSL_PRECISION_FP32),
+                   fnssl_lstm_workspace_bytes_ex(nseq, hidden, ndir, FNSSL_PRECISION_BF16),
+                   fnssl_lstm_workspace_bytes_ex(nseq, hidden, ndir, FNSSL_PRECISION_BF16W)});
 }
 
 namespace {
@@ -248,9 +266,11 @@ __global__ void __launch_bounds__(256) restore_cell_kernel(const unsigned* __res
 int fnssl_lstm_cluster_status(const void* workspace, size_t workspace_bytes, int nseq, int hidden, int ndir, void* stream,
                               unsigned* status) {
   FNSSL_REQUIRE(workspace && status && nseq > 0 && ndir > 0, "lstm_cluster_status: null pointer / empty problem");
-  FNSSL_REQUIRE(workspace_bytes >= fnssl_lstm_workspace_bytes_ex(nseq, hidden, ndir, FNSSL_PRECISION_FP32) && (hidden == 128 || hidden == 256),
+  // the status word opens the cluster area, whose offset does not depend on the precision
+  const size_t off = lstm_ws_layout(nseq, hidden, ndir, FNSSL_PRECISION_FP32).cluster.off;
+  FNSSL_REQUIRE(workspace_bytes >= off + sizeof(unsigned) && (hidden == 128 || hidden == 256),
                 "lstm_cluster_status: not a workspace of a cluster-kernel shape (hidden %d)", hidden);
-  const char* word = reinterpret_cast<const char*>(workspace) + cell_scratch_bytes(nseq, hidden, ndir) + pair_stream_bytes(hidden, ndir);
+  const char* word = reinterpret_cast<const char*>(workspace) + off;
   hipStream_t st = fnssl::as_stream(stream);
   FNSSL_HIP(hipMemcpyAsync(status, word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
   FNSSL_HIP(hipStreamSynchronize(st));
@@ -307,9 +327,9 @@ static int lstm_forward_impl(const fnssl_lstm_desc* d, void* stream, bool dry, i
                                      mult4(d->skip.si) && mult4(d->skip.st))) &&
                     extent_ok(d->out_so, d->out_si, d->out_st, 2 * H),
                 "lstm_forward: strides must be non-negative and one sequence group must span < 4 GB");
-  const size_t need = fnssl_lstm_workspace_bytes_ex(d->nseq, H, d->ndir, d->precision);
-  if (!d->workspace || d->workspace_bytes < need) {
-    fnssl::set_error("lstm_forward: workspace %zu < %zu bytes", d->workspace_bytes, need);
+  const LstmWsLayout ws = lstm_ws_layout(d->nseq, H, d->ndir, d->precision);
+  if (!d->workspace || d->workspace_bytes < ws.total) {
+    fnssl::set_error("lstm_forward: workspace %zu < %zu bytes", d->workspace_bytes, ws.total);
     return FNSSL_E_WORKSPACE;
   }
   LstmParams p;
@@ -329,7 +349,7 @@ static int lstm_forward_impl(const fnssl_lstm_desc* d, void* stream, bool dry, i
   p.wpack[0] = d->wpack[0];
   p.wpack[1] = d->wpack[1];
   p.cscratch = d->workspace;
-  p.cluster_ws = reinterpret_cast<char*>(d->workspace) + cell_scratch_bytes(d->nseq, H, d->ndir) + pair_stream_bytes(H, d->ndir);
+  p.cluster_ws = reinterpret_cast<char*>(d->workspace) + ws.cluster.off;
   p.reserve = d->reserve;
   p.ntasks = (d->nseq + 15) / 16;
   p.c0 = d->c0;
@@ -380,7 +400,7 @@ static int lstm_forward_impl(const fnssl_lstm_desc* d, void* stream, bool dry, i
                       ((fm & 2) || !d->c2 || (mult8(d->src2.so) && mult8(d->src2.si) && mult8(d->src2.st))) &&
                       ((fm & 4) || (mult8(d->out_so) && mult8(d->out_si) && mult8(d->out_st))),
                   "lstm_forward: strides of bf16 tensors must be multiples of 8 elements");
-    return forward_bf16w(p, H, fm, st, family);
+    return forward_bf16w(p, H, fm, ws.cluster.bytes, st, family);
   }
   FNSSL_REQUIRE(d->precision == FNSSL_PRECISION_FP32, "lstm_forward: unknown precision %d", d->precision);
   if (d->reserve) {   // training forward: also save the gate activations (lstm_train.hip)
@@ -398,7 +418,7 @@ static int lstm_forward_impl(const fnssl_lstm_desc* d, void* stream, bool dry, i
     // the full-band layers of a large enough shard: the cluster-resident kernel with the reserve stores (lstm_f32c.h), its
     // guarded fallback = the split kernels below
     if (d->variant == 0 && f32c_handles(p, H, mode)) {
-      const int rc = forward_f32c(p, H, mode, st);
+      const int rc = forward_f32c(p, H, mode, ws.cluster.bytes, st);
       if (rc == FNSSL_OK) {
         report(FNSSL_LSTM_FAMILY_F32_CLUSTER);
         if (dry) return FNSSL_OK;
@@ -417,13 +437,12 @@ static int lstm_forward_impl(const fnssl_lstm_desc* d, void* stream, bool dry, i
   // kernel recorded a hand-off it gave up on: include/fnssl.h, fnssl_lstm_forward)
   if (d->variant == 0 && !(mode & kHas1) && f32c_handles(p, H, mode)) {
     // streaming call: the cluster kernel advances the carried cell state in place — snapshot c_{-1} first, so that the guarded
-    // fallback below can restart from it if the launch gives up (carry_backup_bytes)
-    const size_t cell_bytes = cell_scratch_bytes(d->nseq, H, d->ndir);
-    char* backup = p.cluster_ws + cluster_bytes(d->nseq, H, d->ndir, d->precision);
-    const bool snap = p.carry && !dry && carry_backup_bytes(d->nseq, H, d->ndir, d->precision) >= cell_bytes;
-    FNSSL_REQUIRE(!p.carry || dry || snap, "lstm_forward: no room for the carried cell state's snapshot (hidden %d)", H);
+    // fallback below can restart from it if the launch gives up (LstmWsLayout::carry: room for it in every shape that streams here)
+    const size_t cell_bytes = ws.cell.bytes;
+    char* backup = reinterpret_cast<char*>(d->workspace) + ws.carry.off;
+    const bool snap = p.carry && !dry;
     if (snap) FNSSL_HIP(hipMemcpyAsync(backup, p.cscratch, cell_bytes, hipMemcpyDeviceToDevice, st));
-    const int rc = forward_f32c(p, H, mode, st);
+    const int rc = forward_f32c(p, H, mode, ws.cluster.bytes, st);
     if (rc == FNSSL_OK) {
       report(FNSSL_LSTM_FAMILY_F32_CLUSTER);
       if (rounds) *rounds = 1;
@@ -462,7 +481,8 @@ static int lstm_forward_impl(const fnssl_lstm_desc* d, void* stream, bool dry, i
         if (vr.NW == 12 && d->c0 == 256 && !p.carry && s3) {
           LstmParams p2 = p;
           const long long n4 = (long long)(H / 16) * p.quads_per_slice * 4 * 64;      // float4 per direction
-          char* dst = reinterpret_cast<char*>(d->workspace) + cell_scratch_bytes(d->nseq, H, d->ndir);
+          char* dst = reinterpret_cast<char*>(d->workspace) + ws.stream.off;
+          FNSSL_REQUIRE((size_t)d->ndir * n4 * 16 <= ws.stream.bytes, "lstm_forward: no room for the interleaved weight stream");
           // round 6: four slices per pass on a QUAD-interleaved copy (lstm_static4.h: half the operand re-reads, the weight ring
           // staged by LDS-DMA); NO_STATIC4 keeps the two-slice kernel: A/B, same bits
           const bool s4 = !fnssl::tune(FNSSL_TUNE_NO_STATIC4);

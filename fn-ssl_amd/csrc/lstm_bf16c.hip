@@ -51,7 +51,7 @@ static int launch_one(const LstmParams& p, const ClusterParams& cp, hipStream_t 
 }
 
 // Launches of at most CUs / members clusters (one workgroup per CU: every member of every cluster of a launch is resident).
-int forward_bf16c(LstmParams p, int H, int flags, hipStream_t st) {
+int forward_bf16c(LstmParams p, int H, int flags, size_t cluster_bytes, hipStream_t st) {
   if (flags == kW_F0) {   // block 1's full-band layer: the kernel's one fp32 block is src2; same record layout in the stream
     p.src2 = p.src0;
     p.c2 = p.c0;
@@ -88,6 +88,7 @@ int forward_bf16c(LstmParams p, int H, int flags, hipStream_t st) {
   cp.hx = p.cluster_ws + head;
   FNSSL_REQUIRE((size_t)ncl * 2 * cluster_parity_bytes(H) < 0xf0000000ull, "lstm_forward: too many sequences for one call of the cluster kernel");
   cp.parity_stride = (unsigned)((size_t)ncl * cluster_parity_bytes(H));
+  FNSSL_REQUIRE(head + 2 * (size_t)cp.parity_stride <= cluster_bytes, "lstm_forward: %d clusters exceed the workspace's cluster area", ncl);
   cp.cl_per_dir = cl_per_dir;
   cp.tpc = (tiles + cl_per_dir - 1) / cl_per_dir;
   // placement is a speed matter only; the knob puts the members of a cluster on DIFFERENT XCDs so that tests can show it

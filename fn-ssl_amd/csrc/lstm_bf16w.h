@@ -375,6 +375,7 @@ int launch_bf16w_k(const LstmParams& p, int nwg, hipStream_t st) {
 
 // kNoStatic when the shape / element types have no instantiation
 int launch_bf16w(const LstmParams& p, int H, int NW, int flags, int nwg, hipStream_t st);
-int forward_bf16w(LstmParams p, int H, int flags, hipStream_t st, int* family = nullptr);
+// cluster_bytes = the size of p.cluster_ws (the hand-off area of the cluster-resident kernel, lstm_bf16c.h)
+int forward_bf16w(LstmParams p, int H, int flags, size_t cluster_bytes, hipStream_t st, int* family = nullptr);
 
 }  // namespace fnssl_lstm

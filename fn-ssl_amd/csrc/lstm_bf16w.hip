@@ -9,7 +9,7 @@
 namespace fnssl_lstm {
 
 bool bf16c_handles(const LstmParams& p, int H, int flags);           // lstm_bf16c.hip
-int forward_bf16c(LstmParams p, int H, int flags, hipStream_t st);
+int forward_bf16c(LstmParams p, int H, int flags, size_t cluster_bytes, hipStream_t st);
 
 // NW = 2: two consumer waves + two loader waves on the SIMDs the launch leaves idle; NW = 4: four consumers that
 // fetch their own stream (H = 128 only: at H = 256 the ring plus four h staging areas exceed the LDS)
@@ -58,7 +58,7 @@ int launch_bf16p(const LstmParams& p, int H, int flags, int nwg, hipStream_t st)
 
 // One launch: every 32-sequence group of every direction.  Default: the pair-split kernels; FNSSL_BF16W_SOLO=1 keeps
 // the one-wave-per-group kernels of lstm_bf16w.h (A/B).
-int forward_bf16w(LstmParams p, int H, int flags, hipStream_t st, int* family) {
+int forward_bf16w(LstmParams p, int H, int flags, size_t cluster_bytes, hipStream_t st, int* family) {
   const int ncu = fnssl::device_cus();
   const int groups = (p.nseq + 31) / 32;
   const long long total = (long long)groups * p.ndir;
@@ -68,7 +68,7 @@ int forward_bf16w(LstmParams p, int H, int flags, hipStream_t st, int* family) {
   // — followed by the pair-split launch below as its GUARDED fallback (include/fnssl.h, fnssl_lstm_forward)
   bool guarded = false;
   if (bf16c_handles(p, H, flags)) {
-    const int rc = forward_bf16c(p, H, flags, st);
+    const int rc = forward_bf16c(p, H, flags, cluster_bytes, st);
     if (rc == FNSSL_OK) {
       if (family) *family = FNSSL_LSTM_FAMILY_BF16_CLUSTER;
       if (p.dry) return FNSSL_OK;

@@ -66,8 +66,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     rdx[k] = p.c0g ? split_addr(p.dx, qo * p.dx_so + qi * p.dx_si, dir * p.c0g + 4 * g4, vdx[k]) : rdh[k];
     rres[k] = make_rsrc(reinterpret_cast<const char*>(p.reserve) +
                         ((size_t)dir * p.ntasks + (tvalid[k] ? task : 0)) * p.nsteps * (size_t)(NS * kReserveRecs * 1024));
-    rsc[k] = make_rsrc(reinterpret_cast<const char*>(p.scratch) +
-                       ((size_t)dir * (p.ntasks + 16) + (tvalid[k] ? task : p.ntasks + k)) * (2 * NS * 1024));
+    rsc[k] = make_rsrc(dhdc_record<NS>(p.scratch, p.ntasks, dir, tvalid[k] ? task : p.ntasks + k));
   }
 
   // ---- weight pipeline: this wave's data quads (the zero "bias" quad of each output slice is skipped) form a cyclic sequence

@@ -240,8 +240,7 @@ __global__ void __launch_bounds__(NW_ * 64) lstm_bwdc_kernel(const BwdParams p, 
     locate(task, gr, rdh, rda, rdx);
     const unsigned tt = rev ? step : p.nsteps - 1 - step;      // the forward direction's gradient flows T-1 .. 0
     const unsigned oa = tt * sda;
-    const rsrc_t rsc = make_rsrc(reinterpret_cast<const char*>(p.scratch) +
-                                 ((size_t)dir * (p.ntasks + 16) + task) * (2 * NS * 1024));
+    const rsrc_t rsc = make_rsrc(dhdc_record<NS>(p.scratch, p.ntasks, dir, task));
     unsigned* const tag_g = tag_cl + (size_t)(task - g0) * 16;
     pub_flush();
     // a leftover group's previous step ran on ANOTHER wave of this member: its carried state is final once that wave's

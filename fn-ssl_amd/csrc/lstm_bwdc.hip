@@ -6,12 +6,6 @@
 
 namespace fnssl_lstm {
 
-// bytes behind the carried-state records of fnssl_lstm_backward's workspace: status word (256 B) + tag arrays
-size_t bwdc_bytes(int nseq, int ndir) {
-  const size_t tasks = (size_t)(nseq + 15) / 16;
-  return 256 + (tasks + 256) * (size_t)ndir * 16 * sizeof(unsigned);
-}
-
 // does the cluster kernel take this layer?  H = 128 and the output slices make whole clusters inside an XCD (config 4, block
 // 1: 2 members, 9.4 groups per cluster — 10.7 against 13.4 ms on the split kernels).  Round 4 kept shards of fewer than 8
 // groups per cluster on the split kernels; measured in round 5 (4 / 2 utterances per GPU: 4 / 2 groups per cluster) those
@@ -38,8 +32,9 @@ bool bwdc_handles(const BwdParams& p, int H, BwdClusterParams& cp) {
   return cp.groups_per_cluster >= (min_groups ? min_groups : 1);
 }
 
-// ws = the region bwdc_bytes() sizes.  FNSSL_OK, kNoCluster, or an error.
-int backward_cluster(const BwdParams& p, BwdClusterParams cp, void* ws, hipStream_t st) {
+// ws = the cluster area of fnssl_lstm_backward's workspace (BwdWsLayout, lstm_train.hip), ws_bytes its size.  FNSSL_OK,
+// kNoCluster, or an error.
+int backward_cluster(const BwdParams& p, BwdClusterParams cp, void* ws, size_t ws_bytes, hipStream_t st) {
   cp.status = static_cast<unsigned*>(ws);
   cp.tags = cp.status + 64;
   cp.spin_limit = cluster_spin_limit();
@@ -48,6 +43,7 @@ int backward_cluster(const BwdParams& p, BwdClusterParams cp, void* ws, hipStrea
   cp.no_prefetch = fnssl::tune(FNSSL_TUNE_BWDC_NO_PREFETCH);
   cp.simd_token = !fnssl::tune(FNSSL_TUNE_BWDC_NO_TOKEN);
   const size_t tag_bytes = (size_t)cp.clusters_per_dir * p.ndir * cp.groups_per_cluster * 16 * sizeof(unsigned);
+  FNSSL_REQUIRE(256 + tag_bytes <= ws_bytes, "lstm_backward: the cluster kernel's tags exceed the workspace's cluster area");
   if (!p.dry) FNSSL_HIP(hipMemsetAsync(ws, 0, 256 + tag_bytes, st));   // (dry: the launchers stop after their occupancy check)
 #ifdef FNSSL_BUILD_ABLATE
   if ((cp.ablate = env_int("FNSSL_BWDC_ABLATE", 1, 1 << 20)) != 0) return launch_bwdc_k<kBwdcWaves, true>(p, cp, st);

@@ -175,7 +175,7 @@ __global__ void __launch_bounds__(NW_ * 64) lstm_f32c_kernel(const LstmParams p,
   };
   auto tt_of = [&](int step) { return (unsigned)(rev ? p.nsteps - 1 - step : step); };
   auto rc_of = [&](int task) {
-    return make_rsrc(reinterpret_cast<const char*>(p.cscratch) + ((size_t)dir * (p.ntasks + 16) + task) * (NS * 1024));
+    return make_rsrc(cell_record<NS>(p.cscratch, p.ntasks, dir, task));
   };
 
   if (g0 + ws >= g1) return;                                  // (a wave / slot without a group: nobody waits for it)

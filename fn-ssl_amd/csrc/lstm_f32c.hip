@@ -80,7 +80,7 @@ bool f32c_handles(const LstmParams& p, int H, int mode) {
   return !fnssl::tune(FNSSL_TUNE_NO_F32_SMALL) || groups >= 12LL * ncu;
 }
 
-int forward_f32c(LstmParams p, int H, int mode, hipStream_t st) {
+int forward_f32c(LstmParams p, int H, int mode, size_t cluster_bytes, hipStream_t st) {
   if (f32c_uniform(p, mode)) p.q_inner = p.nseq;   // one outer index: no group ever crosses (any q_inner, e.g. 12 frames)
   const int ncu = cluster_cus();
   const int members = H / 16;
@@ -94,6 +94,7 @@ int forward_f32c(LstmParams p, int H, int mode, hipStream_t st) {
   cp.rotate = !fnssl::tune(FNSSL_TUNE_F32C_NO_ROTATE);   // A/B knob, same bits (wave counts are powers of two)
   cp.prio_mode = fnssl::tune(FNSSL_TUNE_F32C_PRIO, 9, 9) ? 0 : 2;   // see F32ClusterParams
   const size_t tag_bytes = (size_t)p.ndir * cp.clusters_per_dir * cp.groups_per_cluster * members * sizeof(unsigned);
+  FNSSL_REQUIRE(256 + tag_bytes <= cluster_bytes, "lstm_forward: the cluster kernel's tags exceed the workspace's cluster area");
   if (!p.dry) FNSSL_HIP(hipMemsetAsync(p.cluster_ws, 0, 256 + tag_bytes, st));
   // Gate split (lstm_f32c.h): only with ONE group per cluster (one 2-mic utterance, the full-band layers of a streaming
   // chunk) — there a step is the group's own matrix work plus its hand-off, and four SIMDs share the former.  With more

@@ -58,8 +58,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
     ro[k] = split_addr(p.out, qo * p.out_so + qi * p.out_si, dir * H + 4 * g4, voo[k]);
     rres[k] = make_rsrc(reinterpret_cast<const char*>(p.reserve) +
                         ((size_t)dir * p.ntasks + (tvalid[k] ? task : 0)) * p.nsteps * (size_t)(NS * kReserveRecs * 1024));
-    rc[k] = make_rsrc(reinterpret_cast<const char*>(p.cscratch) +
-                      ((size_t)dir * (p.ntasks + 16) + (tvalid[k] ? task : p.ntasks + k)) * (NS * 1024));
+    rc[k] = make_rsrc(cell_record<NS>(p.cscratch, p.ntasks, dir, tvalid[k] ? task : p.ntasks + k));
   }
 
   // ---- weight pipeline: the wave's NSL slices are one contiguous run of NQ quads; ar[q % WD] holds quad q of the step

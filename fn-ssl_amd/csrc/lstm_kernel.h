@@ -32,7 +32,7 @@ struct LstmParams {
   long long out_so, out_si, out_st;
   const float* wpack[2];
   float* cscratch;
-  char* cluster_ws;   // hand-off area of the cluster-resident bf16 kernel (lstm_bf16c.h): status, tags, operand records
+  char* cluster_ws;   // hand-off area of the cluster-resident kernels (lstm_f32c.h, lstm_bf16c.h): status word, tags (, operand records)
   float* reserve;     // training forward (MODE bit kSave): gates + cell state per (dir, group, step, slice)
   int ntasks;         // 16-sequence groups per direction (reserve / cell-state indexing)
   int carry;          // streaming: 1 = h_{-1} is the row before `out` (host passes out - out_st), c_{-1} is in cscratch
@@ -73,6 +73,25 @@ constexpr int kHas1 = 1;   // input segment 0 is src0 + src1
 constexpr int kHas2 = 2;   // concatenated segment src2 present
 constexpr int kSum = 4;    // epilogue also writes out_sum = h + skip
 constexpr int kSave = 8;   // training forward: the epilogue also stores i, f, g, o and c for the backward pass
+
+// Carried-state records in the workspace: one per (direction, slot), `ntasks` slots for the 16-sequence groups and then
+// kSpareTasks private dummy slots for the idle tail waves of a launch (<= 16 waves per workgroup).  The forward's cell state is
+// NS lane-private 1 KiB records per slot, the backward's carried dh / dc 2 x NS; the host sizers (lstm.hip, lstm_train.hip)
+// count the same slots.
+constexpr int kSpareTasks = 16;
+template <int NS>
+__device__ __forceinline__ const char* cell_record(const float* cscratch, int ntasks, int dir, int slot) {
+  return reinterpret_cast<const char*>(cscratch) + ((size_t)dir * (ntasks + kSpareTasks) + slot) * (NS * 1024);
+}
+template <int NS>
+__device__ __forceinline__ const char* dhdc_record(const float* scratch, int ntasks, int dir, int slot) {
+  return reinterpret_cast<const char*>(scratch) + ((size_t)dir * (ntasks + kSpareTasks) + slot) * (2 * NS * 1024);
+}
+// host: one region of a workspace layout (lstm.hip, lstm_train.hip), in bytes from the workspace's start
+struct WsRegion {
+  size_t off, bytes;
+  size_t end() const { return off + bytes; }
+};
 
 // Reserve layout (written by the kSave forward, read by lstm_bwd_kernel): lane-private 1 KiB records
 //   reserve[(((dir * ntasks + group) * nsteps + t) * NS + slice) * 5 + {i, f, g, o, c}][lane] (float4)
@@ -378,9 +397,10 @@ __global__ void __launch_bounds__(NW * 64, (NW == 4 ? 3 : 1)) lstm_rec_kernel(co
   unsigned voo2 = 0;
   const rsrc_t ro2 = SUM ? split_addr(p.out_sum, qo * p.out_so + qi * p.out_si, dir * H + 4 * g, voo2) : ro;
   // cell state: one record per (direction, 16-sequence group, slice) — independent of the launch geometry,
-  // so a streaming caller finds it again in the next call; idle tail waves get private dummy slots
+  // so a streaming caller finds it again in the next call; idle tail waves get private dummy slots (cell_record's addressing,
+  // spelled out: through the helper the compiler schedules this kernel's prologue differently)
   const rsrc_t rc = make_rsrc(reinterpret_cast<const char*>(p.cscratch) +
-                              ((size_t)dir * (p.ntasks + 16) + (task < p.task1 ? task : p.ntasks + w)) * (NS * 1024));
+                              ((size_t)dir * (p.ntasks + kSpareTasks) + (task < p.task1 ? task : p.ntasks + w)) * (NS * 1024));
   const unsigned cy = (unsigned)p.carry;
   const bool tsave = SAVE && task < p.task1;
   const rsrc_t rres = SAVE ? make_rsrc(reinterpret_cast<const char*>(p.reserve) +

@@ -58,8 +58,9 @@ __global__ void __launch_bounds__(NW * 64, (NW == 4 && !DIRECT ? 3 : 1)) lstm_sp
   const rsrc_t rsk = SUM ? split_addr(p.skip.p, qo * p.skip.so + qi * p.skip.si, dir * H + 4 * g, vok) : rx0;
   const rsrc_t ro2 = SUM ? split_addr(p.out_sum, qo * p.out_so + qi * p.out_si, dir * H + 4 * g, voo2) : ro;
   const unsigned stk = SUM ? (unsigned)(p.skip.st * 4) : 0u;
+  // (cell_record's addressing, spelled out: through the helper the compiler schedules this prologue differently)
   const rsrc_t rc = make_rsrc(reinterpret_cast<const char*>(p.cscratch) +
-                              ((size_t)dir * (p.ntasks + 16) + (tvalid ? task : p.ntasks + w)) * (NS * 1024));
+                              ((size_t)dir * (p.ntasks + kSpareTasks) + (tvalid ? task : p.ntasks + w)) * (NS * 1024));
   const rsrc_t rres = SAVE ? make_rsrc(reinterpret_cast<const char*>(p.reserve) +
                                        ((size_t)dir * p.ntasks + (tvalid ? task : 0)) * p.nsteps *
                                            (size_t)(NS * kReserveRecs * 1024))

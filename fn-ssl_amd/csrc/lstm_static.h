@@ -66,8 +66,7 @@ __global__ void __launch_bounds__(NW * 64) lstm_static_kernel(const LstmParams p
   const rsrc_t rsk = SUM ? split_addr(p.skip.p, qo * p.skip.so + qi * p.skip.si, dir * H + 4 * g, vok) : rx0;
   const rsrc_t ro = split_addr(p.out, qo * p.out_so + qi * p.out_si, dir * H + 4 * g, voo);
   const rsrc_t ro2 = SUM ? split_addr(p.out_sum, qo * p.out_so + qi * p.out_si, dir * H + 4 * g, voo2) : ro;
-  const rsrc_t rc = make_rsrc(reinterpret_cast<const char*>(p.cscratch) +
-                              ((size_t)dir * (p.ntasks + 16) + (task < p.task1 ? task : p.ntasks + w)) * (NS * 1024));
+  const rsrc_t rc = make_rsrc(cell_record<NS>(p.cscratch, p.ntasks, dir, task < p.task1 ? task : p.ntasks + w));
   const unsigned cy = (unsigned)p.carry;   // streaming (see lstm_rec_kernel)
   const rsrc_t rw = make_rsrc(p.wpack[dir]);
   const unsigned st0 = (unsigned)(p.src0.st * 4), st2 = HAS2 ? (unsigned)(p.src2.st * 4) : 0u;

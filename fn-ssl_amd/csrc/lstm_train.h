@@ -81,8 +81,7 @@ __global__ void __launch_bounds__(NW * 64) lstm_bwd_kernel(const BwdParams p) {
                                 ((size_t)dir * p.ntasks + (tvalid ? task : 0)) * p.nsteps *
                                     (size_t)(NS * kReserveRecs * 1024));
   // carried dh / dc: one region per (direction, group), shared by the waves of a split group
-  const rsrc_t rsc = make_rsrc(reinterpret_cast<const char*>(p.scratch) +
-                               ((size_t)dir * (p.ntasks + 16) + (tvalid ? task : p.ntasks + w)) * (2 * NS * 1024));
+  const rsrc_t rsc = make_rsrc(dhdc_record<NS>(p.scratch, p.ntasks, dir, tvalid ? task : p.ntasks + w));
   const unsigned sdh = (unsigned)(p.dh.st * 4), sda = (unsigned)(p.da_st * 4), sdx = (unsigned)(p.dx_st * 4);
   const unsigned vlane = lane * 16;
   const bool rev = dir == 1;

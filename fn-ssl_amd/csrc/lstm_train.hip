@@ -17,9 +17,8 @@ namespace fnssl_lstm {
 
 using fnssl::device_cus;
 
-size_t bwdc_bytes(int nseq, int ndir);                                                    // lstm_bwdc.hip
-bool bwdc_handles(const BwdParams& p, int H, BwdClusterParams& cp);
-int backward_cluster(const BwdParams& p, BwdClusterParams cp, void* ws, hipStream_t st);
+bool bwdc_handles(const BwdParams& p, int H, BwdClusterParams& cp);                        // lstm_bwdc.hip
+int backward_cluster(const BwdParams& p, BwdClusterParams cp, void* ws, size_t ws_bytes, hipStream_t st);
 
 struct Geometry {
   int nw, split, t0, t1;
@@ -105,10 +104,22 @@ int forward_save(LstmParams p, int H, int mode, hipStream_t st) {
 
 }  // namespace fnssl_lstm
 
-// carried dh / dc records (one region per direction and group, 16 spare), 256-byte aligned end
-static size_t bwd_scratch_bytes(int nseq, int hidden, int ndir) {
-  const size_t tasks = (size_t)(nseq + 15) / 16 + 16;
-  return tasks * ndir * (size_t)(2 * (hidden / 16)) * 1024 + 256;
+// The backward workspace, front to back: one description behind its size (fnssl_lstm_bwd_workspace_bytes), its carve-up
+// (lstm_backward_impl) and the status read (fnssl_lstm_backward_status).
+struct BwdWsLayout {
+  WsRegion carried;   // carried dh / dc records (dhdc_record: one per direction and group, kSpareTasks spare), 256-byte aligned end
+  WsRegion cluster;   // the cluster kernel's area (lstm_bwdc.hip): status word (256 B) + tags, 16 words per group
+  size_t total;
+};
+
+static BwdWsLayout bwd_ws_layout(int nseq, int hidden, int ndir) {
+  const size_t groups = (size_t)(nseq + 15) / 16;
+  BwdWsLayout L;
+  L.carried = {0, (groups + kSpareTasks) * ndir * (size_t)(2 * (hidden / 16)) * 1024 + 256};
+  // +256: the last cluster's groups are rounded up (<= 256 clusters per direction)
+  L.cluster = {L.carried.end(), 256 + (groups + 256) * (size_t)ndir * 16 * sizeof(unsigned)};
+  L.total = L.cluster.end();
+  return L;
 }
 static int lstm_backward_impl(const fnssl_lstm_bwd_desc* d, void* stream, int dry, int* family);
 
@@ -154,7 +165,7 @@ int fnssl_lstm_pack_bwd(const float* w_ih, const float* w_hh, int c_in, int c0g,
 
 size_t fnssl_lstm_bwd_workspace_bytes(int nseq, int hidden, int ndir) {
   if (nseq <= 0 || hidden <= 0 || ndir <= 0) return 0;
-  return bwd_scratch_bytes(nseq, hidden, ndir) + bwdc_bytes(nseq, ndir);
+  return bwd_ws_layout(nseq, hidden, ndir).total;
 }
 
 int fnssl_lstm_backward(const fnssl_lstm_bwd_desc* d, void* stream) { return lstm_backward_impl(d, stream, 0, nullptr); }
@@ -164,11 +175,11 @@ int fnssl_lstm_backward_plan(const fnssl_lstm_bwd_desc* d, int* family) { return
 int fnssl_lstm_backward_status(const void* workspace, size_t workspace_bytes, int nseq, int hidden, int ndir, void* stream,
                                unsigned* status) {
   FNSSL_REQUIRE(workspace && status, "lstm_backward_status: null pointer");
-  FNSSL_REQUIRE(workspace_bytes >= fnssl_lstm_bwd_workspace_bytes(nseq, hidden, ndir) && nseq > 0,
-                "lstm_backward_status: not a workspace of this layer size");
+  FNSSL_REQUIRE(nseq > 0 && hidden > 0 && ndir > 0, "lstm_backward_status: empty layer");
+  const size_t off = bwd_ws_layout(nseq, hidden, ndir).cluster.off;   // the status word opens the cluster area
+  FNSSL_REQUIRE(workspace_bytes >= off + sizeof(unsigned), "lstm_backward_status: not a workspace of this layer size");
   hipStream_t st = fnssl::as_stream(stream);
-  FNSSL_HIP(hipMemcpyAsync(status, static_cast<const char*>(workspace) + bwd_scratch_bytes(nseq, hidden, ndir), sizeof(unsigned),
-                           hipMemcpyDeviceToHost, st));
+  FNSSL_HIP(hipMemcpyAsync(status, static_cast<const char*>(workspace) + off, sizeof(unsigned), hipMemcpyDeviceToHost, st));
   FNSSL_HIP(hipStreamSynchronize(st));
   return FNSSL_OK;
 }
@@ -201,9 +212,9 @@ static int lstm_backward_impl(const fnssl_lstm_bwd_desc* d, void* stream, int dr
                     (d->c0g == 0 || extent_ok(d->dx_so, d->dx_si, d->dx_st, 2 * d->c0g)) &&
                     (long double)d->nsteps * (H / 16) * kReserveRecs * 1024 < 4.0e9L,
                 "lstm_backward: one sequence group must span < 4 GB");
-  const size_t need = fnssl_lstm_bwd_workspace_bytes(d->nseq, H, d->ndir);
-  if (!d->workspace || d->workspace_bytes < need) {
-    fnssl::set_error("lstm_backward: workspace %zu < %zu bytes", d->workspace_bytes, need);
+  const BwdWsLayout ws = bwd_ws_layout(d->nseq, H, d->ndir);
+  if (!d->workspace || d->workspace_bytes < ws.total) {
+    fnssl::set_error("lstm_backward: workspace %zu < %zu bytes", d->workspace_bytes, ws.total);
     return FNSSL_E_WORKSPACE;
   }
   BwdParams p;
@@ -238,8 +249,8 @@ static int lstm_backward_impl(const fnssl_lstm_bwd_desc* d, void* stream, int dr
   // kernels below as its guarded fallback (they return at once unless the cluster kernel recorded a hand-off it gave up on)
   BwdClusterParams cp{};
   if (bwdc_handles(p, H, cp)) {
-    void* cws = static_cast<char*>(d->workspace) + bwd_scratch_bytes(d->nseq, H, d->ndir);
-    const int rc = backward_cluster(p, cp, cws, st);
+    void* cws = static_cast<char*>(d->workspace) + ws.cluster.off;
+    const int rc = backward_cluster(p, cp, cws, ws.cluster.bytes, st);
     if (rc == FNSSL_OK) {
       if (family) *family = FNSSL_LSTM_FAMILY_BWD_CLUSTER;
       if (dry) return FNSSL_OK;

@@ -360,18 +360,23 @@ def cluster_fallbacks(device=None, reset: bool = False) -> int:
 
 
 
+def _ws_key(device, tag: str):
+    """Key of the workspace cache: (device index, that device's current stream, tag)."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return (device.index, torch.cuda.current_stream(device).cuda_stream, tag)
+
+
 def _workspace(nbytes: int, device, tag: str):
     """Scratch buffer for one op, cached per (device, stream, tag): two forwards issued on different HIP streams
     never share scratch, and on one stream the ops that use a tag are ordered anyway.  A buffer that has to
     grow is replaced; the old one goes back to torch's caching allocator, which keeps it reserved for this
     stream's pending work."""
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream, tag)
+    key = _ws_key(device, tag)
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+        buf = torch.empty(int(nbytes), dtype=torch.uint8, device=torch.device("cuda", key[0]))
         _ws_cache[key] = buf
     return buf
 
@@ -570,8 +575,10 @@ def lstm_cluster_status(nseq: int, hidden: int, ndir: int, device=None) -> int:
     arrived; otherwise the layer was recomputed by the guarded fallback kernels of the same call — see
     fnssl_lstm_cluster_status).  `nseq, hidden, ndir` as in the lstm_layer call that used the workspace."""
     lib = _lib.load()
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    ws = _workspace(lib.fnssl_lstm_workspace_bytes_ex(nseq, hidden, ndir, 0), device, "lstm")   # (the cached buffer: never shrinks)
+    ws = _ws_cache.get(_ws_key("cuda" if device is None else device, "lstm"))
+    if ws is None:
+        raise RuntimeError("fnssl.lstm_cluster_status: no LSTM call has run on this device's current stream yet "
+                           "(there is no LSTM workspace to read the status word from)")
     out = C.c_uint(0xffffffff)
     check(lib.fnssl_lstm_cluster_status(ws.data_ptr(), ws.numel(), nseq, hidden, ndir, _stream(), C.byref(out)),
           "lstm_cluster_status")

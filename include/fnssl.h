@@ -219,7 +219,8 @@ typedef struct {
   int q_inner;         /* see fnssl_view                                      */
   int nsteps;          /* sequence length                                     */
   const float* wpack[2];   /* DEVICE packed weights per direction (fnssl_lstm_pack) */
-  float* workspace;    /* DEVICE, >= fnssl_lstm_workspace_bytes()             */
+  float* workspace;    /* DEVICE, >= fnssl_lstm_workspace_bytes_ex() of the call's precision
+                        * (fnssl_lstm_workspace_bytes() covers every precision) */
   size_t workspace_bytes;
   int variant;         /* 0 = default; see DESIGN.md (kernel variants)        */
   /* training forward (autograd's "save for backward"): when non-NULL the kernel also stores the gate
@@ -277,14 +278,17 @@ size_t fnssl_lstm_packed_floats(int c0, int c2, int hidden);
 int fnssl_lstm_pack(const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
                     int c0, int c2, int hidden, float* packed);
 
-/* Scratch a call of fnssl_lstm_forward needs: cell state of a carried (streaming) call, the re-ordered weight stream of the
- * two-slices-per-pass kernel (hidden 256) and — hidden 128 / 256 — the hand-off area of the cluster-resident bf16 kernels
- * (status word, tags, two parities of h_t operand records: 0.5 / 0.4 MiB per 512 / 768 sequences).  One workspace per stream:
- * two calls in flight must not share it. */
+/* Scratch a call of fnssl_lstm_forward needs, front to back: the cell state (what a carried, streaming call carries), the
+ * pair- / quad-interleaved copy of the weight stream (hidden 256), the hand-off area of the cluster-resident kernels (hidden
+ * 128 / 256: status word, tags and — bf16 "wide" calls — two parities of h_t operand records, 0.5 / 0.4 MiB per 512 / 768
+ * sequences) and — fp32, hidden 256, one direction — a snapshot of the carried cell state.  This function returns the
+ * maximum over the precisions, so its buffer serves every call of the shape.  One workspace per stream: two calls in flight
+ * must not share it. */
 size_t fnssl_lstm_workspace_bytes(int nseq, int hidden, int ndir);
-/* The same for one `precision` (fnssl_lstm_desc.precision) — what fnssl_lstm_forward actually checks: fp32 calls need only
- * the status word and 8 tag words per 16-sequence group of the cluster-resident fp32 kernel (~2 B per sequence) where the
- * bf16 "wide" calls need ~513 B per sequence; training / streaming / per-stream caches should size with this one. */
+/* The same for one `precision` (fnssl_lstm_desc.precision) — what fnssl_lstm_forward actually checks: fp32 calls need the
+ * status word and 8 tag words per 16-sequence group of the cluster-resident fp32 kernel (~2 B per sequence) plus, at hidden
+ * 256 with one direction, the cell-state snapshot (~1 KiB per sequence), where the bf16 "wide" calls need ~513 B per
+ * sequence; training / streaming / per-stream caches should size with this one. */
 size_t fnssl_lstm_workspace_bytes_ex(int nseq, int hidden, int ndir, int precision);
 
 /* Host-only query of the launch planner of fnssl_lstm_forward (full-chip fp32 launches, hidden 128 / 256): the rounds
@@ -327,9 +331,10 @@ int fnssl_lstm_forward(const fnssl_lstm_desc* d, void* stream);
 int fnssl_lstm_plan(const fnssl_lstm_desc* d, int* family, int* rounds);
 
 /* Status word the cluster-resident kernels left in a workspace that fnssl_lstm_forward has used with the same
- * (nseq, hidden, ndir): 0 = every hand-off arrived; 0xKnnnn = a wave of cluster nnnn gave up after the spin limit
- * (K = 1 bf16 tag, 3 fp32 tag, 4 fp32 drift bound, 5 aborted because another wave had) — the layer was then re-run by
- * the guarded fallback kernels of the same call, so this is a diagnostic, not an error.  Synchronises with `stream`. */
+ * (nseq, hidden, ndir) and any precision (the word's offset does not depend on it): 0 = every hand-off arrived; 0xKnnnn =
+ * a wave of cluster nnnn gave up after the spin limit (K = 1 bf16 tag, 3 fp32 tag, 4 fp32 drift bound, 5 aborted because
+ * another wave had) — the layer was then re-run by the guarded fallback kernels of the same call, so this is a diagnostic,
+ * not an error.  Synchronises with `stream`. */
 int fnssl_lstm_cluster_status(const void* workspace, size_t workspace_bytes, int nseq, int hidden, int ndir, void* stream,
                               unsigned* status);
 

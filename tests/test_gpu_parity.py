@@ -1259,6 +1259,15 @@ def test_lstm_bf16_wide_matches_oracle_and_narrow_kernel(dev, mode, H, bidir, c0
     assert np.abs(got - O.bf16_round(want)).mean() < 2e-4
 
 
+def test_lstm_cluster_status_reads_only_an_existing_lstm_workspace(dev):
+    """The status read allocates nothing: on a stream no LSTM call has run on there is no status word to read."""
+    from fnssl import ops
+    with torch.cuda.device(dev), torch.cuda.stream(torch.cuda.Stream(dev)):
+        ops._ws_cache.pop(ops._ws_key(dev, "lstm"), None)   # (torch pools its streams: an earlier test may have used this one)
+        with pytest.raises(RuntimeError, match="no LSTM call has run"):
+            ops.lstm_cluster_status(512, 256, 1, dev)
+
+
 @pytest.mark.parametrize("nb,nt,nf", [
     (2, 7, 256),      # 512 sequences: exactly one cluster
     (3, 5, 200),      # 600 sequences: a second cluster with 88 live sequences (ragged tile, idle waves)
@@ -1297,7 +1306,9 @@ def test_lstm_bf16_cluster_kernel_matches_oracle_and_pair_split(dev, monkeypatch
     monkeypatch.delenv("FNSSL_CLUSTER_SPREAD")
     assert torch.equal(a, s1) and torch.equal(a, s2), "the hand-off depends on which XCD a member runs on"
     with torch.cuda.device(dev):
+        ws = ops._ws_cache[ops._ws_key(dev, "lstm")]
         assert ops.lstm_cluster_status(nb * nf, H, 1, dev) == 0        # no bounded wait ran out
+        assert ops._ws_cache[ops._ws_key(dev, "lstm")].data_ptr() == ws.data_ptr()   # read from the buffer the kernel wrote
     monkeypatch.setenv("FNSSL_NO_CLUSTER", "1")
     assert plan()[0] == "bf16_pair"
     b = run()

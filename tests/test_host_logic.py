@@ -497,6 +497,47 @@ def test_lstm_workspace_covers_the_cluster_hand_off_area():
     assert ws(0, 256, 1) == 0
 
 
+def test_lstm_workspace_sizes_are_pinned_and_cover_every_precision():
+    """One workspace layout per pass (lstm.hip, lstm_train.hip): fnssl_lstm_workspace_bytes is the maximum of the
+    per-precision sizes (fp32 carries the snapshot of the carried cell state at H = 256, one direction), the per-precision
+    and backward sizes are the ones the library has always returned, and the status reads ask only for the bytes up to
+    their status word, before anything touches a device."""
+    lib = _lib.load()
+    ws, ws_ex, bwd = lib.fnssl_lstm_workspace_bytes, lib.fnssl_lstm_workspace_bytes_ex, lib.fnssl_lstm_bwd_workspace_bytes
+    nseqs = sorted({1, 15, 16, 17, 255, 256, 257, 512, 767, 768, 769, 16384, 65536, 70000} | set(range(1, 70001, 4999)))
+    for n in nseqs:
+        for h in (16, 32, 64, 128, 256):
+            for d in (1, 2):
+                assert ws(n, h, d) == max(ws_ex(n, h, d, p) for p in (0, 1, 2)), (n, h, d)
+    # H = 256, one direction: fp32 and bf16 "wide" sizes, and the bound over precisions
+    for n, fp32, bf16w in ((512, 3836672, 3540480), (16384, 36406016, 36078080), (65536, 137265920, 136839680)):
+        assert (ws_ex(n, 256, 1, 0), ws_ex(n, 256, 1, 2), ws(n, 256, 1)) == (fp32, bf16w, fp32)
+    assert ws(512, 256, 1) == 3836672
+    pinned = {(1, 128, 1): (156192, 139776, 534016, 295488), (100, 128, 2): (410560, 377344, 1165824, 787840),
+              (19200, 128, 2): (20033024, 19923456, 47520256, 40032768), (7164, 256, 1): (17494784, 9830912, 17185280, 15249920),
+              (512, 256, 1): (3836672, 3015168, 3540480, 1591808)}
+    for (n, h, d), want in pinned.items():
+        assert tuple(ws_ex(n, h, d, p) for p in (0, 1, 2)) + (bwd(n, h, d),) == want, (n, h, d)
+
+    # status words: the forward one opens the cluster area behind the cell state and (H = 256) the interleaved weight copy,
+    # the backward one the area behind the carried dh / dc records (both: 16 spare groups per direction, + 256 bytes)
+    def fwd_word(n, h, d):
+        cell = ((n + 15) // 16 + 16) * d * (h // 16) * 1024 + 256
+        return cell + (d * 16 * 34 * 4096 if h == 256 else 0)
+
+    def bwd_word(n, h, d):
+        return ((n + 15) // 16 + 16) * d * 2 * (h // 16) * 1024 + 256
+
+    fake = C.c_void_p(1 << 20)   # never dereferenced: the size check fails first
+    word = C.c_uint(0)
+    for n, h, d in ((1, 128, 1), (100, 128, 2), (19200, 128, 2), (512, 256, 1), (7164, 256, 1)):
+        assert fwd_word(n, h, d) + 256 == ws_ex(n, h, d, 1)            # bf16: the cluster area is the status block alone
+        assert fwd_word(n, h, d) < ws_ex(n, h, d, 2) and fwd_word(n, h, d) < ws_ex(n, h, d, 0)
+        assert lib.fnssl_lstm_cluster_status(fake, fwd_word(n, h, d) + 3, n, h, d, None, C.byref(word)) == -1   # FNSSL_E_INVALID
+        assert bwd_word(n, h, d) < bwd(n, h, d)
+        assert lib.fnssl_lstm_backward_status(fake, bwd_word(n, h, d) + 3, n, h, d, None, C.byref(word)) == -1   # FNSSL_E_INVALID
+
+
 def test_train_mode_forward_has_no_cpu_fallback_and_flat_layout_matches_named_parameters():
     """The autograd route (fnssl/autograd.py) is HIP-only like everything else: a CPU tensor in train mode raises instead
     of silently running nn.LSTM; the flat layout / layer table it shares with TrainEngine follows named_parameters."""
