@@ -501,7 +501,7 @@ static int lstm_forward_impl(const fnssl_lstm_desc* d, void* stream, bool dry, i
           FNSSL_CHECK_LAUNCH("pair_stream_kernel");
           rc = s4 ? launch_static4_h256(p2, mode, nwg, st) : launch_static3_h256(p2, mode, nwg, st);
           if (rc != kNoStatic) {
-            report(FNSSL_LSTM_FAMILY_STATIC3);
+            report(s4 ? FNSSL_LSTM_FAMILY_STATIC4 : FNSSL_LSTM_FAMILY_STATIC3);
             return rc;
           }
         }

@@ -328,6 +328,7 @@ int fnssl_lstm_forward(const fnssl_lstm_desc* d, void* stream);
 #define FNSSL_LSTM_FAMILY_TRAIN 12          /* reserve-saving training forward (lstm_train.hip)                 */
 #define FNSSL_LSTM_FAMILY_BWD 13            /* fnssl_lstm_backward_plan: per-wave / split BPTT kernels (lstm_train.h) */
 #define FNSSL_LSTM_FAMILY_BWD_CLUSTER 14    /* ... cluster-resident BPTT kernel (lstm_bwdc.h) + guarded fallback */
+#define FNSSL_LSTM_FAMILY_STATIC4 15        /* STATIC3's rounds, four slices per pass (lstm_static4.h; NO_STATIC4: STATIC3) */
 int fnssl_lstm_plan(const fnssl_lstm_desc* d, int* family, int* rounds);
 
 /* Status word the cluster-resident kernels left in a workspace that fnssl_lstm_forward has used with the same

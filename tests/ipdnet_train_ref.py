@@ -42,12 +42,26 @@ class RefConv(nn.Module):
         self.conv2 = nn.Conv2d(hid, hid, 3, padding=(1, 2), bias=False)
         self.conv3 = nn.Conv2d(hid, out, 3, padding=(1, 2), bias=False)
 
-    def forward(self, x):
-        y = torch.relu(self.conv1(x))[..., :-2]
+    def forward(self, x, relu_masks=None):
+        """``relu_masks`` (optional, bool [nb, hid, nf, nt'] per ReLU): the branch each ReLU takes instead of the sign
+        of its own input, so that a float64 run can follow an fp32 run where a pre-activation lies within rounding of 0.
+        ``self.mask_flips`` then lists per ReLU (positions where the mask differs from the sign, the largest |input|
+        there relative to the largest |input|)."""
+        m = relu_masks if relu_masks is not None else (None, None)
+        self.mask_flips = []
+        y = self._relu(self.conv1(x)[..., :-2], m[0])
         y = nn.functional.avg_pool2d(y, (1, 3))
-        y = torch.relu(self.conv2(y))[..., :-2]
+        y = self._relu(self.conv2(y)[..., :-2], m[1])
         y = nn.functional.avg_pool2d(y, (1, 4))
         return torch.tanh(self.conv3(y)[..., :-2])
+
+    def _relu(self, z, mask):
+        if mask is None:
+            return torch.relu(z)
+        a = z.detach().abs()
+        flip = (z.detach() > 0) != mask
+        self.mask_flips.append((int(flip.sum()), float(a[flip].max() / a.max()) if flip.any() else 0.0))
+        return z * mask
 
 
 class RefIPDnet(nn.Module):
@@ -57,7 +71,7 @@ class RefIPDnet(nn.Module):
         self.block_2 = RefFNblock(hidden_size, hidden_size, input_size, is_online, False)
         self.conv = RefConv(hidden_size + input_size, 2 * (input_size // 2 - 1) * max_track)
 
-    def forward(self, x, masks):
+    def forward(self, x, masks, relu_masks=None):
         x = x.permute(0, 3, 2, 1)
         nb, nt, nf, nc = x.shape
         fb = x.reshape(nb * nt, nf, nc)
@@ -65,7 +79,8 @@ class RefIPDnet(nn.Module):
         x = self.block_1(x, fb, nbs, masks[0], masks[1])
         x = self.block_2(x, fb, nbs, masks[2], masks[3])
         nt2 = nt // 12
-        x = self.conv(x.permute(0, 3, 2, 1)).permute(0, 3, 2, 1).reshape(nb, nt2, nf, 2, -1).permute(0, 1, 3, 2, 4)
+        x = self.conv(x.permute(0, 3, 2, 1), relu_masks).permute(0, 3, 2, 1)
+        x = x.reshape(nb, nt2, nf, 2, -1).permute(0, 1, 3, 2, 4)
         return x.reshape(nb, nt2, 2, nf * 2, -1).permute(0, 1, 3, 4, 2)
 
 

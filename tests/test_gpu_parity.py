@@ -1126,7 +1126,7 @@ def test_config2_full_batch_independence_and_oracle(dev):
     wf = [torch.empty(int(_ops._lib.load().fnssl_lstm_packed_floats(256, 0, 128)), device=dev)] * 2
     wn = [torch.empty(int(_ops._lib.load().fnssl_lstm_packed_floats(256, 0, 256)), device=dev)]
     assert _ops.lstm_plan("full", big, None, None, wf, 128, big, skip=big, out_sum=big) == ("f32_cluster", 1)
-    assert _ops.lstm_plan("narrow", big, None, None, wn, 256, bign, skip=big, out_sum=bign) == ("static3", 1)
+    assert _ops.lstm_plan("narrow", big, None, None, wn, 256, bign, skip=big, out_sum=bign) == ("static4", 1)
     del big, bign
     torch.cuda.empty_cache()
     out = model.predict_step(batch, 0)
@@ -1541,7 +1541,7 @@ def test_few_sequence_launches_take_the_slice_resident_cluster_kernel_and_equal_
     assert ops.cluster_fallbacks(dev) == 0
     monkeypatch.setenv("FNSSL_NO_F32_SMALL", "1")
     fam, _ = run(plan=True)
-    assert fam in ("split", "split_static", "static", "static3", "generic"), fam
+    assert fam in ("split", "split_static", "static", "static3", "static4", "generic"), fam
     b, bsum = run()
     assert torch.isfinite(a).all()
     assert torch.equal(a, b) and torch.equal(a, a2), "cluster kernel differs from the split kernels / is not repeatable"
@@ -1676,13 +1676,13 @@ def test_lstm_operand_ring_kernel_equals_one_slice_kernel(dev, monkeypatch, c2, 
 
     for k in ("FNSSL_NO_STATIC3", "FNSSL_NO_STATIC2", "FNSSL_NO_STATIC4"):
         monkeypatch.delenv(k, raising=False)
-    assert run(plan=True) == ("static3", 1), run(plan=True)
+    assert run(plan=True) == ("static4", 1), run(plan=True)
     a, asum = run()                                      # round 6: four slices per pass, LDS-DMA weight ring (lstm_static4.h)
     a6, a6sum = run()                                    # (and again: repeatable)
     for _ in range(3):                                   # the DMA ring's counted waits: a race would show between launches
         r_, rs_ = run()
         assert torch.equal(r_, a) and (not summed or torch.equal(rs_, asum)), "four-slice kernel is not repeatable"
-    monkeypatch.setenv("FNSSL_NO_STATIC4", "1")          # two slices per pass (lstm_static3.h), same family name
+    monkeypatch.setenv("FNSSL_NO_STATIC4", "1")          # two slices per pass (lstm_static3.h)
     assert run(plan=True) == ("static3", 1)
     p2, p2sum = run()
     assert torch.equal(a, p2) and (not summed or torch.equal(asum, p2sum)), "four slices per pass differ from two"

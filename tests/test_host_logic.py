@@ -29,6 +29,16 @@ def test_library_exports_every_declared_symbol():
     assert lib.fnssl_abi_version() == _lib.ABI_VERSION == 19
 
 
+def test_lstm_family_names_follow_the_header():
+    """Every FNSSL_LSTM_FAMILY_* value of include/fnssl.h has its lower-case name in _lib.LSTM_FAMILY (the retired
+    STATIC2 keeps its marker), so the plan queries report the headline four-slice kernel as "static4", not "static3"."""
+    header = open(os.path.join(ROOT, "include", "fnssl.h")).read()
+    declared = {int(v): n.lower() for n, v in re.findall(r"#define FNSSL_LSTM_FAMILY_([A-Z0-9_]+) (\d+)", header)}
+    assert declared[15] == "static4" and declared[7] == "static3"
+    declared[3] = "static2 (retired)"
+    assert _lib.LSTM_FAMILY == declared
+
+
 def test_shape_helpers_match_reference_formulas():
     for ns in (512, 767, 768, 64000, 77056, 6400):
         assert ops.num_frames(ns) == O.n_frames(ns)

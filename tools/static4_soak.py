@@ -36,7 +36,7 @@ for c2, summed in ((0, True), (0, False), (4, True)):
     ref, refsum = out.clone(), (osum.clone() if summed else None)
     os.environ.pop("FNSSL_NO_STATIC4")
     _lib.refresh_tuning()
-    assert ops.lstm_layer("narrow", x0, None, x2, w, H, out, skip=skip, out_sum=osum, plan_only=True)[0] == "static3"
+    assert ops.lstm_layer("narrow", x0, None, x2, w, H, out, skip=skip, out_sum=osum, plan_only=True)[0] == "static4"
     for label in ("alone", "beside a competing stream"):
         bad = 0
         t0 = time.perf_counter()
