@@ -1,0 +1,144 @@
+"""The Lightning module of the reference's online IPDnet (``MyModel`` of IPDnet/runIPDnetOn.py:80-301) restated over the
+HIP path: a batch ``(mic_sig_batch [nb, ns, nch], {'doa' [nb, nseg, 2, nsrc], 'dp_signal' [nb, ns, nch, nsrc]})`` becomes
+features, DP-VAD, per-source DP-IPD targets and a frame-level PIT-MSE loss with a ``grad_fn`` without leaving the
+device:
+
+    data_preprocess   :237-290   STFT once (features + VAD), ``fnssl_dp_vad``, ``fnssl_ipdnet_targets``
+    cal_loss          :196-206   ``fnssl_pit_mse_loss`` (``fnssl.ipdnet_step.PitMSE``)
+    training_step     :144-154   validation_step / test_step compute and log the loss
+    configure_optimizers :292-301   Adam(lr 5e-4) + ExponentialLR(0.975)
+    predict_step      :182-186
+
+``pytorch_lightning`` is optional: with it ``MyModel`` is a ``LightningModule``, without it an ``nn.Module`` whose
+methods are called directly.  The constructor is the reference's plus a trailing ``arch``: ``None`` builds ``IPDnet()``
+as the reference does; arrays of more than two microphones pass ``IPDnet(2 * nmic, 256, max_source, True)`` (the
+reference tells its users to edit that line).  ``compile`` is accepted and ignored (there is nothing to compile).
+
+Out of scope: the metrics (``get_metric`` / ``PredDOA.evaluate``), datasets and the CLI, runIPDnetOff.py's
+whole-utterance normalisation, and TRAINING the hidden-128 two-microphone default — ``IPDnet()`` keeps raising its
+forward-only error in ``train()`` mode (the full-band H = 64 backward kernels do not exist yet), so with ``arch=None``
+everything here works except the network half of ``loss.backward()``.
+"""
+import os
+import sys
+
+import numpy as np
+import torch
+
+_PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _PKG not in sys.path:
+    sys.path.insert(0, _PKG)
+
+from fnssl import ipdnet_step, ops                                  # noqa: E402
+from IPDnet.FixedAarryIPDnet import IPDnet                          # noqa: E402
+
+try:  # optional, absent in the build image
+    from pytorch_lightning import LightningModule as _Base
+except Exception:  # pragma: no cover
+    _Base = torch.nn.Module
+
+_DEFAULT_MICS = ((-0.04, 0.0, 0.0), (0.04, 0.0, 0.0))
+
+
+class MyModel(_Base):
+    def __init__(self, tar_useVAD: bool = True, ch_mode: str = 'M', res_the: int = 1, res_phi: int = 180, fs: int = 16000,
+                 win_len: int = 512, nfft: int = 512, win_shift_ratio: float = 0.5, max_source: int = 2, device: str = 'cuda',
+                 mic_pos=None, compile: bool = False, is_linear_array: bool = True, is_planar_array: bool = True,
+                 exp_name: str = 'exp', arch=None):
+        super().__init__()
+        if (win_len, nfft, win_shift_ratio) != (512, 512, 0.5):
+            raise ValueError("the MI355X path is built for win_len = nfft = 512, hop 256 (runIPDnetOn.py:34-35)")
+        if ch_mode != 'M':
+            raise ValueError("IPDnet's targets are the reference-microphone pairs (ch_mode 'M'): DPIPD.forward fills only "
+                             "those rows (IPDnet/Module.py:386-387), got %r" % (ch_mode,))
+        if not 1 <= int(max_source) <= ipdnet_step.MAX_SOURCES:
+            raise ValueError("max_source must be 1..%d, got %r" % (ipdnet_step.MAX_SOURCES, max_source))
+        self.arch = IPDnet() if arch is None else arch
+        self.tar_useVAD = tar_useVAD
+        self.ch_mode = ch_mode
+        self.nfft = nfft
+        self.fre_max = fs / 2
+        self.max_source = int(max_source)
+        mic = _DEFAULT_MICS if mic_pos is None else mic_pos
+        mic = mic.detach().cpu().numpy() if isinstance(mic, torch.Tensor) else np.asarray(mic)
+        self.mic_pos = np.ascontiguousarray(mic, dtype=np.float32).reshape(-1, 3)
+        if 2 * self.mic_pos.shape[0] != getattr(self.arch, "input_size", 2 * self.mic_pos.shape[0]):
+            raise ValueError("mic_pos has %d microphones but the network takes %d channels (pass arch=IPDnet(2 * nmic, 256, "
+                             "max_source, True))" % (self.mic_pos.shape[0], self.arch.input_size))
+        self.is_linear_array, self.is_planar_array = is_linear_array, is_planar_array
+        self.res_the, self.res_phi, self.exp_name = res_the, res_phi, exp_name
+        self.speed = 340.0
+        self.vad_th = 0.001                                          # runIPDnetOn.py:274
+        self.fre_range_used = range(1, int(self.nfft / 2) + 1, 1)
+        self.dev = device
+
+    def forward(self, x):
+        return self.arch(x)
+
+    def _log(self, name, value, **kw):
+        if hasattr(self, "log") and getattr(self, "_trainer", None) is not None:
+            self.log(name, value, **kw)
+
+    def _step_loss(self, batch):
+        data_batch = self.data_preprocess(batch[0], batch[1])
+        pred_batch = self(data_batch[0])
+        return self.cal_loss(pred_batch=pred_batch, gt_batch=data_batch[1:])
+
+    def training_step(self, batch, batch_idx: int = 0):
+        loss = self._step_loss(batch)
+        self._log("train/loss", loss, prog_bar=True)
+        return {"loss": loss}
+
+    def validation_step(self, batch, batch_idx: int = 0):
+        """The loss of runIPDnetOn.py:156-167; its DOA metrics are out of scope (module docstring)."""
+        loss = self._step_loss(batch)
+        self._log("valid/loss", loss, sync_dist=True)
+        return loss
+
+    def test_step(self, batch, batch_idx: int = 0):
+        loss = self._step_loss(batch)
+        self._log("test/loss", loss, sync_dist=True)
+        return loss
+
+    @torch.no_grad()
+    def predict_step(self, batch, batch_idx: int = 0):
+        """batch [nb, nch, ns] -> the first utterance's prediction [nt // 12, 512, nmic - 1, max_source] (:182-186)."""
+        data_batch = self.data_preprocess(mic_sig_batch=batch.permute(0, 2, 1))
+        return self.forward(data_batch[0])[0]
+
+    def cal_loss(self, pred_batch=None, gt_batch=None, batch_idx=None):
+        """Frame-level PIT-MSE (:196-206) — one HIP kernel that emits its own gradient; a scalar with a ``grad_fn``."""
+        return ipdnet_step.PitMSE.apply(pred_batch, gt_batch[1])
+
+    def data_preprocess(self, mic_sig_batch=None, acoustic_scene_batch=None, vad_batch=None, eps=1e-6):
+        """:237-290 on device.  Returns [features [nb, 2 nch, 256, nt], doa, ipd.view(nb * nt2, 512, nmic - 1, nsrc),
+        dp_vad (if ``tar_useVAD``)]; without ``acoustic_scene_batch`` just the features (``predict_step``)."""
+        sig = mic_sig_batch.to(self.dev)
+        spec, magsum = ops.stft(sig)                                                 # once, for the features and the VAD
+        x, _ = ops.array_features(spec, magsum, eps, 280, 0)
+        data = [x.permute(0, 3, 2, 1)]                                               # = ops.preprocess_array(sig)
+        if acoustic_scene_batch is None:
+            return data
+        dp = acoustic_scene_batch['dp_signal'].to(self.dev)
+        if dp.ndim != 4 or dp.shape[3] != self.max_source or tuple(dp.shape[:2]) != tuple(sig.shape[:2]):
+            raise RuntimeError("data_preprocess: dp_signal must be [nb, ns, nch, %d] like the mixture %s, got %s"
+                               % (self.max_source, tuple(sig.shape), tuple(dp.shape)))
+        dp_spec, _ = ops.stft(dp[:, :, 0, :])                                        # channel 0 only (:230), read in place
+        dp_vad = ipdnet_step.dp_vad(spec, dp_spec)
+        doa = acoustic_scene_batch['doa'].to(self.dev)
+        if tuple(doa.shape[:2]) != tuple(dp_vad.shape[:2]) or doa.shape[-1] != self.max_source:
+            raise RuntimeError("data_preprocess: doa %s does not match the %d segments x %d sources of the signals"
+                               % (tuple(doa.shape), dp_vad.shape[1], self.max_source))
+        mic, non_source = ipdnet_step.non_source_device(self.mic_pos, doa.device)
+        ipd = ipdnet_step.ipdnet_targets(doa.float(), dp_vad, mic, non_source, 1, int(self.nfft / 2), int(self.nfft / 2) + 1,
+                                         self.fre_max, self.speed, self.vad_th)
+        nb, nt2, nf2, nm1, nsrc = ipd.shape
+        data += [doa, ipd.view(nb * nt2, nf2, nm1, nsrc)]
+        if self.tar_useVAD:
+            data += [dp_vad]
+        return data
+
+    def configure_optimizers(self):
+        optimizer = torch.optim.Adam(self.arch.parameters(), lr=0.0005)
+        lr_scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=0.975, last_epoch=-1)
+        return {'optimizer': optimizer, 'lr_scheduler': {'scheduler': lr_scheduler, 'monitor': 'valid/loss'}}

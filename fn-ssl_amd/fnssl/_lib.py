@@ -54,6 +54,7 @@ SYMBOLS = [
     "fnssl_lstm_reserve_bytes", "fnssl_lstm_bwd_packed_floats", "fnssl_lstm_pack_bwd", "fnssl_lstm_bwd_workspace_bytes",
     "fnssl_lstm_backward", "fnssl_lstm_backward_plan", "fnssl_lstm_backward_status", "fnssl_lstm_weight_grads_workspace_bytes", "fnssl_lstm_weight_grads", "fnssl_lstm_packed_floats_bf16", "fnssl_lstm_pack_bf16", "fnssl_train_combine", "fnssl_dropout_scale", "fnssl_head_backward_workspace_bytes",
     "fnssl_head_backward", "fnssl_mse_loss", "fnssl_adam_step",
+    "fnssl_pit_mse_workspace_bytes", "fnssl_pit_mse_loss", "fnssl_dp_vad", "fnssl_ipdnet_targets",
     "fnssl_forward_workspace_bytes", "fnssl_forward", "fnssl_timing_enable", "fnssl_timing_collect", "fnssl_timing_select", "fnssl_mfma_f32_peak", "fnssl_mfma_f32_peak_clocks",
     "fnssl_lstm_packed_floats_bf16w", "fnssl_lstm_pack_bf16w",
     "fnssl_train_create", "fnssl_train_destroy", "fnssl_train_param_floats", "fnssl_train_param_offset",
@@ -252,6 +253,11 @@ def load():
     lib.fnssl_head_backward.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp, i, vp, sz, vp]
     lib.fnssl_mse_loss.argtypes = [vp, vp, i, i, i, i, ll, vp, vp, i, vp, sz, vp]
     lib.fnssl_adam_step.argtypes = [vp, vp, vp, vp, ll, f, f, f, f, i, f, vp]
+    lib.fnssl_pit_mse_workspace_bytes.argtypes = [i]
+    lib.fnssl_pit_mse_workspace_bytes.restype = sz
+    lib.fnssl_pit_mse_loss.argtypes = [vp, C.POINTER(ll), vp, i, i, i, i, i, ll, vp, vp, i, vp, vp, sz, vp]
+    lib.fnssl_dp_vad.argtypes = [vp, vp, i, i, i, i, vp, vp]
+    lib.fnssl_ipdnet_targets.argtypes = [vp, vp, i, i, i, vp, i, vp, i, i, i, f, f, f, vp, vp]
     lib.fnssl_array_features.argtypes = [vp, vp, vp, vp, i, i, i, C.c_float, vp, vp, i, vp]
     lib.fnssl_conv3x3_packed_floats.argtypes = [i, i, i]
     lib.fnssl_conv3x3_packed_floats.restype = sz

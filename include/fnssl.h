@@ -479,6 +479,54 @@ int fnssl_mse_loss(const float* pred, const float* gt, int nb, int np, int nt2, 
                    float* dpred, float* loss, int accumulate, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/*
+ * IPDnet's cal_loss (IPDnet/runIPDnetOn.py:196-206) with its gradient: frame-level permutation-invariant MSE.
+ * Logical operands pred, gt [rows, D, nsrc], rows = nb * nt2, D = nf2 * nm1 (nf2 = 2 nf, nm1 = nmic - 1), source innermost
+ * (the reference's reshape(nb * nt, -1, nsrc)).
+ *   gt            contiguous
+ *   pred          read in place through pred_strides, a HOST array of the five element strides of
+ *                 [nb, nt2, nf2, nm1, nsrc] (IPDnet.forward returns a permuted view in train() mode); the strides must
+ *                 address distinct elements; dpred is written through the same strides
+ *   per row       E[i][j] = sum_d (pred[d, i] - gt[d, j])^2; the permutation pm minimising sum_j E[pm[j]][j], searched
+ *                 in itertools.permutations(range(nsrc)) order with a strict "<" (ties keep the earliest: the identity
+ *                 first); dpred[d, pm[j]] = 2 (pred[d, pm[j]] - gt[d, j]) / n_total
+ *   *loss         (DEVICE) = or += sum_rows min / n_total;  n_total as in fnssl_mse_loss (element count of the WHOLE
+ *                 batch, >= rows * D * nsrc when the batch is processed in chunks)
+ *   perm_out      optional DEVICE int [rows]: index of the chosen permutation in that order
+ *   nsrc 1..4.  Reductions are two-stage in a fixed order (no float atomics): two runs give the same bits, and so do a
+ *   strided pred and its contiguous copy.  workspace >= fnssl_pit_mse_workspace_bytes(rows).
+ */
+size_t fnssl_pit_mse_workspace_bytes(int rows);
+int fnssl_pit_mse_loss(const float* pred, const long long* pred_strides, const float* gt, int nb, int nt2, int nf2, int nm1,
+                       int nsrc, long long n_total, float* dpred, float* loss, int accumulate, int* perm_out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * cal_vad (IPDnet/runIPDnetOn.py:224-235): the direct-path voice activity of every source.
+ *   mix_spec  [nb, nch, nt, 257] complex, dp_spec [nb, nsrc, nt, 257] complex: outputs of fnssl_stft — the latter of
+ *             fnssl_stft on the strided view dp_signal[:, :, 0, :] = [nb, ns, nsrc] (only channel 0 is used, :230)
+ *   dp_vad    [nb, nt / 12, nsrc] = mean over the segment's 12 frames (AvgPool2d((12, 1)): frames past the last whole
+ *             segment are dropped) of the mean over all 257 bins of |dp| / |mix channel 0|; fp32 division as torch's
+ *             (x / 0 = inf, 0 / 0 = NaN propagate)
+ */
+int fnssl_dp_vad(const float* mix_spec, const float* dp_spec, int nb, int nch, int nsrc, int nt, float* dp_vad, void* stream);
+
+/*
+ * The ground-truth half of IPDnet's data_preprocess (IPDnet/runIPDnetOn.py:256-283; DPIPD.forward of IPDnet/Module.py:368-403:
+ * reference-microphone pairs, the source axis kept).
+ *   doa [nb, nseg, 2, nsrc] (elevation, azimuth);  dp_vad [nb, nseg, nsrc] or NULL (all active);
+ *   mic_loc DEVICE [nmic, 3];  non_source DEVICE [2 nf_used, nmic - 1] (the Bessel target of silent slots, :209-221)
+ *   ipd [nb, nseg, 2 nf_used, nmic - 1, nsrc]:
+ *     v >  vad_th  [cos | sin](2 pi f_k tau_m), tau_m = r(doa) . (mic_0 - mic_m) / speed in fp32 (the reference is handed
+ *                  fp32 DOAs and an fp32 array), f_k = (bin0 + k) fre_max / (nbins - 1), the phase in double like numpy's,
+ *                  rounded to fp32 once
+ *     v <= vad_th  non_source[:, m]          v NaN: NaN (what :273-283 leave)
+ *   nsrc 1..4, nmic 2..64.  The reference applies the mask whatever tar_useVAD says (:278 is unconditional).
+ */
+int fnssl_ipdnet_targets(const float* doa, const float* dp_vad, int nb, int nseg, int nsrc, const float* mic_loc, int nmic,
+                         const float* non_source, int bin0, int nf_used, int nbins, float fre_max, float speed, float vad_th,
+                         float* ipd, void* stream);
+
 /* torch.optim.Adam (main.py:269-271; no amsgrad, no weight decay) on a flat vector; the gradient is
  * multiplied by grad_scale first (1 / world_size after the sum all-reduce).  step counts from 1. */
 int fnssl_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n,

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """IPDnet training-step throughput at the BASELINE config-3 geometry (IPDnet(16, 256, 2, True): 8 microphones, 256 bins
 x 300 frames, fp32, 64 utterances) with a per-kernel breakdown.  The step is the reference's loop through the drop-in
-module: forward in train() mode, PIT-MSE loss, loss.backward(), torch.optim.Adam(lr=5e-4).  Secondary measurement —
+module: forward in train() mode, PIT-MSE loss (fnssl.ipdnet_step.PitMSE; its own time is reported as ``loss_ms``),
+loss.backward(), torch.optim.Adam(lr=5e-4).  Secondary measurement —
 bench.py's headline stays the inference metric.
 
     python tools/ipdnet_train_bench.py [--utts 64] [--frames 300] [--steps 3] [--warmup 1] [--offline]
@@ -13,14 +14,13 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "fn-ssl_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from IPDnet.FixedAarryIPDnet import IPDnet  # noqa: E402
 from fnssl import ops  # noqa: E402
 from fnssl import weights as W  # noqa: E402
-from ipdnet_train_ref import pit_mse  # noqa: E402
+from fnssl.ipdnet_step import PitMSE  # noqa: E402
 
 ROOF = 157.3e12          # fp32 MFMA peak of the MI355X (flop/s)
 
@@ -65,7 +65,7 @@ def main():
 
     def step():
         opt.zero_grad(set_to_none=True)
-        loss = pit_mse(net(x), gt)
+        loss = PitMSE.apply(net(x), gt)
         loss.backward()
         opt.step()
         return loss
@@ -82,6 +82,18 @@ def main():
         times.append(e0.elapsed_time(e1))
         losses.append(float(loss.item()))
     fallbacks = ops.cluster_fallbacks(dev)
+    # the loss alone (fnssl_pit_mse_loss: error matrices, permutation, gradient, sum) on the network's strided output
+    with torch.no_grad():
+        pred = net(x)
+    PitMSE.apply(pred, gt)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(20):
+        PitMSE.apply(pred, gt)
+    e1.record()
+    torch.cuda.synchronize()
+    loss_ms = e0.elapsed_time(e1) / 20
+    del pred
     ops.timing_enable(True)
     step()
     torch.cuda.synchronize()
@@ -98,7 +110,7 @@ def main():
         "value": round(ms, 1), "unit": "ms/step", "n_gpus": 1, "dtype": "fp32", "data": "synthetic",
         "config": {"workload": "IPDnet(%d, 256, 2, %s) training step, %d utterances, %d bins x %d frames"
                    % (nc, online, args.utts, args.bins, args.frames)},
-        "step_ms_all": [round(t, 1) for t in times],
+        "step_ms_all": [round(t, 1) for t in times], "loss_ms": round(loss_ms, 3),
         "tflop_per_step": {k: round(v / 1e12, 2) for k, v in fl.items()}, "tflop_per_step_total": round(total / 1e12, 2),
         "achieved_tflops": round(total / (ms * 1e-3) / 1e12, 1), "frac_of_fp32_mfma_roof": round(total / (ms * 1e-3) / ROOF, 3),
         "conv_backward_frac_of_roof": {k: kern[k]["frac_of_roof"] for k in ("conv3x3_dgrad", "conv3x3_wgrad") if k in kern},
