@@ -52,19 +52,24 @@ ipd2doa_kernel(const float* __restrict__ pred, long long sb, long long sp, long 
     if (s == 0)
       for (int c = tid; c < ncand; c += 256) ss[((long long)b * nt + t) * ncand + c] = score[c];
     if (wave == 0) {
-      // first maximum (torch.argmax): lane-strided scan, then reduce (value desc, index asc)
-      float bv = -INFINITY;
-      int bi = 0x7fffffff;
-      for (int c = lane; c < ncand; c += 64)
-        if (score[c] > bv) {
-          bv = score[c];
+      // torch.argmax: a NaN counts as the maximum and the first one wins; otherwise the first maximum, -inf included.
+      // Every lane starts from candidate 0 (never from a sentinel), so best_s is in [0, ncand) whatever the scores
+      // hold; lane-strided scan in ascending c, then reduce (NaN first, value desc, index asc).
+      float bv = score[0];
+      int bi = 0;
+      for (int c = lane; c < ncand; c += 64) {
+        const float v = score[c];
+        if (v > bv || (v != v && bv == bv)) {
+          bv = v;
           bi = c;
         }
+      }
 #pragma unroll
       for (int d = 32; d >= 1; d >>= 1) {
         const float ov = __shfl_xor(bv, d, 64);
         const int oi = __shfl_xor(bi, d, 64);
-        if (ov > bv || (ov == bv && oi < bi)) {
+        const bool on = ov != ov, bn = bv != bv;
+        if (on ? (!bn || oi < bi) : (!bn && (ov > bv || (ov == bv && oi < bi)))) {
           bv = ov;
           bi = oi;
         }

@@ -599,6 +599,11 @@ int fnssl_linear(const float* x, int m, int k, const float* wt, const float* b, 
  *   ss    [nb, nt, ncand]    spatial spectrum before any subtraction
  *   idx   [nb, nt, nsrc]     winning candidate per source (int32)
  *   vad   [nb, nt, nsrc]     1 ('kNum') or the projection ratio ('unkNum', unk_num = 1)
+ * Non-finite predictions: the choice follows torch.argmax (Module.py:554) — a NaN score counts as the maximum and the
+ * first one wins, otherwise the first maximum, -inf included — so idx is always in [0, ncand).  A segment that holds a
+ * NaN has only NaN scores: idx = 0 for every source, ss and the ratio ('unkNum' vad) are NaN, 'kNum' vad stays 1.  A
+ * segment that holds +-inf gets scores of +-inf and NaN and the index torch.argmax gives on them.  Other segments are
+ * not affected.
  */
 /*
  * DP-IPD TARGETS of the training step: replaces DPIPD.forward(source_doa) (FN-SSL/Lightning/Module.py:464-498) and the
