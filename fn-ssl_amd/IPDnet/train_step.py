@@ -5,7 +5,9 @@ device:
 
     data_preprocess   :237-290   STFT once (features + VAD), ``fnssl_dp_vad``, ``fnssl_ipdnet_targets``
     cal_loss          :196-206   ``fnssl_pit_mse_loss`` (``fnssl.ipdnet_step.PitMSE``)
-    training_step     :144-154   validation_step / test_step compute and log the loss
+    training_step     :144-154
+    validation_step / test_step :156-180   the loss, then ``get_metric`` (``IPDnet.Module.PredDOA``): the template search of
+                                 all tracks and ACC / MDR / FAR / MAE / RMSE on device, logged as ``valid/<m>`` / ``test/<m>``
     configure_optimizers :292-301   Adam(lr 5e-4) + ExponentialLR(0.975)
     predict_step      :182-186
 
@@ -14,7 +16,7 @@ methods are called directly.  The constructor is the reference's plus a trailing
 as the reference does; arrays of more than two microphones pass ``IPDnet(2 * nmic, 256, max_source, True)`` (the
 reference tells its users to edit that line).  ``compile`` is accepted and ignored (there is nothing to compile).
 
-Out of scope: the metrics (``get_metric`` / ``PredDOA.evaluate``), datasets and the CLI, runIPDnetOff.py's
+Out of scope: datasets and the CLI, the ``np.save`` dumps of ``test_step``'s evaluation, runIPDnetOff.py's
 whole-utterance normalisation, and TRAINING the hidden-128 two-microphone default — ``IPDnet()`` keeps raising its
 forward-only error in ``train()`` mode (the full-band H = 64 backward kernels do not exist yet), so with ``arch=None``
 everything here works except the network half of ``loss.backward()``.
@@ -31,6 +33,7 @@ if _PKG not in sys.path:
 
 from fnssl import ipdnet_step, ops                                  # noqa: E402
 from IPDnet.FixedAarryIPDnet import IPDnet                          # noqa: E402
+from IPDnet.Module import PredDOA                                   # noqa: E402
 
 try:  # optional, absent in the build image
     from pytorch_lightning import LightningModule as _Base
@@ -71,6 +74,10 @@ class MyModel(_Base):
         self.vad_th = 0.001                                          # runIPDnetOn.py:274
         self.fre_range_used = range(1, int(self.nfft / 2) + 1, 1)
         self.dev = device
+        # mapping IPD to DOA and calculating the metrics (runIPDnetOn.py:127)
+        self.get_metric = PredDOA(mic_location=self.mic_pos, is_linear_array=is_linear_array, is_planar_array=is_planar_array,
+                                  max_track=self.max_source, dev=device)
+        self.last_metrics = None
 
     def forward(self, x):
         return self.arch(x)
@@ -79,10 +86,27 @@ class MyModel(_Base):
         if hasattr(self, "log") and getattr(self, "_trainer", None) is not None:
             self.log(name, value, **kw)
 
-    def _step_loss(self, batch):
+    def _forward_loss(self, batch):
+        """(loss, pred_batch, gt_batch) of one batch: data_preprocess, forward, cal_loss."""
         data_batch = self.data_preprocess(batch[0], batch[1])
         pred_batch = self(data_batch[0])
-        return self.cal_loss(pred_batch=pred_batch, gt_batch=data_batch[1:])
+        gt_batch = data_batch[1:]
+        return self.cal_loss(pred_batch=pred_batch, gt_batch=gt_batch), pred_batch, gt_batch
+
+    def _step_loss(self, batch):
+        return self._forward_loss(batch)[0]
+
+    def _eval_step(self, batch, stage, idx):
+        """:156-180 — the loss as ``_step_loss`` forms it, then the metrics of the same prediction under ``no_grad``; the
+        dict of one-element device tensors stays on ``self.last_metrics`` and is logged when a trainer is attached."""
+        loss, pred_batch, gt_batch = self._forward_loss(batch)
+        self._log(stage + "/loss", loss, sync_dist=True)
+        with torch.no_grad():
+            metric = self.get_metric(pred_batch=pred_batch, gt_batch=gt_batch, idx=idx)
+        self.last_metrics = metric
+        for m in metric:
+            self._log(stage + '/' + m, metric[m], sync_dist=True)
+        return loss
 
     def training_step(self, batch, batch_idx: int = 0):
         loss = self._step_loss(batch)
@@ -90,15 +114,11 @@ class MyModel(_Base):
         return {"loss": loss}
 
     def validation_step(self, batch, batch_idx: int = 0):
-        """The loss of runIPDnetOn.py:156-167; its DOA metrics are out of scope (module docstring)."""
-        loss = self._step_loss(batch)
-        self._log("valid/loss", loss, sync_dist=True)
-        return loss
+        """The loss and the DOA metrics of runIPDnetOn.py:156-167; returns the loss."""
+        return self._eval_step(batch, "valid", None)
 
     def test_step(self, batch, batch_idx: int = 0):
-        loss = self._step_loss(batch)
-        self._log("test/loss", loss, sync_dist=True)
-        return loss
+        return self._eval_step(batch, "test", batch_idx)
 
     @torch.no_grad()
     def predict_step(self, batch, batch_idx: int = 0):

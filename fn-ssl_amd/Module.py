@@ -3,7 +3,8 @@
 
 The signal front end and — as the first "next" row of SURVEY.md §8f — the IPD->DOA back end
 (DPIPD templates :424-519, SourceDetectLocalize 'IDL' :516-577, PredDOA.predgt2DOA :690-727)
-live here; metrics and plotting of the reference's Module.py are out of scope.  The
+and the evaluation (getMetric :106-318, PredDOA.evaluate / forward :686-689, :744-773; one HIP kernel,
+``fnssl.metrics.doa_metrics``) live here; the plotting of the reference's Module.py is out of scope.  The
 fused front end used by ``predict_step`` is ``fnssl.ops.preprocess`` (one STFT
 kernel + one scan + one pack kernel); the classes below exist so code written
 against the reference's per-stage API keeps working, with the same shapes and
@@ -14,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from fnssl import doa as fdoa
+from fnssl import metrics as fmetrics
 from fnssl import ops
 
 
@@ -143,8 +145,66 @@ class SourceDetectLocalize(nn.Module):
         return doas, vads, ss
 
 
+class getMetric(nn.Module):
+    """Localisation metrics on device (reference getMetric, Module.py:106-318): ``forward`` has the reference's signature
+    and returns its dict — 'single': ACC (scalar), MAE [modes]; 'multiple': ACC, MDR, FAR [1], MAE, RMSE [modes] — of
+    device tensors, the MAE / RMSE entries in the reference's order (ele, azi, aziele).  ``last_counts`` keeps the
+    per-utterance integer counts (K_gt, K_est, K_corr) of the last call."""
+
+    _ORDER = ('ele', 'azi', 'aziele')
+
+    def __init__(self, source_mode='multiple', large_number=10000, invalid_source_idx=10, eps=+1e-5):
+        super(getMetric, self).__init__()
+        if source_mode not in ('single', 'multiple'):
+            raise ValueError("source_mode must be 'single' or 'multiple'")
+        if 0 <= int(invalid_source_idx) < fmetrics.MAX_SOURCES:
+            raise ValueError("invalid_source_idx %r would collide with a source index (0..%d)"
+                             % (invalid_source_idx, fmetrics.MAX_SOURCES - 1))
+        self.source_mode = source_mode
+        self.inf = large_number
+        self.invlid_sidx = invalid_source_idx
+        self.eps = eps
+        self.last_counts = None
+
+    def forward(self, doa_gt, vad_gt, doa_est, vad_est, ae_mode, ae_TH=30, useVAD=True, vad_TH=[2 / 3, 2 / 3],
+                metric_unfold=False, radians=False):
+        """doa_gt, doa_est [nb, nt, 2, ns] in degrees (``radians=True``: radians, converted by the kernel as
+        ``PredDOA.evaluate`` does), vad_gt, vad_est [nb, nt, ns]."""
+        fmetrics.ae_mask(ae_mode)                                                # 'Angle error mode unrecognized'
+        modes = [m for m in self._ORDER if m in ae_mode]
+        if self.source_mode == 'multiple' and len(modes) != len(ae_mode):
+            raise RuntimeError("getMetric: ae_mode %r names a mode twice (the reference's assignment fails there)" % (ae_mode,))
+        f = lambda t: None if t is None else t.float()                           # noqa: E731
+        m, k_gt, k_est, k_corr = fmetrics.doa_metrics(f(doa_gt), f(vad_gt), f(doa_est), f(vad_est), self.source_mode, modes,
+                                                      ae_TH, useVAD, vad_TH, radians, self.inf, self.eps)
+        self.last_counts = {'K_gt': k_gt, 'K_est': k_est, 'K_corr': k_corr}
+        def pick(first):                                                          # slices of m: no copy, no host tensor
+            return torch.cat([m[first + fmetrics.AE_SLOT[x]:first + fmetrics.AE_SLOT[x] + 1] for x in modes])
+        metric = {}
+        if self.source_mode == 'single':
+            metric['ACC'] = m[fmetrics.SLOT_ACC]
+            metric['MAE'] = pick(fmetrics.SLOT_MAE)
+        else:
+            metric['ACC'] = m[fmetrics.SLOT_ACC:fmetrics.SLOT_ACC + 1]
+            metric['MDR'] = m[fmetrics.SLOT_MDR:fmetrics.SLOT_MDR + 1]
+            metric['FAR'] = m[fmetrics.SLOT_FAR:fmetrics.SLOT_FAR + 1]
+            metric['MAE'] = pick(fmetrics.SLOT_MAE)
+            metric['RMSE'] = pick(fmetrics.SLOT_RMSE)
+        if metric_unfold:
+            unfolded, key_list = self.unfold_metric(metric)
+            return (unfolded, key_list) if self.source_mode == 'single' else unfolded        # :176-178 / :272-274
+        return metric
+
+    def unfold_metric(self, metric):
+        """dict of tensors -> (flat list of Python floats, keys) (:309-318; this is the one place that reads back)."""
+        metric_unfold = []
+        for m in metric.keys():
+            metric_unfold += metric[m].reshape(-1).tolist()
+        return metric_unfold, [i for i in metric.keys()]
+
+
 class PredDOA(nn.Module):
-    """DP-IPD predictions -> DOA tracks (prediction half of the reference's PredDOA, Module.py:650-727).
+    """DP-IPD predictions -> DOA tracks -> metrics (the reference's PredDOA, Module.py:650-773).
     ``mic_location`` defaults to the reference's hard-coded two-microphone array."""
 
     def __init__(self, method_mode='IDL', source_num_mode='kNum', cuda_activated=True, max_num_sources=1,
@@ -163,6 +223,21 @@ class PredDOA(nn.Module):
                                                    source_num_mode=source_num_mode, meth_mode=method_mode)
         bank, self.doa_candidate = fdoa.template_bank(self.gerdpipd.dpipd_template)
         self.register_buffer("bank", torch.from_numpy(bank), persistent=False)
+        self.getmetric = getMetric(source_mode='single')
+
+    def forward(self, pred_batch, gt_batch):
+        pred_batch, gt_batch = self.predgt2DOA(pred_batch=pred_batch, gt_batch=gt_batch)
+        return self.evaluate(pred=pred_batch, gt=gt_batch)
+
+    def evaluate(self, pred, gt, metric_setting={'ae_mode': ['azi'], 'ae_TH': 5, 'useVAD': True, 'vad_TH': [2 / 3, 2 / 3],
+                                                 'metric_unfold': False}):
+        """pred, gt: dicts with 'doa' [nb, nt, 2, ns] in radians and 'vad_sources' [nb, nt, ns] -> the metric dict
+        (Module.py:744-773); the degrees are formed inside the kernel."""
+        dev = pred['doa'].device
+        return self.getmetric(gt['doa'].to(dev), gt['vad_sources'].to(dev), pred['doa'], pred['vad_sources'],
+                              ae_mode=metric_setting['ae_mode'], ae_TH=metric_setting['ae_TH'],
+                              useVAD=metric_setting['useVAD'], vad_TH=metric_setting['vad_TH'],
+                              metric_unfold=metric_setting['metric_unfold'], radians=True)
 
     def predgt2DOA(self, pred_batch=None, gt_batch=None, time_pool_size=None):
         if pred_batch is not None:

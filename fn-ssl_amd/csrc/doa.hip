@@ -20,9 +20,10 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// pred element (b, p, t, k) at pred[b*sb + p*sp + t*st + k*sk]; bank [ncand, nf2, np]; ss [nb, nt, ncand]; idx [nb, nt, nsrc]; vad [nb, nt, nsrc]
+// pred element (b, p, t, k) of track r = blockIdx.y at pred[r*sr + b*sb + p*sp + t*st + k*sk]; bank [ncand, nf2, np];
+// ss [ntrack, nb, nt, ncand]; idx [ntrack, nb, nt, nsrc]; vad [ntrack, nb, nt, nsrc] (fnssl_ipd2doa: one track, sr = 0)
 __global__ void __launch_bounds__(256)
-ipd2doa_kernel(const float* __restrict__ pred, long long sb, long long sp, long long st, long long sk,
+ipd2doa_kernel(const float* __restrict__ pred, long long sb, long long sp, long long st, long long sk, long long sr,
                const float* __restrict__ bank, int nb, int np, int nt, int nf2,
                int ncand, int nsrc, int unk_num, float* __restrict__ ss, int* __restrict__ idx,
                float* __restrict__ vad) {
@@ -34,6 +35,13 @@ ipd2doa_kernel(const float* __restrict__ pred, long long sb, long long sp, long 
   const int b = blockIdx.x / nt, t = blockIdx.x - b * nt;
   const int X = nf2 * np;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  {
+    const long long seg = (long long)blockIdx.y * nb * nt;      // this track's slice of the outputs
+    pred += (long long)blockIdx.y * sr;
+    ss += seg * ncand;
+    idx += seg * nsrc;
+    vad += seg * nsrc;
+  }
   for (int i = tid; i < X; i += 256) {
     const int k = i / np, p = i - k * np;
     res[i] = pred[b * sb + p * sp + t * st + k * sk];
@@ -116,8 +124,30 @@ int fnssl_ipd2doa(const float* pred, long long sb, long long sp, long long st, l
   FNSSL_REQUIRE(lds <= 60 * 1024, "ipd2doa: 2nf*np = %d does not fit the LDS budget", nf2 * np);
   FNSSL_REQUIRE((long long)nb * nt < (1ll << 31), "ipd2doa: too many segments");
   fnssl::TimedLaunch tl("ipd2doa", fnssl::as_stream(stream));
-  hipLaunchKernelGGL(ipd2doa_kernel, dim3(nb * nt), dim3(256), lds, fnssl::as_stream(stream), pred, sb, sp, st, sk, bank,
+  hipLaunchKernelGGL(ipd2doa_kernel, dim3(nb * nt), dim3(256), lds, fnssl::as_stream(stream), pred, sb, sp, st, sk, 0ll, bank,
                      nb, np, nt, nf2, ncand, nsrc, unk_num, ss, idx, vad);
+  FNSSL_CHECK_LAUNCH("ipd2doa_kernel");
+  return FNSSL_OK;
+}
+
+// All tracks of IPDnet's output in one launch (reference: PredDOA.pred2DOA calling pred2DOA_track once per track,
+// IPDnet/Module.py:463-579).  Checked against the kernel above: pred2DOA_track divides the spectrum by nmic * nf / 2 with
+// the RE-BATCHED sizes (:520-521: nmic = pairs, nf = 2 * bins), which is the kernel's np * nf2 / 2; its 'UnkNum' VAD is
+// ratio = sum(template * pred) / sum(template * template) of the winning template (:556-565), which is the kernel's
+// unk_num output; both flatten (feature, pair) as k * np + p.  So a track is exactly one fnssl_ipd2doa on pred[..., r].
+int fnssl_ipd2doa_tracks(const float* pred, long long sb, long long sp, long long st, long long sk, long long sr,
+                         const float* bank, int nb, int np, int nt, int nf2, int ncand, int nsrc, int ntrack, int unk_num,
+                         float* ss, int* idx, float* vad, void* stream) {
+  FNSSL_REQUIRE(nb > 0 && np > 0 && nt >= 0 && nf2 > 0 && ncand > 0 && nsrc > 0, "ipd2doa_tracks: bad sizes");
+  FNSSL_REQUIRE(ntrack >= 1 && ntrack <= 65535, "ipd2doa_tracks: %d tracks", ntrack);
+  if (nt == 0) return FNSSL_OK;
+  FNSSL_REQUIRE(pred && bank && ss && idx && vad, "ipd2doa_tracks: null pointer");
+  const size_t lds = ((size_t)nf2 * np + ncand) * sizeof(float);
+  FNSSL_REQUIRE(lds <= 60 * 1024, "ipd2doa_tracks: 2nf*np = %d does not fit the LDS budget", nf2 * np);
+  FNSSL_REQUIRE((long long)nb * nt < (1ll << 31), "ipd2doa_tracks: too many segments");
+  fnssl::TimedLaunch tl("ipd2doa_tracks", fnssl::as_stream(stream));
+  hipLaunchKernelGGL(ipd2doa_kernel, dim3(nb * nt, ntrack), dim3(256), lds, fnssl::as_stream(stream), pred, sb, sp, st, sk, sr,
+                     bank, nb, np, nt, nf2, ncand, nsrc, unk_num, ss, idx, vad);
   FNSSL_CHECK_LAUNCH("ipd2doa_kernel");
   return FNSSL_OK;
 }

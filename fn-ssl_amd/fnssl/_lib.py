@@ -62,6 +62,7 @@ SYMBOLS = [
     "fnssl_train_step",
     "fnssl_sn_layernorm", "fnssl_sn_encoder", "fnssl_sn_fconv", "fnssl_sn_full", "fnssl_sn_mamba_workspace_bytes",
     "fnssl_sn_mamba", "fnssl_sn_head", "fnssl_sn_forward_workspace_bytes", "fnssl_sn_state_floats", "fnssl_sn_forward",
+    "fnssl_ipd2doa_tracks", "fnssl_doa_metrics",
 ]
 
 
@@ -220,6 +221,9 @@ def load():
     lib.fnssl_linear.argtypes = [vp, i, i, vp, vp, i, vp, vp]
     lib.fnssl_ipd2doa.argtypes = [vp, ll, ll, ll, ll, vp, i, i, i, i, i, i, i, vp, vp, vp, vp]
     lib.fnssl_doa_peaks.argtypes = [vp, i, i, i, i, vp, vp, vp, vp]
+    lib.fnssl_ipd2doa_tracks.argtypes = [vp, ll, ll, ll, ll, ll, vp, i, i, i, i, i, i, i, i, vp, vp, vp, vp]
+    lib.fnssl_doa_metrics.argtypes = [vp, C.POINTER(ll), vp, C.POINTER(ll), vp, C.POINTER(ll), vp, C.POINTER(ll), i, i, i, i,
+                                      i, i, f, f, f, i, i, f, f, vp, vp, vp, vp, vp, vp]
     lib.fnssl_dpipd_targets.argtypes = [vp, vp, i, i, i, i, vp, i, i, i, i, i, f, f, i, vp, vp, vp]
     lib.fnssl_lstm_packed_floats_bf16.argtypes = [i, i, i]
     lib.fnssl_lstm_packed_floats_bf16.restype = sz

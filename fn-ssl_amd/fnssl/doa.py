@@ -24,14 +24,15 @@ def pair_list(nmic: int, ch_mode: str):
 
 
 def dpipd_templates(mic_location, nele: int = 37, nazi: int = 73, nf: int = 257, fre_max: float = 8000.0,
-                    ch_mode: str = "MM", speed: float = 340.0):
-    """exp(-j 2 pi f tau) for every candidate direction and mic pair (DPIPD.__init__, Module.py:429-463).
+                    ch_mode: str = "MM", speed: float = 340.0, search_space_ele=(0, np.pi), search_space_azi=(-np.pi, np.pi)):
+    """exp(-j 2 pi f tau) for every candidate direction and mic pair (DPIPD.__init__, Module.py:429-463; IPDnet's version
+    searches elevation pi/2 and azimuth [0, pi], IPDnet/Module.py:334-361).
 
     Returns (complex64 [nele, nazi, nf, np], [ele_candidate, azi_candidate]).
     """
     mic = np.asarray(mic_location, dtype=np.float64)
-    ele = np.linspace(0, np.pi, nele)
-    azi = np.linspace(-np.pi, np.pi, nazi)
+    ele = np.linspace(search_space_ele[0], search_space_ele[1], nele)
+    azi = np.linspace(search_space_azi[0], search_space_azi[1], nazi)
     fre = np.linspace(0.0, fre_max, nf)
     unit = np.stack([np.outer(np.sin(ele), np.cos(azi)), np.outer(np.sin(ele), np.sin(azi)),
                      np.tile(np.cos(ele), [nazi, 1]).transpose()], axis=2)

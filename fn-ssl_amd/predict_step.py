@@ -19,12 +19,17 @@ from ``nn.Module`` and ``predict_step`` is called directly (``Predict.py``).
   ``torch.optim.Optimizer`` whose ``step()`` does no arithmetic (the engine has already applied Adam) but which
   Lightning's manual-optimisation loop counts, so ``trainer.global_step`` advances and ``ModelCheckpoint`` /
   ``max_steps`` / logger step indices work, and whose ``state_dict`` carries the engine's Adam moments into checkpoints.
-  The numpy DP-IPD target generator and the DOA metrics stay outside this path
-(SURVEY.md §8): ``gt_batch['ipd']`` must already hold the target IPDs.
+  The numpy DP-IPD target generator stays outside this path: ``gt_batch['ipd']`` must already hold
+  the target IPDs.
+
+``validation_step`` / ``test_step`` (main.py:159-182): ``data_preprocess``, forward, ``cal_loss``, then ``get_metric``
+(``Module.PredDOA``: template search and ACC / MAE on device); they log ``valid/<m>`` / ``test/<m>`` when a trainer is
+attached, keep the metric dict on ``self.last_metrics`` and return the loss.
 """
 import torch
 
 import Model as at_model
+import Module as at_module
 from fnssl import ops
 
 try:  # optional, absent in the build image
@@ -122,6 +127,8 @@ class MyModel(_Base):
         self.nfft = nfft
         self.dev = device
         self.fre_range_used = range(1, int(self.nfft / 2) + 1, 1)
+        self.get_metric = at_module.PredDOA(device=device, ch_mode=ch_mode, mic_location=self.mic_location)   # main.py:131
+        self.last_metrics = None
         self.eval()
 
     def forward(self, x):
@@ -161,6 +168,26 @@ class MyModel(_Base):
             opt = self.optimizers()
             (opt[0] if isinstance(opt, (list, tuple)) else opt).step()
         return {"loss": loss.detach().clone().reshape(())}
+
+    def _eval_step(self, batch, stage):
+        """main.py:159-182: loss and metrics of one batch (waveforms, {'doa', 'vad_sources'})."""
+        in_batch, gt_batch = self.data_preprocess(batch[0], batch[1])
+        with torch.no_grad():
+            pred_batch = self(in_batch)
+            loss = self.cal_loss(pred_batch=pred_batch, gt_batch=gt_batch)
+            metric = self.get_metric(pred_batch=pred_batch, gt_batch=gt_batch)
+        self.last_metrics = metric
+        if hasattr(self, "log") and getattr(self, "_trainer", None) is not None:
+            self.log(stage + "/loss", loss, sync_dist=True)
+            for m in metric:
+                self.log(stage + '/' + m, metric[m] if metric[m].numel() == 1 else metric[m][0], sync_dist=True)
+        return loss
+
+    def validation_step(self, batch, batch_idx: int = 0):
+        return self._eval_step(batch, "valid")
+
+    def test_step(self, batch, batch_idx: int = 0):
+        return self._eval_step(batch, "test")
 
     @ops.on_device
     def cal_loss(self, pred_batch=None, gt_batch=None):

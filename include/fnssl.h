@@ -628,6 +628,44 @@ int fnssl_ipd2doa(const float* pred, long long sb, long long sp, long long st, l
                   int ncand, int nsrc, int unk_num, float* ss, int* idx, float* vad, void* stream);
 
 /*
+ * fnssl_ipd2doa for all `ntrack` tracks of IPDnet's output in ONE launch (reference: PredDOA.pred2DOA -> pred2DOA_track per
+ * track, IPDnet/Module.py:463-579): element (b, p, t, k) of track r at pred[r*sr + b*sb + p*sp + t*st + k*sk] — the
+ * forward's [nb, nt2, 2nf, nmic - 1, ntrack] view read in place.  Outputs are track-major, ss [ntrack, nb, nt, ncand],
+ * idx / vad [ntrack, nb, nt, nsrc], and equal ntrack calls of fnssl_ipd2doa on the views pred[..., r] bit for bit.
+ */
+int fnssl_ipd2doa_tracks(const float* pred, long long sb, long long sp, long long st, long long sk, long long sr,
+                         const float* bank, int nb, int np, int nt, int nf2, int ncand, int nsrc, int ntrack, int unk_num,
+                         float* ss, int* idx, float* vad, void* stream);
+
+/*
+ * DOA evaluation on device: getMetric.forward of both reference versions (FN-SSL/Lightning/Module.py:126-276 and
+ * IPDnet/Module.py:92-237), see csrc/metrics.hip.
+ *   doa_gt [nb, nt, 2, ns_gt], vad_gt [nb, nt, ns_gt], doa_est [nb, nt, 2, ns_est], vad_est [nb, nt, ns_est]: device
+ *   tensors, each read through its own element strides (HOST arrays of 4 / 3 strides); 1..4 sources a side
+ *   ('single': ns_gt = ns_est).  radians != 0: the DOAs are radians and degrees are formed as x * 180 / pi in fp32
+ *   (PredDOA.evaluate); 0: they are degrees already.  use_vad = 0: every entry is active, the VADs may be NULL.
+ *   ae_modes: FNSSL_AE_* bits; the error sums of the other modes are not formed and their slots are 0.
+ *   large_number: the cost of an invalid pair (reference: 10000; > 360).  eps: the MAE / RMSE denominators' + 1e-5.
+ *   metrics [FNSSL_DOA_METRIC_FLOATS] (written): [0] ACC  [1] MDR  [2] FAR  [3..5] MAE (azi, ele, aziele)
+ *     [6..8] RMSE (azi, ele, aziele); 'single' fills ACC and MAE.  0 / 0 is NaN as in torch.
+ *   per_utt [nb, FNSSL_DOA_METRIC_FLOATS] (written; workspace): 'multiple' — the same ratios per utterance
+ *   k_gt, k_est, k_corr [nb] (written): active ground truths, gated estimates, correct assignments per utterance
+ * Two launches on `stream`, no allocation, no synchronisation, no atomics: two runs give the same bits.
+ */
+#define FNSSL_METRIC_SINGLE 0
+#define FNSSL_METRIC_MULTIPLE 1
+#define FNSSL_AE_AZI 1
+#define FNSSL_AE_ELE 2
+#define FNSSL_AE_AZIELE 4
+#define FNSSL_DOA_METRIC_FLOATS 9
+int fnssl_doa_metrics(const float* doa_gt, const long long* doa_gt_strides, const float* vad_gt,
+                      const long long* vad_gt_strides, const float* doa_est, const long long* doa_est_strides,
+                      const float* vad_est, const long long* vad_est_strides, int nb, int nt, int ns_gt, int ns_est,
+                      int mode, int ae_modes, float ae_th, float vad_th_gt, float vad_th_est, int use_vad, int radians,
+                      float large_number, float eps, float* metrics, float* per_utt, int* k_gt, int* k_est, int* k_corr,
+                      void* stream);
+
+/*
  * Replaces the peak search of SourceDetectLocalize.forward, meth_mode 'PD' (FN-SSL/Lightning/Module.py:580-611; the
  * reference: eight shifted copies of the spectrum, then a Python double loop with a sort per frame).
  *   ss     [nframes, nele, nazi]  spatial spectrum (fnssl_ipd2doa's `ss`)
