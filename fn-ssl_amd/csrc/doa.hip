@@ -334,3 +334,114 @@ extern "C" int fnssl_doa_peaks(const float* ss, int nframes, int nele, int nazi,
   FNSSL_CHECK_LAUNCH("doa_peaks_kernel");
   return FNSSL_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// MSE template search of IPDnet2 (reference: PredDOA.pred2DOA_track, IPDnet2/Module.py:573-666): a candidate's score is
+// mean_i (res[i] - bank[c][i])^2 over the 2nf * (nmic - 1) values (:607), the winner the FIRST MINIMUM (torch.argmin, :623),
+// the track's activity that MSE itself (:644-651), and for a further source the whole winning template is subtracted with
+// no projection ratio (:652).  Same shape as ipd2doa_kernel: one workgroup owns one (track, utterance, frame), the
+// residual lives in LDS, each wave scores a share of the candidates with a lane-strided sum + wavefront reduction, wave 0
+// picks the winner.  Every sum runs in a fixed order and nothing is accumulated across workgroups: two runs give the
+// same bits, and a strided pred and its contiguous copy feed the same arithmetic.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+// pred element (b, p, t, k) of track r = blockIdx.y at pred[r*sr + b*sb + p*sp + t*st + k*sk]; bank [ncand, nf2, np];
+// ss [ntrack, nb, nt, ncand]; idx / vad [ntrack, nb, nt, nsrc]
+__global__ void __launch_bounds__(256)
+ipd2doa_mse_kernel(const float* __restrict__ pred, long long sb, long long sp, long long st, long long sk, long long sr,
+                   const float* __restrict__ bank, int nb, int np, int nt, int nf2, int ncand, int nsrc, int unk_num,
+                   float* __restrict__ ss, int* __restrict__ idx, float* __restrict__ vad) {
+  extern __shared__ float smem[];
+  float* res = smem;                 // [nf2 * np] residual IPD vector, index k*np + p (reference flattening)
+  float* score = smem + nf2 * np;    // [ncand]
+  __shared__ int best_s;
+  const int b = blockIdx.x / nt, t = blockIdx.x - b * nt;
+  const int X = nf2 * np;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  {
+    const long long seg = (long long)blockIdx.y * nb * nt;      // this track's slice of the outputs
+    pred += (long long)blockIdx.y * sr;
+    ss += seg * ncand;
+    idx += seg * nsrc;
+    vad += seg * nsrc;
+  }
+  for (int i = tid; i < X; i += 256) {
+    const int k = i / np, p = i - k * np;
+    res[i] = pred[b * sb + p * sp + t * st + k * sk];
+  }
+  __syncthreads();
+  const float count = (float)X;
+  for (int s = 0; s < nsrc; ++s) {
+    for (int c = wave; c < ncand; c += 4) {
+      const float* tp = bank + (long long)c * X;
+      float acc = 0.f;
+      for (int i = lane; i < X; i += 64) {
+        const float d = __fsub_rn(res[i], tp[i]);
+        acc = fmaf(d, d, acc);
+      }
+      acc = wave_sum(acc);
+      if (lane == 0) score[c] = __fdiv_rn(acc, count);
+    }
+    __syncthreads();
+    if (s == 0)
+      for (int c = tid; c < ncand; c += 256) ss[((long long)b * nt + t) * ncand + c] = score[c];
+    if (wave == 0) {
+      // torch.argmin: a NaN counts as the minimum and the first one wins; otherwise the first minimum, +inf included.
+      // Every lane starts from candidate 0 (never from a sentinel), so best_s is in [0, ncand) whatever the scores
+      // hold; lane-strided scan in ascending c, then reduce (NaN first, value asc, index asc).
+      float bv = score[0];
+      int bi = 0;
+      for (int c = lane; c < ncand; c += 64) {
+        const float v = score[c];
+        if (v < bv || (v != v && bv == bv)) {
+          bv = v;
+          bi = c;
+        }
+      }
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) {
+        const float ov = __shfl_xor(bv, d, 64);
+        const int oi = __shfl_xor(bi, d, 64);
+        const bool on = ov != ov, bn = bv != bv;
+        if (on ? (!bn || oi < bi) : (!bn && (ov < bv || (ov == bv && oi < bi)))) {
+          bv = ov;
+          bi = oi;
+        }
+      }
+      if (lane == 0) {
+        best_s = bi;
+        idx[((long long)b * nt + t) * nsrc + s] = bi;
+        vad[((long long)b * nt + t) * nsrc + s] = unk_num ? score[bi] : 1.0f;
+      }
+    }
+    __syncthreads();
+    if (s + 1 < nsrc) {
+      const float* tp = bank + (long long)best_s * X;
+      for (int i = tid; i < X; i += 256) res[i] = __fsub_rn(res[i], tp[i]);
+      __syncthreads();
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int fnssl_ipd2doa_mse_tracks(const float* pred, long long sb, long long sp, long long st, long long sk, long long sr,
+                                        const float* bank, int nb, int np, int nt, int nf2, int ncand, int nsrc, int ntrack,
+                                        int unk_num, float* ss, int* idx, float* vad, void* stream) {
+  FNSSL_REQUIRE(nb > 0 && np > 0 && nt >= 0 && nf2 > 0 && ncand > 0, "ipd2doa_mse_tracks: bad sizes");
+  FNSSL_REQUIRE(nsrc >= 1 && nsrc <= 4, "ipd2doa_mse_tracks: %d sources per track (1..4)", nsrc);
+  FNSSL_REQUIRE(np <= 63, "ipd2doa_mse_tracks: %d microphone pairs (1..63: 2..64 microphones)", np);
+  FNSSL_REQUIRE(ntrack >= 1 && ntrack <= 65535, "ipd2doa_mse_tracks: %d tracks", ntrack);
+  const size_t lds = ((size_t)nf2 * np + ncand) * sizeof(float);
+  FNSSL_REQUIRE(lds <= 60 * 1024, "ipd2doa_mse_tracks: 2nf*np = %lld with %d candidates does not fit the LDS budget",
+                (long long)nf2 * np, ncand);
+  FNSSL_REQUIRE((long long)nb * nt < (1ll << 31), "ipd2doa_mse_tracks: too many segments");
+  if (nt == 0) return FNSSL_OK;
+  FNSSL_REQUIRE(pred && bank && ss && idx && vad, "ipd2doa_mse_tracks: null pointer");
+  fnssl::TimedLaunch tl("ipd2doa_mse_tracks", fnssl::as_stream(stream));
+  hipLaunchKernelGGL(ipd2doa_mse_kernel, dim3(nb * nt, ntrack), dim3(256), lds, fnssl::as_stream(stream), pred, sb, sp, st, sk,
+                     sr, bank, nb, np, nt, nf2, ncand, nsrc, unk_num, ss, idx, vad);
+  FNSSL_CHECK_LAUNCH("ipd2doa_mse_kernel");
+  return FNSSL_OK;
+}

@@ -288,6 +288,70 @@ targets_kernel(const float* __restrict__ doa, const float* __restrict__ vad, con
   }
 }
 
+// IPDnet2's near-field targets (DPIPD2.forward(source_doa, source_distance), IPDnet2/Module.py:443-483, as
+// run_IPDnet2.py:290-328 drives it).  One workgroup per (utterance, frame).  Where the chain rounds, for fp32 DOAs and
+// distances and a float64 microphone table, is where numpy rounds it:
+//   fp32    sin / cos of the DOA (np.sin of a float32 array is float32; here the correctly rounded value), then the source
+//           position x = (d * sin ele) * cos azi, y = (d * sin ele) * sin azi, z = d * cos ele, one fp32 product at a time
+//   double  position - microphone, the norm sqrt((dx^2 + dy^2) + dz^2) with no fused multiply-add, tau_m = (|src - mic_m|
+//           - |src - mic_0|) / speed, the phase (2 pi f_k) tau_m
+//   fp32    cos | sin of the phase, rounded once (.astype(np.float32), run_IPDnet2.py:303)
+__global__ void __launch_bounds__(256)
+targets2_kernel(const float* __restrict__ doa, const float* __restrict__ distance, const float* __restrict__ vad,
+                const double* __restrict__ mic, const float* __restrict__ non_source, int nsrc, int nm1, int bin0, int nf_used,
+                int nbins, float fre_max, float speed, float th, float* __restrict__ ipd) {
+  __shared__ double dist_s[kMaxSrc * (kMaxPairs + 1)];   // [source][microphone]
+  __shared__ double tau_s[kMaxSrc * kMaxPairs];
+  __shared__ int gate_s[kMaxSrc];          // 0: DP-IPD, 1: non-source target, 2: NaN
+  const int bs = blockIdx.x, tid = threadIdx.x, nmic = nm1 + 1;
+  if (tid < nsrc) {
+    int g = 0;
+    if (vad) {
+      const float v = vad[(long long)bs * nsrc + tid];
+      g = v > th ? 0 : (v <= th ? 1 : 2);
+    }
+    gate_s[tid] = g;
+  }
+  for (int i = tid; i < nsrc * nmic; i += 256) {
+    const int s = i / nmic, m = i - s * nmic;
+    const float ele = doa[((long long)bs * 2 + 0) * nsrc + s], azi = doa[((long long)bs * 2 + 1) * nsrc + s];
+    const float d = distance[(long long)bs * nsrc + s];
+    const float se = (float)sin((double)ele), ce = (float)cos((double)ele), sa = (float)sin((double)azi),
+                ca = (float)cos((double)azi);
+    const float dse = __fmul_rn(d, se);
+    const float x = __fmul_rn(dse, ca), y = __fmul_rn(dse, sa), z = __fmul_rn(d, ce);
+    const double dx = __dsub_rn((double)x, mic[m * 3]), dy = __dsub_rn((double)y, mic[m * 3 + 1]),
+                 dz = __dsub_rn((double)z, mic[m * 3 + 2]);
+    dist_s[s * nmic + m] = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
+  }
+  __syncthreads();
+  for (int i = tid; i < nsrc * nm1; i += 256) {
+    const int s = i / nm1, m = i - s * nm1;
+    tau_s[i] = __ddiv_rn(__dsub_rn(dist_s[s * nmic + m + 1], dist_s[s * nmic]), (double)speed);
+  }
+  __syncthreads();
+  const double two_pi = 6.283185307179586476925286766559;
+  const double step = (double)fre_max / (double)(nbins - 1);                    // np.linspace(0, fre_max, nbins)
+  const int per_bin = nm1 * nsrc;
+  float* o = ipd + (long long)bs * 2 * nf_used * per_bin;
+  for (int i = tid; i < nf_used * per_bin; i += 256) {
+    const int k = i / per_bin, r = i - k * per_bin, m = r / nsrc, s = r - m * nsrc;
+    const int g = gate_s[s];
+    float re, im;
+    if (g == 0) {
+      double sn, cs;
+      sincos(__dmul_rn(__dmul_rn(two_pi, __dmul_rn((double)(bin0 + k), step)), tau_s[s * nm1 + m]), &sn, &cs);
+      re = (float)cs, im = (float)sn;
+    } else if (g == 1) {
+      re = non_source[(long long)k * nm1 + m], im = non_source[(long long)(nf_used + k) * nm1 + m];
+    } else {
+      re = im = __builtin_nanf("");
+    }
+    o[i] = re;
+    o[(long long)nf_used * per_bin + i] = im;
+  }
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
@@ -382,6 +446,25 @@ int fnssl_ipdnet_targets(const float* doa, const float* dp_vad, int nb, int nseg
   hipLaunchKernelGGL(targets_kernel, dim3(nb * nseg), dim3(256), 0, st, doa, dp_vad, mic_loc, non_source, nsrc, nmic - 1, bin0,
                      nf_used, nbins, fre_max, speed, vad_th, ipd);
   FNSSL_CHECK_LAUNCH("targets_kernel");
+  return FNSSL_OK;
+}
+
+int fnssl_ipdnet2_targets(const float* doa, const float* distance, const float* vad, int nb, int nseg, int nsrc,
+                          const double* mic_loc, int nmic, const float* non_source, int bin0, int nf_used, int nbins,
+                          float fre_max, float speed, float vad_th, float* ipd, void* stream) {
+  FNSSL_REQUIRE(doa && distance && mic_loc && ipd && (non_source || !vad), "ipdnet2_targets: null pointer");
+  FNSSL_REQUIRE(nb > 0 && nseg > 0 && (long long)nb * nseg <= 0x7fffffffLL, "ipdnet2_targets: nb %d frames %d", nb, nseg);
+  FNSSL_REQUIRE(nsrc >= 1 && nsrc <= kMaxSrc, "ipdnet2_targets: %d sources (1..%d)", nsrc, kMaxSrc);
+  FNSSL_REQUIRE(nmic >= 2 && nmic - 1 <= kMaxPairs, "ipdnet2_targets: %d microphones (2..%d)", nmic, kMaxPairs + 1);
+  FNSSL_REQUIRE(nbins >= 2 && bin0 >= 0 && nf_used >= 1 && bin0 + nf_used <= nbins && fre_max > 0.f && speed > 0.f,
+                "ipdnet2_targets: bins [%d, %d) of %d, fre_max %g, speed %g", bin0, bin0 + nf_used, nbins, (double)fre_max,
+                (double)speed);
+  FNSSL_REQUIRE(vad_th == vad_th, "ipdnet2_targets: the VAD threshold is NaN");
+  hipStream_t st = fnssl::as_stream(stream);
+  fnssl::TimedLaunch tl("ipdnet2_targets", st);
+  hipLaunchKernelGGL(targets2_kernel, dim3(nb * nseg), dim3(256), 0, st, doa, distance, vad, mic_loc, non_source, nsrc, nmic - 1,
+                     bin0, nf_used, nbins, fre_max, speed, vad_th, ipd);
+  FNSSL_CHECK_LAUNCH("targets2_kernel");
   return FNSSL_OK;
 }
 

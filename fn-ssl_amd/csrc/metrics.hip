@@ -160,7 +160,8 @@ __device__ int lsap(const float (*cost)[kMaxSrc], int ng, int ne, int* prow, int
 //   'single'  : slots 3..5 = sum of vad_gt * error (azi, ele, aziele); the counts travel in k_gt / k_corr
 __global__ void __launch_bounds__(64)
 doa_metrics_utt_kernel(View4 dg, View3 vg, View4 de, View3 ve, int nt, int ns_gt, int ns_est, int mode, int ae_modes,
-                       float ae_th, float th_gt, float th_est, int use_vad, int radians, float inf_cost, float eps,
+                       float ae_th, float th_gt, float th_est, int use_vad, int gt_radians, int est_radians, int est_below,
+                       float ratio_eps, float inf_cost, float eps,
                        float* __restrict__ part, int* __restrict__ k_gt, int* __restrict__ k_est, int* __restrict__ k_corr) {
   const int b = blockIdx.x, lane = threadIdx.x;
   int n_gt = 0, n_est = 0, n_corr = 0;
@@ -173,14 +174,19 @@ doa_metrics_utt_kernel(View4 dg, View3 vg, View4 de, View3 ve, int nt, int ns_gt
       g_on[s] = e_on[s] = false;
       g_ele[s] = g_azi[s] = e_ele[s] = e_azi[s] = 0.f;
       if (s < ns_gt) {
-        g_ele[s] = to_deg(dg.p[b * dg.s0 + t * dg.s1 + 0 * dg.s2 + s * dg.s3], radians);
-        g_azi[s] = to_deg(dg.p[b * dg.s0 + t * dg.s1 + 1 * dg.s2 + s * dg.s3], radians);
+        g_ele[s] = to_deg(dg.p[b * dg.s0 + t * dg.s1 + 0 * dg.s2 + s * dg.s3], gt_radians);
+        g_azi[s] = to_deg(dg.p[b * dg.s0 + t * dg.s1 + 1 * dg.s2 + s * dg.s3], gt_radians);
         g_on[s] = use_vad ? vg.p[b * vg.s0 + t * vg.s1 + s * vg.s2] > th_gt : true;
       }
       if (s < ns_est) {
-        e_ele[s] = to_deg(de.p[b * de.s0 + t * de.s1 + 0 * de.s2 + s * de.s3], radians);
-        e_azi[s] = to_deg(de.p[b * de.s0 + t * de.s1 + 1 * de.s2 + s * de.s3], radians);
-        e_on[s] = use_vad ? ve.p[b * ve.s0 + t * ve.s1 + s * ve.s2] > th_est : true;
+        e_ele[s] = to_deg(de.p[b * de.s0 + t * de.s1 + 0 * de.s2 + s * de.s3], est_radians);
+        e_azi[s] = to_deg(de.p[b * de.s0 + t * de.s1 + 1 * de.s2 + s * de.s3], est_radians);
+        if (use_vad) {                                                         // IPDnet2's activity is an MSE: active BELOW
+          const float v = ve.p[b * ve.s0 + t * ve.s1 + s * ve.s2];
+          e_on[s] = est_below ? v < th_est : v > th_est;
+        } else {
+          e_on[s] = true;
+        }
       }
     }
     if (mode == FNSSL_METRIC_SINGLE) {
@@ -269,9 +275,10 @@ doa_metrics_utt_kernel(View4 dg, View3 vg, View4 de, View3 ve, int nt, int ns_gt
     return;
   }
   const float kg = (float)n_gt, kc = (float)n_corr, ke = (float)n_est;
-  o[0] = __fdiv_rn(kc, kg);                                                    // 0 / 0 = NaN, as in torch (:207-209)
-  o[1] = __fdiv_rn(__fsub_rn(kg, kc), kg);
-  o[2] = __fdiv_rn(__fsub_rn(ke, kc), kg);
+  const float dg_ = ratio_eps != 0.f ? __fadd_rn(kg, ratio_eps) : kg;          // IPDnet2: K_gt + 1e-6 (IPDnet2/Module.py:208-210)
+  o[0] = __fdiv_rn(kc, dg_);                                                   // 0 / 0 = NaN, as in torch (:207-209)
+  o[1] = __fdiv_rn(__fsub_rn(kg, kc), dg_);
+  o[2] = __fdiv_rn(__fsub_rn(ke, kc), dg_);
   const float den = __fadd_rn(kc, eps);                                        // + 1e-5 here and nowhere else (:214-221)
   for (int m = 0; m < 3; ++m)
     if (ae_modes & (1 << m)) {
@@ -310,12 +317,13 @@ doa_metrics_batch_kernel(const float* __restrict__ part, const int* __restrict__
 
 }  // namespace
 
-extern "C" int fnssl_doa_metrics(const float* doa_gt, const long long* doa_gt_strides, const float* vad_gt,
-                                 const long long* vad_gt_strides, const float* doa_est, const long long* doa_est_strides,
-                                 const float* vad_est, const long long* vad_est_strides, int nb, int nt, int ns_gt, int ns_est,
-                                 int mode, int ae_modes, float ae_th, float vad_th_gt, float vad_th_est, int use_vad,
-                                 int radians, float large_number, float eps, float* metrics, float* per_utt, int* k_gt,
-                                 int* k_est, int* k_corr, void* stream) {
+extern "C" int fnssl_doa_metrics_ex(const float* doa_gt, const long long* doa_gt_strides, const float* vad_gt,
+                                    const long long* vad_gt_strides, const float* doa_est, const long long* doa_est_strides,
+                                    const float* vad_est, const long long* vad_est_strides, int nb, int nt, int ns_gt,
+                                    int ns_est, int mode, int ae_modes, float ae_th, float vad_th_gt, float vad_th_est,
+                                    int use_vad, int gt_radians, int est_radians, int est_below, float ratio_eps,
+                                    float large_number, float eps, float* metrics, float* per_utt, int* k_gt, int* k_est,
+                                    int* k_corr, void* stream) {
   FNSSL_REQUIRE(mode == FNSSL_METRIC_SINGLE || mode == FNSSL_METRIC_MULTIPLE, "doa_metrics: unknown source mode %d", mode);
   FNSSL_REQUIRE(nb > 0 && nt > 0, "doa_metrics: %d utterances x %d segments", nb, nt);
   FNSSL_REQUIRE(ns_gt >= 1 && ns_gt <= kMaxSrc && ns_est >= 1 && ns_est <= kMaxSrc,
@@ -328,6 +336,7 @@ extern "C" int fnssl_doa_metrics(const float* doa_gt, const long long* doa_gt_st
   FNSSL_REQUIRE(!use_vad || (vad_gt && vad_est && vad_gt_strides && vad_est_strides), "doa_metrics: null pointer (vad)");
   FNSSL_REQUIRE(metrics && per_utt && k_gt && k_est && k_corr, "doa_metrics: null pointer (outputs)");
   FNSSL_REQUIRE(large_number > 360.f, "doa_metrics: large_number %g must exceed every angular error", (double)large_number);
+  FNSSL_REQUIRE(ratio_eps >= 0.f, "doa_metrics: ratio_eps %g must not be negative", (double)ratio_eps);
   const View4 dg{doa_gt, doa_gt_strides[0], doa_gt_strides[1], doa_gt_strides[2], doa_gt_strides[3]};
   const View4 de{doa_est, doa_est_strides[0], doa_est_strides[1], doa_est_strides[2], doa_est_strides[3]};
   View3 vg{nullptr, 0, 0, 0}, ve{nullptr, 0, 0, 0};
@@ -339,11 +348,25 @@ extern "C" int fnssl_doa_metrics(const float* doa_gt, const long long* doa_gt_st
   {
     fnssl::TimedLaunch tl("doa_metrics_utt", s);
     hipLaunchKernelGGL(doa_metrics_utt_kernel, dim3(nb), dim3(64), 0, s, dg, vg, de, ve, nt, ns_gt, ns_est, mode, ae_modes, ae_th,
-                       vad_th_gt, vad_th_est, use_vad, radians, large_number, eps, per_utt, k_gt, k_est, k_corr);
+                       vad_th_gt, vad_th_est, use_vad, gt_radians, est_radians, est_below, ratio_eps, large_number, eps, per_utt, k_gt,
+                       k_est, k_corr);
     FNSSL_CHECK_LAUNCH("doa_metrics_utt_kernel");
   }
   fnssl::TimedLaunch tl("doa_metrics_batch", s);
   hipLaunchKernelGGL(doa_metrics_batch_kernel, dim3(1), dim3(64), 0, s, per_utt, k_gt, k_corr, nb, mode, ae_modes, metrics);
   FNSSL_CHECK_LAUNCH("doa_metrics_batch_kernel");
   return FNSSL_OK;
+}
+
+// The entry point of before the _ex form: estimates active ABOVE their threshold, bare K_gt denominators, one unit for
+// both sides.  Same kernels, same arguments, same bits.
+extern "C" int fnssl_doa_metrics(const float* doa_gt, const long long* doa_gt_strides, const float* vad_gt,
+                                 const long long* vad_gt_strides, const float* doa_est, const long long* doa_est_strides,
+                                 const float* vad_est, const long long* vad_est_strides, int nb, int nt, int ns_gt, int ns_est,
+                                 int mode, int ae_modes, float ae_th, float vad_th_gt, float vad_th_est, int use_vad,
+                                 int radians, float large_number, float eps, float* metrics, float* per_utt, int* k_gt,
+                                 int* k_est, int* k_corr, void* stream) {
+  return fnssl_doa_metrics_ex(doa_gt, doa_gt_strides, vad_gt, vad_gt_strides, doa_est, doa_est_strides, vad_est, vad_est_strides,
+                              nb, nt, ns_gt, ns_est, mode, ae_modes, ae_th, vad_th_gt, vad_th_est, use_vad, radians, radians, 0,
+                              0.f, large_number, eps, metrics, per_utt, k_gt, k_est, k_corr, stream);
 }

@@ -63,6 +63,7 @@ SYMBOLS = [
     "fnssl_sn_layernorm", "fnssl_sn_encoder", "fnssl_sn_fconv", "fnssl_sn_full", "fnssl_sn_mamba_workspace_bytes",
     "fnssl_sn_mamba", "fnssl_sn_head", "fnssl_sn_forward_workspace_bytes", "fnssl_sn_state_floats", "fnssl_sn_forward",
     "fnssl_ipd2doa_tracks", "fnssl_doa_metrics",
+    "fnssl_doa_metrics_ex", "fnssl_ipd2doa_mse_tracks", "fnssl_ipdnet2_targets",
 ]
 
 
@@ -224,6 +225,11 @@ def load():
     lib.fnssl_ipd2doa_tracks.argtypes = [vp, ll, ll, ll, ll, ll, vp, i, i, i, i, i, i, i, i, vp, vp, vp, vp]
     lib.fnssl_doa_metrics.argtypes = [vp, C.POINTER(ll), vp, C.POINTER(ll), vp, C.POINTER(ll), vp, C.POINTER(ll), i, i, i, i,
                                       i, i, f, f, f, i, i, f, f, vp, vp, vp, vp, vp, vp]
+    # fnssl_doa_metrics with `radians` split in two and est_below, ratio_eps after it
+    lib.fnssl_doa_metrics_ex.argtypes = [vp, C.POINTER(ll), vp, C.POINTER(ll), vp, C.POINTER(ll), vp, C.POINTER(ll), i, i, i, i,
+                                         i, i, f, f, f, i, i, i, i, f, f, f, vp, vp, vp, vp, vp, vp]
+    lib.fnssl_ipd2doa_mse_tracks.argtypes = [vp, ll, ll, ll, ll, ll, vp, i, i, i, i, i, i, i, i, vp, vp, vp, vp]
+    lib.fnssl_ipdnet2_targets.argtypes = [vp, vp, vp, i, i, i, vp, i, vp, i, i, i, f, f, f, vp, vp]
     lib.fnssl_dpipd_targets.argtypes = [vp, vp, i, i, i, i, vp, i, i, i, i, i, f, f, i, vp, vp, vp]
     lib.fnssl_lstm_packed_floats_bf16.argtypes = [i, i, i]
     lib.fnssl_lstm_packed_floats_bf16.restype = sz

@@ -6,6 +6,8 @@ IPDnet/runIPDnetOn.py:144-154, 196-290):
     dp_vad(mix_spec, dp_spec)    cal_vad from the spectra ``ops.stft`` writes
     ipdnet_targets(...)          per-source DP-IPD targets, DP-VAD gate, Bessel target in silent slots
     non_source_target(mic_pos)   that Bessel target (host, numpy only), ``non_source_device`` its cached upload
+    ipdnet2_targets(...)         IPDnet2's near-field targets (IPDnet2/run_IPDnet2.py:290-322), gated by the label VAD
+    ipdnet2_geometry(mic, dev)   per geometry, cached: the float64 table, its Bessel target and PredDOA's candidate bank
 
 ROCm tensors only: there is no CPU implementation and no ATen fall-back.
 """
@@ -140,4 +142,76 @@ def ipdnet_targets(doa: torch.Tensor, vad, mic_loc: torch.Tensor, non_source, bi
     _lib.check(_lib.load().fnssl_ipdnet_targets(_ptr(doa), _ptr(vad), nb, nseg, nsrc, _ptr(mic_loc), nmic, _ptr(non_source),
                                                 int(bin0), int(nf_used), int(nbins), float(fre_max), float(speed),
                                                 float(vad_th), _ptr(ipd), _stream()), "ipdnet_targets")
+    return ipd
+
+
+_geometry2_cache = {}
+
+
+def ipdnet2_geometry(mic_pos, device, res_the: int = 1, res_phi: int = 360, nfft: int = 512, fre_max: float = 8000.0,
+                     speed: float = 340.0):
+    """What IPDnet2's evaluation needs of one array, computed once per (geometry, grid, device) and uploaded once:
+
+        mic         float64 [nmic, 3] on ``device`` (the reference keeps the table in float64: ``fnssl_ipdnet2_targets``)
+        non_source  float32 [512, nmic - 1]: euclidean_distances_to_bessel (run_IPDnet2.py:252-264) of that table
+        bank        float32 [res_the, res_phi, 2 * (nfft // 2), nmic - 1]: DPIPD2.__init__'s far-field templates
+                    (IPDnet2/Module.py:416-441; equal to DPIPD's: elevation pi / 2, azimuth linspace(-pi, pi, res_phi),
+                    reference-microphone pairs), [cos | sin] of bins 1 .. nfft / 2 as pred2DOA_track takes them (:585)
+        ele, azi    float32 candidate grids on ``device``
+    """
+    from . import doa as fdoa
+    mic = np.ascontiguousarray(np.asarray(mic_pos, dtype=np.float64).reshape(-1, 3))
+    key = (mic.tobytes(), str(device), int(res_the), int(res_phi), int(nfft), float(fre_max), float(speed))
+    if key not in _geometry2_cache:
+        nf = int(nfft / 2) + 1
+        template, cand = fdoa.dpipd_templates(mic, int(res_the), int(res_phi), nf, fre_max, "M", speed,
+                                              search_space_ele=(np.pi / 2, np.pi / 2), search_space_azi=(-np.pi, np.pi))
+        k = list(range(1, nf))
+        bank = np.ascontiguousarray(np.concatenate((template.real[:, :, k, :], template.imag[:, :, k, :]), axis=2).astype(np.float32))
+        non_source = non_source_target(mic) if nf == 257 and fre_max == 8000.0 and speed == 340.0 else None
+        _geometry2_cache[key] = {
+            "mic": torch.from_numpy(mic).to(device),
+            "non_source": None if non_source is None else torch.from_numpy(non_source).to(device),
+            "bank": torch.from_numpy(bank).to(device),
+            "ele": torch.from_numpy(cand[0].astype(np.float32)).to(device),
+            "azi": torch.from_numpy(cand[1].astype(np.float32)).to(device),
+        }
+    return _geometry2_cache[key]
+
+
+@on_device
+def ipdnet2_targets(doa: torch.Tensor, distance: torch.Tensor, vad, mic_loc: torch.Tensor, non_source, bin0: int = 1,
+                    nf_used: int = 256, nbins: int = 257, fre_max: float = 8000.0, speed: float = 340.0, vad_th: float = 0.0):
+    """doa [nb, nt, 2, nsrc] (elevation, azimuth; radians), distance [nb, nt, nsrc] (metres), vad [nb, nt, nsrc] or None
+    (all active): float32; mic_loc FLOAT64 [nmic, 3] and non_source float32 [2 nf_used, nmic - 1], all on the device
+    -> ipd [nb, nt, 2 nf_used, nmic - 1, nsrc].  ``vad > vad_th`` gives the near-field DP-IPD of DPIPD2.forward, otherwise
+    the ``non_source`` column; a NaN VAD gives NaN."""
+    _need_dev(doa, distance, vad, non_source)
+    if not isinstance(mic_loc, torch.Tensor) or not mic_loc.is_cuda or mic_loc.dtype != torch.float64:
+        raise RuntimeError("fnssl.ipdnet2_targets: mic_loc must be a float64 ROCm tensor (fnssl.ipdnet_step.ipdnet2_geometry)")
+    if doa.ndim != 4 or doa.shape[2] != 2:
+        raise RuntimeError("fnssl.ipdnet2_targets: doa must be [nb, nt, 2, nsource], got %s" % (tuple(doa.shape),))
+    nb, nseg, _, nsrc = doa.shape
+    if not 1 <= nsrc <= MAX_SOURCES:
+        raise RuntimeError("fnssl.ipdnet2_targets: 1..%d sources, got %d" % (MAX_SOURCES, nsrc))
+    if tuple(distance.shape) != (nb, nseg, nsrc):
+        raise RuntimeError("fnssl.ipdnet2_targets: distance %s does not match doa %s" % (tuple(distance.shape), tuple(doa.shape)))
+    if vad is not None and tuple(vad.shape) != (nb, nseg, nsrc):
+        raise RuntimeError("fnssl.ipdnet2_targets: vad %s does not match doa %s" % (tuple(vad.shape), tuple(doa.shape)))
+    if mic_loc.ndim != 2 or mic_loc.shape[1] != 3 or not 2 <= mic_loc.shape[0] <= 64:
+        raise RuntimeError("fnssl.ipdnet2_targets: mic_loc must be [nmic, 3] with 2..64 microphones, got %s" % (tuple(mic_loc.shape),))
+    nmic = mic_loc.shape[0]
+    if vad is not None and non_source is None:
+        raise RuntimeError("fnssl.ipdnet2_targets: a VAD needs the non_source target of the silent slots")
+    if non_source is not None and tuple(non_source.shape) != (2 * nf_used, nmic - 1):
+        raise RuntimeError("fnssl.ipdnet2_targets: non_source %s is not [%d, %d]" % (tuple(non_source.shape), 2 * nf_used, nmic - 1))
+    doa, distance, mic_loc = doa.contiguous(), distance.contiguous(), mic_loc.contiguous()
+    vad = None if vad is None else vad.contiguous()
+    non_source = None if non_source is None else non_source.contiguous()
+    ipd = torch.empty((nb, nseg, 2 * nf_used, nmic - 1, nsrc), dtype=torch.float32, device=doa.device)
+    if ipd.numel() == 0:
+        return ipd
+    _lib.check(_lib.load().fnssl_ipdnet2_targets(_ptr(doa), _ptr(distance), _ptr(vad), nb, nseg, nsrc, _ptr(mic_loc), nmic,
+                                                 _ptr(non_source), int(bin0), int(nf_used), int(nbins), float(fre_max),
+                                                 float(speed), float(vad_th), _ptr(ipd), _stream()), "ipdnet2_targets")
     return ipd

@@ -665,6 +665,62 @@ int fnssl_doa_metrics(const float* doa_gt, const long long* doa_gt_strides, cons
                       float large_number, float eps, float* metrics, float* per_utt, int* k_gt, int* k_est, int* k_corr,
                       void* stream);
 
+/* ---- IPDnet2 evaluation (IPDnet2/Module.py:443-483, 573-706; IPDnet2/run_IPDnet2.py:173-222, 266-328) -------------------
+ * The three entry points below were added without changing any existing declaration or behaviour, so FNSSL_ABI_VERSION
+ * stays 19: a caller built against the earlier header keeps working, and a caller that needs these checks for the symbols. */
+
+/*
+ * fnssl_doa_metrics with the three things IPDnet2's getMetric does differently (IPDnet2/Module.py:67-278):
+ *   est_below            1: an estimate is active when vad_est < vad_th_est (its activity is an MSE, :167); 0: when >
+ *   ratio_eps            added in fp32 to the K_gt denominators of ACC / MDR / FAR (:208-210 use 1e-6, so an utterance
+ *                        with no active ground truth gives 0); 0 leaves 0 / 0 = NaN.  Must not be negative.
+ *   gt_radians, est_radians   the unit of each side separately (IPDnet2's ground truth arrives in degrees, its estimates
+ *                        in radians, :675-678)
+ * fnssl_doa_metrics(..., radians, ...) is fnssl_doa_metrics_ex(..., radians, radians, 0, 0.f, ...).
+ */
+int fnssl_doa_metrics_ex(const float* doa_gt, const long long* doa_gt_strides, const float* vad_gt,
+                         const long long* vad_gt_strides, const float* doa_est, const long long* doa_est_strides,
+                         const float* vad_est, const long long* vad_est_strides, int nb, int nt, int ns_gt, int ns_est,
+                         int mode, int ae_modes, float ae_th, float vad_th_gt, float vad_th_est, int use_vad, int gt_radians,
+                         int est_radians, int est_below, float ratio_eps, float large_number, float eps, float* metrics,
+                         float* per_utt, int* k_gt, int* k_est, int* k_corr, void* stream);
+
+/*
+ * The MSE template search of IPDnet2's PredDOA.pred2DOA_track (IPDnet2/Module.py:573-666) for all `ntrack` tracks in one
+ * launch.  pred and bank are addressed as in fnssl_ipd2doa_tracks (pred read in place through sb, sp, st, sk, sr; bank
+ * [ncand, nf2, np]); outputs are track-major.  Per (track, utterance, frame), for source s = 0 .. nsrc - 1:
+ *   ss  [ntrack, nb, nt, ncand]  ss[c] = sum_i (res[i] - bank[c][i])^2 / (nf2 * np), of the first source (:607)
+ *   idx [ntrack, nb, nt, nsrc]   the FIRST MINIMUM of the scores, with torch.argmin's rule (:623): a NaN counts as the
+ *                                minimum and the first NaN wins; always in [0, ncand)
+ *   vad [ntrack, nb, nt, nsrc]   the winner's MSE (unk_num = 1, 'UnkNum', :644-651) or 1 ('KNum')
+ *   then res -= bank[idx], the whole template with no projection ratio (:652)
+ * Bounds: nsrc 1..4, np 1..63, ntrack 1..65535, and the residual and the scores live in LDS:
+ * (nf2 * np + ncand) * 4 bytes <= 60 KiB (config 5: 2048 + 360 floats = 9.4 KiB); a larger problem is FNSSL_E_INVALID.
+ * One launch, no atomics, every sum in a fixed order: two runs give the same bits.
+ */
+int fnssl_ipd2doa_mse_tracks(const float* pred, long long sb, long long sp, long long st, long long sk, long long sr,
+                             const float* bank, int nb, int np, int nt, int nf2, int ncand, int nsrc, int ntrack, int unk_num,
+                             float* ss, int* idx, float* vad, void* stream);
+
+/*
+ * The ground-truth half of IPDnet2's data_preprocess (IPDnet2/run_IPDnet2.py:290-322): fnssl_ipdnet_targets with the
+ * near-field delay of DPIPD2.forward(source_doa, source_distance) (IPDnet2/Module.py:443-483), reference-microphone pairs.
+ *   doa [nb, nseg, 2, nsrc] (elevation, azimuth; radians);  distance [nb, nseg, nsrc] in metres;
+ *   vad [nb, nseg, nsrc] or NULL (all active);  mic_loc DEVICE [nmic, 3] DOUBLE (the reference's table is float64);
+ *   non_source DEVICE [2 nf_used, nmic - 1]
+ *   ipd [nb, nseg, 2 nf_used, nmic - 1, nsrc]:
+ *     v >  vad_th  [cos | sin](2 pi f_k tau_m), tau_m = (|src - mic_m| - |src - mic_0|) / speed, src = distance * r(doa)
+ *     v <= vad_th  non_source[:, m]          v NaN: NaN          (the drop-in passes vad_th = 0 and the label VAD)
+ *   Rounding follows numpy on fp32 inputs: sin / cos of the DOA and the three products that form src are fp32 (the
+ *   reference hands np.sin / np.cos float32 arrays); the differences against the float64 table, the norms, tau and the
+ *   phase are double; cos | sin are rounded to fp32 once.  The kernel's fp32 sin / cos are the correctly rounded values;
+ *   numpy's float32 loops may differ from them in the last bit.
+ *   nsrc 1..4, nmic 2..64.
+ */
+int fnssl_ipdnet2_targets(const float* doa, const float* distance, const float* vad, int nb, int nseg, int nsrc,
+                          const double* mic_loc, int nmic, const float* non_source, int bin0, int nf_used, int nbins,
+                          float fre_max, float speed, float vad_th, float* ipd, void* stream);
+
 /*
  * Replaces the peak search of SourceDetectLocalize.forward, meth_mode 'PD' (FN-SSL/Lightning/Module.py:580-611; the
  * reference: eight shifted copies of the spectrum, then a Python double loop with a sort per frame).
