@@ -31,18 +31,18 @@
 using namespace fnssl_lstm;
 
 namespace fnssl_lstm {
-extern template int launch_h<16>(int, const LstmParams&, int, int, hipStream_t);
-extern template int launch_h<32>(int, const LstmParams&, int, int, hipStream_t);
-extern template int launch_h<64>(int, const LstmParams&, int, int, hipStream_t);
-extern template int launch_h<128>(int, const LstmParams&, int, int, hipStream_t);
-extern template int launch_h<256>(int, const LstmParams&, int, int, hipStream_t);
-extern template int launch_split_h<128>(int, const LstmParams&, int, int, hipStream_t);
-extern template int launch_split_h<256>(int, const LstmParams&, int, int, hipStream_t);
-int forward_save(LstmParams p, int H, int mode, hipStream_t st);   // lstm_train.hip
-int forward_bf16(LstmParams p, int H, hipStream_t st);             // lstm_bf16.hip
+extern template int launch_h<16>(int, const LstmParams&, int, int, const LaunchCtx&);
+extern template int launch_h<32>(int, const LstmParams&, int, int, const LaunchCtx&);
+extern template int launch_h<64>(int, const LstmParams&, int, int, const LaunchCtx&);
+extern template int launch_h<128>(int, const LstmParams&, int, int, const LaunchCtx&);
+extern template int launch_h<256>(int, const LstmParams&, int, int, const LaunchCtx&);
+extern template int launch_split_h<128>(int, const LstmParams&, int, int, const LaunchCtx&);
+extern template int launch_split_h<256>(int, const LstmParams&, int, int, const LaunchCtx&);
+int forward_save(LstmParams p, int H, int mode, const LaunchCtx& lc);   // lstm_train.hip
+int forward_bf16(LstmParams p, int H, const LaunchCtx& lc);             // lstm_bf16.hip
 bool f32c_handles(const LstmParams& p, int H, int mode);           // lstm_f32c.hip
 // FNSSL_OK, kNoCluster (not co-resident: caller takes the rounds) or an error; cluster_bytes = the size of p.cluster_ws
-int forward_f32c(LstmParams p, int H, int mode, size_t cluster_bytes, hipStream_t st);
+int forward_f32c(LstmParams p, int H, int mode, size_t cluster_bytes, const LaunchCtx& lc);
 }  // namespace fnssl_lstm
 
 // ---- launch planner (host) -------------------------------------------------------------------------------------
@@ -91,6 +91,26 @@ static int plan_lstm_rounds(int H, int tasks, int ndir, int ncu, std::vector<int
   }
   return FNSSL_OK;
 }
+
+namespace {
+// standard stream [slice][quad][4 records] -> N-interleaved [slice N-tuple][quad][slice in tuple][4 records]: the pair-
+// interleaved copy of lstm_static3.h (N = 2), the quad-interleaved one of lstm_static4.h (N = 4); one thread per float4
+template <int N>
+__global__ void __launch_bounds__(256) interleave_stream_kernel(const float4* __restrict__ in, int qps, long long n4,
+                                                                float4* __restrict__ out) {
+  static_assert(N == 2 || N == 4, "pairs or quads of slices");
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const int l = (int)(i & 63);                      // float4 inside the 1-KiB record
+  const long long rec = i >> 6;                      // output record index = ((p * qps + q) * N + j) * 4 + r
+  const int r = (int)(rec & 3), j = (int)((rec >> 2) & (N - 1));
+  const long long pq = rec >> (N == 2 ? 3 : 4);
+  const int q = (int)(pq % qps);
+  const long long pp = pq / qps;
+  const long long src = (((N * pp + j) * qps + q) * 4 + r) * 64 + l;
+  out[i] = in[src];
+}
+}  // namespace
 
 extern "C" {
 
@@ -223,37 +243,6 @@ size_t fnssl_lstm_workspace_bytes(int nseq, int hidden, int ndir) {   // suffici
 }
 
 namespace {
-// standard stream [slice][quad][4 records] -> pair-interleaved [slice pair][quad][slice in pair][4 records]; one thread
-// per float4 of the stream
-__global__ void __launch_bounds__(256) pair_stream_kernel(const float4* __restrict__ in, int qps, long long n4,
-                                                          float4* __restrict__ out) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  const int l = (int)(i & 63);                      // float4 inside the 1-KiB record
-  const long long rec = i >> 6;                      // output record index = ((p * qps + q) * 2 + j) * 4 + r
-  const int r = (int)(rec & 3), j = (int)((rec >> 2) & 1);
-  const long long pq = rec >> 3;
-  const int q = (int)(pq % qps);
-  const long long pp = pq / qps;
-  const long long src = (((2 * pp + j) * qps + q) * 4 + r) * 64 + l;
-  out[i] = in[src];
-}
-
-// standard stream [slice][quad][4 records] -> quad-interleaved [slice quad][quad][slice in quad][4 records] (lstm_static4.h)
-__global__ void __launch_bounds__(256) quad_stream_kernel(const float4* __restrict__ in, int qps, long long n4,
-                                                          float4* __restrict__ out) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  const int l = (int)(i & 63);                      // float4 inside the 1-KiB record
-  const long long rec = i >> 6;                      // output record index = ((p * qps + q) * 4 + j) * 4 + r
-  const int r = (int)(rec & 3), j = (int)((rec >> 2) & 3);
-  const long long pq = rec >> 4;
-  const int q = (int)(pq % qps);
-  const long long pp = pq / qps;
-  const long long src = (((4 * pp + j) * qps + q) * 4 + r) * 64 + l;
-  out[i] = in[src];
-}
-
 // guarded fallback of a streaming (carry) call, first step: put back the cell state the aborted cluster kernel has advanced.
 // Returns at once unless the cluster kernel left a non-zero status word.
 __global__ void __launch_bounds__(256) restore_cell_kernel(const unsigned* __restrict__ guard, const float4* __restrict__ backup,
@@ -279,11 +268,8 @@ int fnssl_lstm_cluster_status(const void* workspace, size_t workspace_bytes, int
 
 }  // extern "C"
 
-// dry = true (fnssl_lstm_plan): every decision of the real call is taken, nothing is enqueued; *family / *rounds report
-// the kernel family and its number of launches
-static int lstm_forward_impl(const fnssl_lstm_desc* d, void* stream, bool dry, int* family, int* rounds) {
-  FNSSL_REQUIRE(d, "lstm_forward: null descriptor");
-  fnssl::TuningScope tuning_of_this_call(d->tuning);
+// ---- fnssl_lstm_forward / fnssl_lstm_plan, step by step ---------------------------------------------------------------
+static int check_fwd_desc(const fnssl_lstm_desc* d, bool dry, size_t ws_bytes) {
   const int H = d->hidden;
   FNSSL_REQUIRE(H == 16 || H == 32 || H == 64 || H == 128 || H == 256,
                 "lstm_forward: hidden size %d unsupported (16/32/64/128/256)", H);
@@ -303,42 +289,29 @@ static int lstm_forward_impl(const fnssl_lstm_desc* d, void* stream, bool dry, i
     for (const void* o : outs)
       for (const void* i : ins) FNSSL_REQUIRE(!o || o != i, "lstm_forward: an input tensor aliases an output tensor");
   }
-  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  FNSSL_REQUIRE(aligned(d->src0.p) && aligned(d->src1.p) && aligned(d->src2.p) && aligned(d->out) &&
-                    aligned(d->wpack[0]) && aligned(d->wpack[1]) && aligned(d->workspace) && aligned(d->skip.p) &&
-                    aligned(d->out_sum),
+  FNSSL_REQUIRE(aligned16(d->src0.p, d->src1.p, d->src2.p, d->out, d->wpack[0], d->wpack[1], d->workspace, d->skip.p, d->out_sum),
                 "lstm_forward: pointers must be 16-byte aligned");
-  auto mult4 = [](long long v) { return (v & 3) == 0; };
-  FNSSL_REQUIRE(mult4(d->src0.so) && mult4(d->src0.si) && mult4(d->src0.st) && mult4(d->out_so) &&
-                    mult4(d->out_si) && mult4(d->out_st) &&
-                    (!d->src1.p || (mult4(d->src1.so) && mult4(d->src1.si) && mult4(d->src1.st))) &&
-                    (!d->src2.p || (mult4(d->src2.so) && mult4(d->src2.si) && mult4(d->src2.st))),
+  FNSSL_REQUIRE(mult4(d->src0) && mult4(d->out_so, d->out_si, d->out_st) && (!d->src1.p || mult4(d->src1)) &&
+                    (!d->src2.p || mult4(d->src2)),
                 "lstm_forward: strides must be multiples of 4 floats");
-  // buffer addressing: per-wave lane spread + step walk + one row must fit 32 bits
-  auto extent_ok = [&](long long so, long long si, long long st, long long width) {
-    auto ab = [](long long v) { return v < 0 ? -v : v; };
-    const long double e = ((long double)ab(so) + 16.0L * ab(si) + (long double)d->nsteps * ab(st) + width) * 4.0L;
-    return so >= 0 && si >= 0 && st >= 0 && e < 4.0e9L;
-  };
-  FNSSL_REQUIRE(extent_ok(d->src0.so, d->src0.si, d->src0.st, d->c0) &&
-                    (!d->src1.p || extent_ok(d->src1.so, d->src1.si, d->src1.st, d->c0)) &&
-                    (!d->src2.p || extent_ok(d->src2.so, d->src2.si, d->src2.st, d->c2)) &&
-                    (!d->out_sum || (extent_ok(d->skip.so, d->skip.si, d->skip.st, 2 * H) && mult4(d->skip.so) &&
-                                     mult4(d->skip.si) && mult4(d->skip.st))) &&
-                    extent_ok(d->out_so, d->out_si, d->out_st, 2 * H),
+  FNSSL_REQUIRE(extent_ok(d->src0, d->c0, d->nsteps) && (!d->src1.p || extent_ok(d->src1, d->c0, d->nsteps)) &&
+                    (!d->src2.p || extent_ok(d->src2, d->c2, d->nsteps)) &&
+                    (!d->out_sum || (extent_ok(d->skip, 2 * H, d->nsteps) && mult4(d->skip))) &&
+                    extent_ok(d->out_so, d->out_si, d->out_st, 2 * H, d->nsteps),
                 "lstm_forward: strides must be non-negative and one sequence group must span < 4 GB");
-  const LstmWsLayout ws = lstm_ws_layout(d->nseq, H, d->ndir, d->precision);
-  if (!d->workspace || d->workspace_bytes < ws.total) {
-    fnssl::set_error("lstm_forward: workspace %zu < %zu bytes", d->workspace_bytes, ws.total);
-    return FNSSL_E_WORKSPACE;
-  }
+  if (const int rc = check_workspace("lstm_forward", d->workspace, d->workspace_bytes, ws_bytes)) return rc;
+  FNSSL_REQUIRE(!d->carry_state || (d->ndir == 1 && !d->reserve),
+                "lstm_forward: carry_state needs a uni-directional layer (and is not a training mode)");
+  return FNSSL_OK;
+}
+
+// the kernel parameters every family starts from (chq / pad and the launch's range: set per launch)
+static LstmParams fwd_params(const fnssl_lstm_desc* d, const LstmWsLayout& ws) {
   LstmParams p;
   p.src0 = View{d->src0.p, d->src0.so, d->src0.si, d->src0.st};
   p.src1 = View{d->src1.p, d->src1.so, d->src1.si, d->src1.st};
   p.src2 = View{d->src2.p, d->src2.so, d->src2.si, d->src2.st};
   p.skip = View{d->skip.p, d->skip.so, d->skip.si, d->skip.st};
-  FNSSL_REQUIRE(!d->carry_state || (d->ndir == 1 && !d->reserve),
-                "lstm_forward: carry_state needs a uni-directional layer (and is not a training mode)");
   p.carry = d->carry_state ? 1 : 0;
   // streaming: the kernel addresses the output one row down so that "step -1" is the caller's h_{-1} row
   p.out = d->carry_state ? d->out - d->out_st : d->out;
@@ -358,223 +331,177 @@ static int lstm_forward_impl(const fnssl_lstm_desc* d, void* stream, bool dry, i
   p.q_inner = d->q_inner;
   p.nsteps = d->nsteps;
   p.ndir = d->ndir;
-  p.quads_per_slice = quads_per_slice(d->c0, d->c2, H);
+  p.quads_per_slice = quads_per_slice(d->c0, d->c2, d->hidden);
 #ifdef FNSSL_BUILD_ABLATE
   p.ablate = env_int("FNSSL_ABLATE", 1, 255);   // timing experiments: twin kernels that skip work (wrong results)
 #else
   p.ablate = 0;                                 // the shipping library contains no ablation twins (make ABLATE=1)
 #endif
-  p.dry = dry ? 1 : 0;
   p.fallback_count = d->fallback_count;
+  return p;
+}
+
+// One fp32 call: what its steps share, and the steps.  family / rounds: where fnssl_lstm_plan wants its answers — both null
+// in a real call, and nulled for the guarded fallback of a cluster kernel, whose family is the one reported.
+struct Fp32Call {
+  const fnssl_lstm_desc* d;
+  const LstmWsLayout& ws;
+  const LaunchCtx& lc;
+  LstmParams p;
+  int H, mode;
+  int* family;
+  int* rounds;
   int nlaunch = 0;
-  bool guarded = false;   // true: what follows is the guarded fallback of a cluster kernel (family already reported)
-  auto report = [&](int f) {
-    if (family && !guarded) *family = f;
-  };
-  const int tasks = (d->nseq + 15) / 16;
-  const int mode = ((d->src1.p != nullptr && d->c0 > 0) ? kHas1 : 0) | (d->c2 > 0 ? kHas2 : 0) |
-                   (d->out_sum ? kSum : 0);
-
-  const double flops = 2.0 * 4 * H * (double)(d->c0 + d->c2 + H) * d->nseq * (double)d->nsteps * d->ndir;
-  static const char* names[5] = {"lstm_h16", "lstm_h32", "lstm_h64", "lstm_h128", "lstm_h256"};
-  const int hi = H == 16 ? 0 : H == 32 ? 1 : H == 64 ? 2 : H == 128 ? 3 : 4;
-  hipStream_t st = fnssl::as_stream(stream);
-  fnssl::TimedLaunch tl(dry ? nullptr : names[hi], st, flops);
-
-  if (d->precision == FNSSL_PRECISION_BF16) {   // bf16 MFMA operands (weights packed by fnssl_lstm_pack_bf16)
-    FNSSL_REQUIRE(!(mode & (kHas1 | kSum)) && !d->reserve && !d->carry_state && d->c0 % 16 == 0 && d->c2 % 16 == 0,
-                  "lstm_forward: the bf16 path takes one summed and one concatenated input of 16-channel blocks, "
-                  "no fused residual / reserve / carry");
-    p.quads_per_slice = bf16_quads_per_slice(d->c0, d->c2, H);
-    p.chq = 0;
-    p.pad = 0;
-    report(FNSSL_LSTM_FAMILY_BF16);
-    return forward_bf16(p, H, st);
+  void report(int f) {
+    if (family) *family = f;
   }
-  if (d->precision == FNSSL_PRECISION_BF16W) {   // wide bf16 kernels: 32 sequences per wave, bf16 / fp32 activation tensors
-    FNSSL_REQUIRE(!(mode & (kHas1 | kSum)) && !d->reserve && !d->carry_state && d->c0 % 16 == 0 && d->c2 % 16 == 0,
-                  "lstm_forward: the wide bf16 path takes 16-channel input blocks, no fused residual / reserve / carry");
-    auto mult8 = [](long long v) { return (v & 7) == 0; };
-    const int fm = d->f32_mask & 7;
-    FNSSL_REQUIRE(((fm & 1) || !d->c0 || (mult8(d->src0.so) && mult8(d->src0.si) && mult8(d->src0.st))) &&
-                      ((fm & 2) || !d->c2 || (mult8(d->src2.so) && mult8(d->src2.si) && mult8(d->src2.st))) &&
-                      ((fm & 4) || (mult8(d->out_so) && mult8(d->out_si) && mult8(d->out_st))),
-                  "lstm_forward: strides of bf16 tensors must be multiples of 8 elements");
-    return forward_bf16w(p, H, fm, ws.cluster.bytes, st, family);
+  int done(int rc) {   // the rounds of this call are all enqueued
+    if (rounds) *rounds = nlaunch;
+    return rc;
   }
-  FNSSL_REQUIRE(d->precision == FNSSL_PRECISION_FP32, "lstm_forward: unknown precision %d", d->precision);
-  if (d->reserve) {   // training forward: also save the gate activations (lstm_train.hip)
-    FNSSL_REQUIRE((H == 128 || H == 256) && !(mode & (kHas1 | kSum)),
-                  "lstm_forward: the reserve-saving forward needs hidden 128/256 and no src1 / out_sum");
-    FNSSL_REQUIRE(d->reserve_bytes >= fnssl_lstm_reserve_bytes(d->nseq, H, d->ndir, d->nsteps) &&
-                      (reinterpret_cast<uintptr_t>(d->reserve) & 15) == 0 &&
-                      (long double)d->nsteps * (H / 16) * kReserveRecs * 1024 < 4.0e9L,
-                  "lstm_forward: reserve buffer too small or misaligned");
-    p.chq = 0;
-    p.pad = 0;
-    p.task0 = 0;
-    p.task1 = tasks;
-    p.wgs_per_dir = 0;
-    // the full-band layers of a large enough shard: the cluster-resident kernel with the reserve stores (lstm_f32c.h), its
-    // guarded fallback = the split kernels below
-    if (d->variant == 0 && f32c_handles(p, H, mode)) {
-      const int rc = forward_f32c(p, H, mode, ws.cluster.bytes, st);
-      if (rc == FNSSL_OK) {
-        report(FNSSL_LSTM_FAMILY_F32_CLUSTER);
-        if (dry) return FNSSL_OK;
-        guarded = true;
-        p.guard = reinterpret_cast<const unsigned*>(p.cluster_ws);
-      } else if (rc != kNoCluster) {
-        return rc;
-      }
+  int train();
+  int inference();
+  int planned_rounds();
+  int launch_round(int variant, int t0, int t1);
+  int launch_round_interleaved_h256(int NW, int nwg);
+  int launch_split(int split, bool static_only);
+};
+
+// training forward: also save the gate activations (lstm_train.hip)
+int Fp32Call::train() {
+  FNSSL_REQUIRE((H == 128 || H == 256) && !(mode & (kHas1 | kSum)),
+                "lstm_forward: the reserve-saving forward needs hidden 128/256 and no src1 / out_sum");
+  FNSSL_REQUIRE(d->reserve_bytes >= fnssl_lstm_reserve_bytes(d->nseq, H, d->ndir, d->nsteps) && aligned16(d->reserve) &&
+                    (long double)d->nsteps * (H / 16) * kReserveRecs * 1024 < 4.0e9L,
+                "lstm_forward: reserve buffer too small or misaligned");
+  p.chq = 0;
+  p.pad = 0;
+  p.task0 = 0;
+  p.task1 = p.ntasks;
+  p.wgs_per_dir = 0;
+  // the full-band layers of a large enough shard: the cluster-resident kernel with the reserve stores (lstm_f32c.h), its
+  // guarded fallback = the split kernels
+  return cluster_then_fallback(
+      lc, d->variant == 0 && f32c_handles(p, H, mode), FNSSL_LSTM_FAMILY_F32_CLUSTER, family, p.cluster_ws,
+      [&] { return forward_f32c(p, H, mode, ws.cluster.bytes, lc); },
+      [&](const unsigned* guard) {
+        p.guard = guard;
+        if (!guard) report(FNSSL_LSTM_FAMILY_TRAIN);
+        return lc.dry ? FNSSL_OK : forward_save(p, H, mode, lc);
+      });
+}
+
+// H = 256, the full-chip narrow-band rounds: the operand-ring kernel (lstm_static3.h: two hidden slices per pass, x_t and h_{t-1}
+// streamed, no register spills; block 1's 260-channel layer included) on a pair-interleaved copy of the stream (re-
+// ordered into the workspace first: 2 MB per direction, one tiny launch).  NO_STATIC3 keeps the one-slice kernel: A/B.
+// (Round 3's two-slice kernel with h_{t-1} in registers, lstm_static2.h, was removed in round 5: superseded.)
+// kNoStatic: not one of their shapes.
+int Fp32Call::launch_round_interleaved_h256(int NW, int nwg) {
+  const bool s3 = !p.ablate && !fnssl::tune(FNSSL_TUNE_NO_STATIC3) && (mode == kSum || mode == 0 || mode == (kHas2 | kSum)) &&
+                  ((d->c2 == 0 && !(mode & kHas2)) || (d->c2 == 4 && (mode & kHas2)));
+  if (!(NW == 12 && d->c0 == 256 && !p.carry && s3)) return kNoStatic;
+  LstmParams p2 = p;
+  const long long n4 = (long long)(256 / 16) * p.quads_per_slice * 4 * 64;      // float4 per direction
+  char* dst = reinterpret_cast<char*>(d->workspace) + ws.stream.off;
+  FNSSL_REQUIRE((size_t)d->ndir * n4 * 16 <= ws.stream.bytes, "lstm_forward: no room for the interleaved weight stream");
+  // round 6: four slices per pass on a QUAD-interleaved copy (lstm_static4.h: half the operand re-reads, the weight ring
+  // staged by LDS-DMA); NO_STATIC4 keeps the two-slice kernel: A/B, same bits
+  const bool s4 = !fnssl::tune(FNSSL_TUNE_NO_STATIC4);
+  const auto interleave = s4 ? Kernel{interleave_stream_kernel<4>, 256, 0, "interleave_stream_kernel"}
+                             : Kernel{interleave_stream_kernel<2>, 256, 0, "interleave_stream_kernel"};
+  for (int di = 0; di < d->ndir; ++di) {
+    float4* o = reinterpret_cast<float4*>(dst + (size_t)di * n4 * 16);
+    if (const int rc = enqueue(lc, interleave, (int)((n4 + 255) / 256), reinterpret_cast<const float4*>(p.wpack[di]), p.quads_per_slice, n4, o))
+      return rc;
+    p2.wpack[di] = reinterpret_cast<const float*>(o);
+  }
+  const int rc = s4 ? launch_static4_h256(p2, mode, nwg, lc) : launch_static3_h256(p2, mode, nwg, lc);
+  if (rc != kNoStatic) report(s4 ? FNSSL_LSTM_FAMILY_STATIC4 : FNSSL_LSTM_FAMILY_STATIC3);
+  return rc;
+}
+
+// one launch of kVariants[variant].NW waves per workgroup over the 16-sequence groups [t0, t1) of every direction
+int Fp32Call::launch_round(int variant, int t0, int t1) {
+  const Variant& vr = kVariants[variant];
+  p.task0 = t0;
+  p.task1 = t1;
+  p.wgs_per_dir = (t1 - t0 + vr.NW - 1) / vr.NW;
+  const int nwg = p.wgs_per_dir * d->ndir;
+  ++nlaunch;
+  if (d->variant == 0 && !fnssl::tune(FNSSL_TUNE_LSTM_NO_STATIC)) {
+    int rc = kNoStatic;
+    if (H == 128) rc = launch_static_h128(p, mode, vr.NW, nwg, lc);
+    if (H == 256) {
+      rc = launch_round_interleaved_h256(vr.NW, nwg);
+      if (rc != kNoStatic) return rc;
+      rc = launch_static_h256(p, mode, vr.NW, nwg, lc);
     }
-    report(FNSSL_LSTM_FAMILY_TRAIN);
-    return dry ? FNSSL_OK : forward_save(p, H, mode, st);
-  }
-
-  // H = 128 full-band layers at full-chip size: hidden slices over clusters of 8 CUs, groups as work items (lstm_f32c.h)
-  // — followed, in the same call, by the rounds below as its GUARDED fallback (they return at once unless the cluster
-  // kernel recorded a hand-off it gave up on: include/fnssl.h, fnssl_lstm_forward)
-  if (d->variant == 0 && !(mode & kHas1) && f32c_handles(p, H, mode)) {
-    // streaming call: the cluster kernel advances the carried cell state in place — snapshot c_{-1} first, so that the guarded
-    // fallback below can restart from it if the launch gives up (LstmWsLayout::carry: room for it in every shape that streams here)
-    const size_t cell_bytes = ws.cell.bytes;
-    char* backup = reinterpret_cast<char*>(d->workspace) + ws.carry.off;
-    const bool snap = p.carry && !dry;
-    if (snap) FNSSL_HIP(hipMemcpyAsync(backup, p.cscratch, cell_bytes, hipMemcpyDeviceToDevice, st));
-    const int rc = forward_f32c(p, H, mode, ws.cluster.bytes, st);
-    if (rc == FNSSL_OK) {
-      report(FNSSL_LSTM_FAMILY_F32_CLUSTER);
-      if (rounds) *rounds = 1;
-      if (dry) return FNSSL_OK;
-      guarded = true;
-      p.guard = reinterpret_cast<const unsigned*>(p.cluster_ws);
-      if (snap) {
-        const long long n4 = (long long)(cell_bytes / 16);
-        hipLaunchKernelGGL(restore_cell_kernel, dim3((unsigned)std::min<long long>((n4 + 255) / 256, 2048)), dim3(256), 0, st, p.guard,
-                           reinterpret_cast<const float4*>(backup), reinterpret_cast<float4*>(p.cscratch), n4);
-        FNSSL_CHECK_LAUNCH("restore_cell_kernel");
-      }
-    } else if (rc != kNoCluster) {
+    if (rc == kNoStatic && !fnssl::tune(FNSSL_TUNE_NO_STATIC_IPDNET)) rc = launch_static_ipdnet(p, mode, H, vr.NW, nwg, lc);
+    if (rc != kNoStatic) {
+      report(FNSSL_LSTM_FAMILY_STATIC);
       return rc;
     }
   }
+  report(FNSSL_LSTM_FAMILY_GENERIC);
+  p.chq = 0;
+  p.pad = 0;
+  if (vr.ring) choose_chunk(p.quads_per_slice, vr, p.chq, p.pad);
+  switch (H) {
+    case 16: return launch_h<16>(variant, p, mode, nwg, lc);
+    case 32: return launch_h<32>(variant, p, mode, nwg, lc);
+    case 64: return launch_h<64>(variant, p, mode, nwg, lc);
+    case 128: return launch_h<128>(variant, p, mode, nwg, lc);
+    default: return launch_h<256>(variant, p, mode, nwg, lc);
+  }
+}
 
-  // one launch of `nw` waves per workgroup over the 16-sequence groups [t0, t1) of every direction
-  auto launch_range = [&](int variant, int t0, int t1) -> int {
-    const Variant& vr = kVariants[variant];
-    p.task0 = t0;
-    p.task1 = t1;
-    p.wgs_per_dir = (t1 - t0 + vr.NW - 1) / vr.NW;
-    const int nwg = p.wgs_per_dir * d->ndir;
-    ++nlaunch;
-    if (d->variant == 0 && !fnssl::tune(FNSSL_TUNE_LSTM_NO_STATIC)) {
-      int rc = kNoStatic;
-      if (H == 128) rc = launch_static_h128(p, mode, vr.NW, nwg, st);
-      if (H == 256) {
-        // the full-chip narrow-band rounds: the operand-ring kernel (lstm_static3.h: two hidden slices per pass, x_t and h_{t-1}
-        // streamed, no register spills; block 1's 260-channel layer included) on a pair-interleaved copy of the stream (re-
-        // ordered into the workspace first: 2 MB per direction, one tiny launch).  NO_STATIC3 keeps the one-slice kernel: A/B.
-        // (Round 3's two-slice kernel with h_{t-1} in registers, lstm_static2.h, was removed in round 5: superseded.)
-        const bool s3 = !p.ablate && !fnssl::tune(FNSSL_TUNE_NO_STATIC3) && (mode == kSum || mode == 0 || mode == (kHas2 | kSum)) &&
-                        ((d->c2 == 0 && !(mode & kHas2)) || (d->c2 == 4 && (mode & kHas2)));
-        if (vr.NW == 12 && d->c0 == 256 && !p.carry && s3) {
-          LstmParams p2 = p;
-          const long long n4 = (long long)(H / 16) * p.quads_per_slice * 4 * 64;      // float4 per direction
-          char* dst = reinterpret_cast<char*>(d->workspace) + ws.stream.off;
-          FNSSL_REQUIRE((size_t)d->ndir * n4 * 16 <= ws.stream.bytes, "lstm_forward: no room for the interleaved weight stream");
-          // round 6: four slices per pass on a QUAD-interleaved copy (lstm_static4.h: half the operand re-reads, the weight ring
-          // staged by LDS-DMA); NO_STATIC4 keeps the two-slice kernel: A/B, same bits
-          const bool s4 = !fnssl::tune(FNSSL_TUNE_NO_STATIC4);
-          for (int di = 0; di < d->ndir; ++di) {
-            float4* o = reinterpret_cast<float4*>(dst + (size_t)di * n4 * 16);
-            if (!dry) {
-              if (s4)
-                hipLaunchKernelGGL(quad_stream_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
-                                   reinterpret_cast<const float4*>(p.wpack[di]), p.quads_per_slice, n4, o);
-              else
-                hipLaunchKernelGGL(pair_stream_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
-                                   reinterpret_cast<const float4*>(p.wpack[di]), p.quads_per_slice, n4, o);
-            }
-            p2.wpack[di] = reinterpret_cast<const float*>(o);
-          }
-          FNSSL_CHECK_LAUNCH("pair_stream_kernel");
-          rc = s4 ? launch_static4_h256(p2, mode, nwg, st) : launch_static3_h256(p2, mode, nwg, st);
-          if (rc != kNoStatic) {
-            report(s4 ? FNSSL_LSTM_FAMILY_STATIC4 : FNSSL_LSTM_FAMILY_STATIC3);
-            return rc;
-          }
-        }
-        rc = launch_static_h256(p, mode, vr.NW, nwg, st);
-      }
-      if (rc == kNoStatic && !fnssl::tune(FNSSL_TUNE_NO_STATIC_IPDNET)) rc = launch_static_ipdnet(p, mode, H, vr.NW, nwg, st);
-      if (rc != kNoStatic) {
-        report(FNSSL_LSTM_FAMILY_STATIC);
-        return rc;
-      }
-    }
-    report(FNSSL_LSTM_FAMILY_GENERIC);
-    p.chq = 0;
-    p.pad = 0;
-    if (vr.ring) choose_chunk(p.quads_per_slice, vr, p.chq, p.pad);
-    switch (H) {
-      case 16: return launch_h<16>(variant, p, mode, nwg, st);
-      case 32: return launch_h<32>(variant, p, mode, nwg, st);
-      case 64: return launch_h<64>(variant, p, mode, nwg, st);
-      case 128: return launch_h<128>(variant, p, mode, nwg, st);
-      default: return launch_h<256>(variant, p, mode, nwg, st);
-    }
-  };
+// few sequences (a single utterance, a streaming chunk): `split` waves per 16-sequence group, one launch.  static_only: only
+// the shape-specialised kernels, kNoStatic when there is none.
+int Fp32Call::launch_split(int split, bool static_only) {
+  const int nw = split == 4 ? 8 : 4, groups_per_wg = nw / split;
+  p.task0 = 0;
+  p.task1 = p.ntasks;
+  p.wgs_per_dir = (p.ntasks + groups_per_wg - 1) / groups_per_wg;
+  const Variant vr{nw, split == 4 ? 8 : 4, 1};
+  choose_chunk(p.quads_per_slice, vr, p.chq, p.pad, split);
+  const int nwg = p.wgs_per_dir * p.ndir;
+  if (rounds) *rounds = 1;
+  if (!p.carry && !(mode & kHas1)) {   // shape-specialised (ring-free) kernels for the network's own shapes
+    const int rc = launch_split_static(p, H, nw, split, mode, 0, nwg, lc);
+    if (rc != kNoStatic) report(FNSSL_LSTM_FAMILY_SPLIT_STATIC);
+    if (rc != kNoStatic || static_only) return rc;
+  } else if (static_only) {
+    return kNoStatic;
+  }
+  report(FNSSL_LSTM_FAMILY_SPLIT);
+  return H == 128 ? launch_split_h<128>(split, p, mode, nwg, lc) : launch_split_h<256>(split, p, mode, nwg, lc);
+}
 
+// The fp32 inference router behind the cluster kernel: a forced variant or a small hidden size (one launch), the split
+// kernels (few sequences), or the launch planner's rounds.
+int Fp32Call::planned_rounds() {
+  const int tasks = p.ntasks;
   if (d->variant != 0 || H < 128) {
     const int variant = d->variant ? d->variant : default_variant(H);
     FNSSL_REQUIRE(variant >= 1 && variant <= kNumVariants, "lstm_forward: unknown variant %d", variant);
-    const int rc = launch_range(variant, 0, tasks);
-    if (rounds && !guarded) *rounds = nlaunch;
-    return rc;
+    return done(launch_round(variant, 0, tasks));
   }
-  if (const int forced = default_variant_override(H)) {
-    const int rc = launch_range(forced, 0, tasks);
-    if (rounds && !guarded) *rounds = nlaunch;
-    return rc;
-  }
+  if (const int forced = default_variant_override(H)) return done(launch_round(forced, 0, tasks));
 
   const int ncu = fnssl::device_cus();
-  // ---- few sequences (a single utterance, a streaming chunk): several waves per 16-sequence group ------
-  auto launch_split = [&](int split, int t0, int t1, bool static_only) -> int {
-    const int nw = split == 4 ? 8 : 4, groups_per_wg = nw / split;
-    p.task0 = t0;
-    p.task1 = t1;
-    p.wgs_per_dir = (t1 - t0 + groups_per_wg - 1) / groups_per_wg;
-    const Variant vr{nw, split == 4 ? 8 : 4, 1};
-    choose_chunk(p.quads_per_slice, vr, p.chq, p.pad, split);
-    const int nwg = p.wgs_per_dir * d->ndir;
-    if (rounds) *rounds = 1;
-    if (!p.carry && !(mode & kHas1)) {   // shape-specialised (ring-free) kernels for the network's own shapes
-      const int rc = launch_split_static(p, H, nw, split, mode, 0, nwg, st);
-      if (rc != kNoStatic) report(FNSSL_LSTM_FAMILY_SPLIT_STATIC);
-      if (rc != kNoStatic || static_only) return rc;
-    } else if (static_only) {
-      return kNoStatic;
+  const long long total = (long long)tasks * d->ndir;
+  if (const int f = fnssl::tune(FNSSL_TUNE_LSTM_SPLIT, 1, 4)) {
+    if (f != 1) return launch_split(f == 3 ? 2 : f, false);
+  } else {
+    // ring-free shape-specialised kernels (H = 256 layers of the network): 4 waves per group pay up to 6 groups
+    // per CU (16 utterances: 13.9 -> 15.6 k frames/s); generic split kernels up to 2 groups per CU
+    // (profiles/r01/d_batch_scan.txt)
+    const int s4 = fnssl::tune(FNSSL_TUNE_SPLIT4_MAX_H256, 1, 64) ? fnssl::tune(FNSSL_TUNE_SPLIT4_MAX_H256, 1, 64) : 6;   // tuning knob
+    if (H == 256 && total <= (long long)s4 * ncu) {
+      const int rc = launch_split(4, true);
+      if (rc != kNoStatic) return rc;
     }
-    report(FNSSL_LSTM_FAMILY_SPLIT);
-    return H == 128 ? launch_split_h<128>(split, p, mode, nwg, st) : launch_split_h<256>(split, p, mode, nwg, st);
-  };
-  {
-    const long long total = (long long)tasks * d->ndir;
-    if (const int f = fnssl::tune(FNSSL_TUNE_LSTM_SPLIT, 1, 4)) {
-      if (f != 1) return launch_split(f == 3 ? 2 : f, 0, tasks, false);
-    } else {
-      // ring-free shape-specialised kernels (H = 256 layers of the network): 4 waves per group pay up to 6 groups
-      // per CU (16 utterances: 13.9 -> 15.6 k frames/s); generic split kernels up to 2 groups per CU
-      // (profiles/r01/d_batch_scan.txt)
-      const int s4 = fnssl::tune(FNSSL_TUNE_SPLIT4_MAX_H256, 1, 64) ? fnssl::tune(FNSSL_TUNE_SPLIT4_MAX_H256, 1, 64) : 6;   // tuning knob
-      if (H == 256 && total <= (long long)s4 * ncu) {
-        const int rc = launch_split(4, 0, tasks, true);
-        if (rc != kNoStatic) return rc;
-      }
-      if (total <= 2LL * ncu) return launch_split(4, 0, tasks, false);
-    }
+    if (total <= 2LL * ncu) return launch_split(4, false);
   }
 
   // ---- launch planner ---------------------------------------------------------------
@@ -586,32 +513,99 @@ static int lstm_forward_impl(const fnssl_lstm_desc* d, void* stream, bool dry, i
   // W = 29 -> 15 + 14 (no SIMD-balanced split covers 29); 191 of its 192 pairs, 7164 groups -> W = 28 -> 16 + 12, one
   // wave-time per SIMD less (Model.FN_SSL peels the last pair onto a second stream for exactly this reason).
   std::vector<int> seq_nw, seq_var;
-  {
-    const int rc = plan_lstm_rounds(H, tasks, d->ndir, ncu, seq_nw, seq_var);
-    if (rc != FNSSL_OK) return rc;
-  }
+  if (const int rc = plan_lstm_rounds(H, tasks, d->ndir, ncu, seq_nw, seq_var)) return rc;
   const int wgs_per_dir_round = ncu / d->ndir > 0 ? ncu / d->ndir : 1;
   int t0 = 0;
   for (size_t r = 0; r < seq_nw.size() && t0 < tasks; ++r) {
     int t1 = r + 1 == seq_nw.size() ? tasks : t0 + wgs_per_dir_round * seq_nw[r];
     if (t1 > tasks) t1 = tasks;
-    const int rc = launch_range(seq_var[r], t0, t1);
+    const int rc = launch_round(seq_var[r], t0, t1);
     if (rc != FNSSL_OK) return rc;
     t0 = t1;
   }
-  if (rounds && !guarded) *rounds = nlaunch;
-  return FNSSL_OK;
+  return done(FNSSL_OK);
+}
+
+// fp32 inference.  H = 128 full-band layers at full-chip size, H = 256 below it: hidden slices over clusters of CUs, groups as
+// work items (lstm_f32c.h) — followed, in the same call, by the router's launches as its GUARDED fallback (they return at
+// once unless the cluster kernel recorded a hand-off it gave up on: include/fnssl.h, fnssl_lstm_forward)
+int Fp32Call::inference() {
+  // streaming call: the cluster kernel advances the carried cell state in place — snapshot c_{-1} first, so that the guarded
+  // fallback can restart from it if the launch gives up (LstmWsLayout::carry: room for it in every shape that streams here)
+  const bool snap = p.carry && !lc.dry;
+  char* backup = reinterpret_cast<char*>(d->workspace) + ws.carry.off;
+  const size_t cell_bytes = ws.cell.bytes;
+  return cluster_then_fallback(
+      lc, d->variant == 0 && !(mode & kHas1) && f32c_handles(p, H, mode), FNSSL_LSTM_FAMILY_F32_CLUSTER, family, p.cluster_ws,
+      [&] {
+        if (snap) FNSSL_HIP(hipMemcpyAsync(backup, p.cscratch, cell_bytes, hipMemcpyDeviceToDevice, lc.st));
+        return forward_f32c(p, H, mode, ws.cluster.bytes, lc);
+      },
+      [&](const unsigned* guard) {
+        p.guard = guard;
+        if (guard) family = rounds = nullptr;
+        if (guard && snap) {
+          const long long n4 = (long long)(cell_bytes / 16);
+          const int rc = enqueue(lc, Kernel{restore_cell_kernel, 256, 0, "restore_cell_kernel"}, (int)std::min<long long>((n4 + 255) / 256, 2048),
+                                 guard, reinterpret_cast<const float4*>(backup), reinterpret_cast<float4*>(p.cscratch), n4);
+          if (rc != FNSSL_OK) return rc;
+        }
+        return planned_rounds();
+      });
+}
+
+// family / rounds: fnssl_lstm_plan's answers (the kernel family and its number of launches), null in a real call
+static int lstm_forward_impl(const fnssl_lstm_desc* d, const LaunchCtx& lc, int* family, int* rounds) {
+  FNSSL_REQUIRE(d, "lstm_forward: null descriptor");
+  fnssl::TuningScope tuning_of_this_call(d->tuning);
+  const int H = d->hidden;
+  const LstmWsLayout ws = lstm_ws_layout(d->nseq, H, d->ndir, d->precision);
+  if (const int rc = check_fwd_desc(d, lc.dry, ws.total)) return rc;
+  const int mode = ((d->src1.p != nullptr && d->c0 > 0) ? kHas1 : 0) | (d->c2 > 0 ? kHas2 : 0) | (d->out_sum ? kSum : 0);
+  Fp32Call c{d, ws, lc, fwd_params(d, ws), H, mode, family, rounds};
+  LstmParams& p = c.p;
+
+  const double flops = 2.0 * 4 * H * (double)(d->c0 + d->c2 + H) * d->nseq * (double)d->nsteps * d->ndir;
+  static const char* names[5] = {"lstm_h16", "lstm_h32", "lstm_h64", "lstm_h128", "lstm_h256"};
+  const int hi = H == 16 ? 0 : H == 32 ? 1 : H == 64 ? 2 : H == 128 ? 3 : 4;
+  fnssl::TimedLaunch tl(lc.dry ? nullptr : names[hi], lc.st, flops);
+
+  if (d->precision == FNSSL_PRECISION_BF16) {   // bf16 MFMA operands (weights packed by fnssl_lstm_pack_bf16)
+    FNSSL_REQUIRE(!(mode & (kHas1 | kSum)) && !d->reserve && !d->carry_state && d->c0 % 16 == 0 && d->c2 % 16 == 0,
+                  "lstm_forward: the bf16 path takes one summed and one concatenated input of 16-channel blocks, "
+                  "no fused residual / reserve / carry");
+    p.quads_per_slice = bf16_quads_per_slice(d->c0, d->c2, H);
+    p.chq = 0;
+    p.pad = 0;
+    c.report(FNSSL_LSTM_FAMILY_BF16);
+    return forward_bf16(p, H, lc);
+  }
+  if (d->precision == FNSSL_PRECISION_BF16W) {   // wide bf16 kernels: 32 sequences per wave, bf16 / fp32 activation tensors
+    FNSSL_REQUIRE(!(mode & (kHas1 | kSum)) && !d->reserve && !d->carry_state && d->c0 % 16 == 0 && d->c2 % 16 == 0,
+                  "lstm_forward: the wide bf16 path takes 16-channel input blocks, no fused residual / reserve / carry");
+    auto mult8 = [](long long so, long long si, long long st) { return ((so | si | st) & 7) == 0; };
+    const int fm = d->f32_mask & 7;
+    FNSSL_REQUIRE(((fm & 1) || !d->c0 || mult8(d->src0.so, d->src0.si, d->src0.st)) &&
+                      ((fm & 2) || !d->c2 || mult8(d->src2.so, d->src2.si, d->src2.st)) &&
+                      ((fm & 4) || mult8(d->out_so, d->out_si, d->out_st)),
+                  "lstm_forward: strides of bf16 tensors must be multiples of 8 elements");
+    return forward_bf16w(p, H, fm, ws.cluster.bytes, lc, family);
+  }
+  FNSSL_REQUIRE(d->precision == FNSSL_PRECISION_FP32, "lstm_forward: unknown precision %d", d->precision);
+  return d->reserve ? c.train() : c.inference();
 }
 
 extern "C" {
 
-int fnssl_lstm_forward(const fnssl_lstm_desc* d, void* stream) { return lstm_forward_impl(d, stream, false, nullptr, nullptr); }
+int fnssl_lstm_forward(const fnssl_lstm_desc* d, void* stream) {
+  return lstm_forward_impl(d, LaunchCtx{fnssl::as_stream(stream), false}, nullptr, nullptr);
+}
 
 int fnssl_lstm_plan(const fnssl_lstm_desc* d, int* family, int* rounds) {
   FNSSL_REQUIRE(family, "lstm_plan: null pointer");
   *family = 0;
-  if (rounds) *rounds = 1;
-  return lstm_forward_impl(d, nullptr, true, family, rounds);
+  if (rounds) *rounds = 1;   // what every family but the planner's rounds (Fp32Call::done) takes
+  return lstm_forward_impl(d, LaunchCtx{nullptr, true}, family, rounds);
 }
 
 }  // extern "C"
@@ -619,5 +613,5 @@ int fnssl_lstm_plan(const fnssl_lstm_desc* d, int* family, int* rounds) {
 // ---- the generic recurrence kernels for hidden size 128 (explicit instantiation, see lstm_kernel.h; the other hidden sizes:
 // lstm_hsmall.hip, lstm_h256.hip)
 namespace fnssl_lstm {
-template int launch_h<128>(int, const LstmParams&, int, int, hipStream_t);
+template int launch_h<128>(int, const LstmParams&, int, int, const LaunchCtx&);
 }  // namespace fnssl_lstm

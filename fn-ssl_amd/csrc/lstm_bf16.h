@@ -228,20 +228,13 @@ __global__ void __launch_bounds__(NW * 64) lstm_bf16_kernel(const LstmParams p) 
 }
 
 template <int H, int NW, int M, int NV0, int NV2, int CHQ, int PAD>
-int launch_bf16_k(const LstmParams& p, int nwg, hipStream_t st) {
-  if (p.dry) return FNSSL_OK;   // fnssl_lstm_plan: report the family, launch nothing
+int launch_bf16_k(const LstmParams& p, int nwg, const LaunchCtx& lc) {
   const size_t lds = (size_t)2 * CHQ * 4096;
   static_assert(2 * CHQ * 4096 <= 160 * 1024, "ring does not fit the LDS");
-  auto k = lstm_bf16_kernel<H, NW, M, NV0, NV2, CHQ, PAD>;
-  if (lds > 48 * 1024)
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-  hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, st, p);
-  FNSSL_CHECK_LAUNCH("lstm_bf16_kernel");
-  return FNSSL_OK;
+  return enqueue(lc, Kernel{lstm_bf16_kernel<H, NW, M, NV0, NV2, CHQ, PAD>, NW * 64, lds, "lstm_bf16_kernel"}, nwg, p);
 }
 
 // kNoStatic when (H, NW, c0, c2) has no bf16 instantiation
-int launch_bf16(const LstmParams& p, int H, int NW, int nwg, hipStream_t st);
+int launch_bf16(const LstmParams& p, int H, int NW, int nwg, const LaunchCtx& lc);
 
 }  // namespace fnssl_lstm

@@ -8,9 +8,9 @@ namespace fnssl_lstm {
 
 #define TRYB(H_, NW_, M_, NV0_, NV2_, CHQ_, PAD_)                                          \
   if (H == H_ && NW == NW_ && p.c0 == 16 * NV0_ && p.c2 == 16 * NV2_)                       \
-    return launch_bf16_k<H_, NW_, M_, NV0_, NV2_, CHQ_, PAD_>(p, nwg, st);
+    return launch_bf16_k<H_, NW_, M_, NV0_, NV2_, CHQ_, PAD_>(p, nwg, lc);
 
-int launch_bf16(const LstmParams& p, int H, int NW, int nwg, hipStream_t st) {
+int launch_bf16(const LstmParams& p, int H, int NW, int nwg, const LaunchCtx& lc) {
   // IPDnet, hidden 256 (more than two microphones): narrow-band 256 <- [256 | 16]
   TRYB(256, 4, 12, 16, 1, 9, 0)
   // full-band 128 <- [256 | 16] (block 2; also the offline narrow-band layers) and 128 <- 16 (block 1)
@@ -41,7 +41,7 @@ static unsigned short to_bf16(float f) {   // round to nearest even
 }
 
 // Launch plan of the bf16 path: 4 or 8 waves per workgroup, rounds of 8 waves per CU.
-int forward_bf16(LstmParams p, int H, hipStream_t st) {
+int forward_bf16(LstmParams p, int H, const LaunchCtx& lc) {
   const int ncu = fnssl::device_cus();
   const int tasks = p.ntasks;
   const long long total = (long long)tasks * p.ndir;
@@ -59,7 +59,7 @@ int forward_bf16(LstmParams p, int H, hipStream_t st) {
     p.task0 = t0;
     p.task1 = t1;
     p.wgs_per_dir = (t1 - t0 + nw - 1) / nw;
-    const int rc = launch_bf16(p, H, nw, p.wgs_per_dir * p.ndir, st);
+    const int rc = launch_bf16(p, H, nw, p.wgs_per_dir * p.ndir, lc);
     if (rc == kNoStatic) {
       fnssl::set_error("lstm_forward: the bf16 path is not built for hidden %d with inputs (%d, %d)", H, p.c0, p.c2);
       return FNSSL_E_INVALID;

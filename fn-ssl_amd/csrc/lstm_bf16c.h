@@ -389,18 +389,11 @@ __global__ void __launch_bounds__(512) lstm_bf16c_kernel(const LstmParams p, con
 }
 
 template <int H, int NB0, int NB2, int FLAGS, int ABL = 0, int WG_ = 0, int AD = 1>
-int launch_bf16c_k(const LstmParams& p, const ClusterParams& cp, hipStream_t st) {
+int launch_bf16c_k(const LstmParams& p, const ClusterParams& cp, const LaunchCtx& lc) {
   constexpr int KT = 1 + NB0 + NB2 + H / 16, CL = cluster_members(H);
   const size_t lds = (size_t)(H / 8 / CL) * KT * 1024;
-  auto k = lstm_bf16c_kernel<H, NB0, NB2, FLAGS, ABL, WG_, AD>;
-  FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int nwg = 8 * CL * ((cp.ncl + 7) / 8);
-  // every member of every cluster of the launch must be resident at once (see launch_f32c_k)
-  if (!cluster_grid_fits(reinterpret_cast<const void*>(k), 512, lds, nwg)) return kNoCluster;
-  if (p.dry) return FNSSL_OK;   // fnssl_lstm_plan: report the family, launch nothing
-  hipLaunchKernelGGL(k, dim3(nwg), dim3(512), lds, st, p, cp);
-  FNSSL_CHECK_LAUNCH("lstm_bf16c_kernel");
-  return FNSSL_OK;
+  return enqueue(lc, Kernel{lstm_bf16c_kernel<H, NB0, NB2, FLAGS, ABL, WG_, AD>, 512, lds, "lstm_bf16c_kernel", true}, nwg, p, cp);
 }
 
 }  // namespace fnssl_lstm

@@ -26,18 +26,18 @@ bool bf16c_handles(const LstmParams& p, int H, int flags) {
 }
 
 template <int H>
-static int launch_one(const LstmParams& p, const ClusterParams& cp, hipStream_t st) {
+static int launch_one(const LstmParams& p, const ClusterParams& cp, const LaunchCtx& lc) {
   if constexpr (H == 128) {
-    if (p.c0 == 0) return launch_bf16c_k<128, 0, 1, kW_F2>(p, cp, st);   // block 1 (its input travels as the fp32 block)
+    if (p.c0 == 0) return launch_bf16c_k<128, 0, 1, kW_F2>(p, cp, lc);   // block 1 (its input travels as the fp32 block)
   }
 #ifdef FNSSL_BUILD_ABLATE   // timing ablations (wrong results): make ABLATE=1 only
   switch (env_int("FNSSL_CLUSTER_ABL", 1, 127)) {
-    case 1: return launch_bf16c_k<H, 16, 1, kW_F2, 1>(p, cp, st);
-    case 2: return launch_bf16c_k<H, 16, 1, kW_F2, 2>(p, cp, st);
-    case 9: return launch_bf16c_k<H, 16, 1, kW_F2, 9>(p, cp, st);
-    case 25: return launch_bf16c_k<H, 16, 1, kW_F2, 25>(p, cp, st);
-    case 32: return launch_bf16c_k<H, 16, 1, kW_F2, 32>(p, cp, st);
-    case 65: return launch_bf16c_k<H, 16, 1, kW_F2, 65>(p, cp, st);
+    case 1: return launch_bf16c_k<H, 16, 1, kW_F2, 1>(p, cp, lc);
+    case 2: return launch_bf16c_k<H, 16, 1, kW_F2, 2>(p, cp, lc);
+    case 9: return launch_bf16c_k<H, 16, 1, kW_F2, 9>(p, cp, lc);
+    case 25: return launch_bf16c_k<H, 16, 1, kW_F2, 25>(p, cp, lc);
+    case 32: return launch_bf16c_k<H, 16, 1, kW_F2, 32>(p, cp, lc);
+    case 65: return launch_bf16c_k<H, 16, 1, kW_F2, 65>(p, cp, lc);
     default: break;
   }
 #endif
@@ -47,11 +47,11 @@ static int launch_one(const LstmParams& p, const ClusterParams& cp, hipStream_t 
   //  between the MFMAs — was built and measured: bit-identical, 8.3 ms against 5.7 for the narrow-band layer; the gate math
   //  of 64 sequences needs every issue cycle the MFMAs leave free, and one wave per SIMD exposes every store
   //  acknowledgement and tag wait: profiles/r03/l_cluster_64_sequences_per_wave_not_kept.txt, git history for the code)
-  return launch_bf16c_k<H, 16, 1, kW_F2>(p, cp, st);
+  return launch_bf16c_k<H, 16, 1, kW_F2>(p, cp, lc);
 }
 
 // Launches of at most CUs / members clusters (one workgroup per CU: every member of every cluster of a launch is resident).
-int forward_bf16c(LstmParams p, int H, int flags, size_t cluster_bytes, hipStream_t st) {
+int forward_bf16c(LstmParams p, int H, int flags, size_t cluster_bytes, const LaunchCtx& lc) {
   if (flags == kW_F0) {   // block 1's full-band layer: the kernel's one fp32 block is src2; same record layout in the stream
     p.src2 = p.src0;
     p.c2 = p.c0;
@@ -96,14 +96,14 @@ int forward_bf16c(LstmParams p, int H, int flags, size_t cluster_bytes, hipStrea
   cp.spin_limit = cluster_spin_limit();
   cp.stall_member = cluster_test_stall();
   // status word + tags, and the parity-1 operand records (step 0 reads h_{-1} = 0 from them)
-  if (!p.dry) {
-    FNSSL_HIP(hipMemsetAsync(p.cluster_ws, 0, head, st));
-    FNSSL_HIP(hipMemsetAsync(cp.hx + cp.parity_stride, 0, cp.parity_stride, st));
+  if (!lc.dry) {
+    FNSSL_HIP(hipMemsetAsync(p.cluster_ws, 0, head, lc.st));
+    FNSSL_HIP(hipMemsetAsync(cp.hx + cp.parity_stride, 0, cp.parity_stride, lc.st));
   }
   for (int c0 = 0; c0 < ncl; c0 += per_launch) {
     cp.cl0 = c0;
     cp.ncl = ncl - c0 < per_launch ? ncl - c0 : per_launch;
-    const int rc = H == 256 ? launch_one<256>(p, cp, st) : launch_one<128>(p, cp, st);
+    const int rc = H == 256 ? launch_one<256>(p, cp, lc) : launch_one<128>(p, cp, lc);
     if (rc != FNSSL_OK) return rc;
   }
   return FNSSL_OK;

@@ -361,21 +361,15 @@ __global__ void __launch_bounds__((NW + NL) * 64) lstm_bf16w_kernel(const LstmPa
 }
 
 template <int H, int NW, int NB0, int NB2, int FLAGS, int NSLOT, int NL, int ABL = 0>
-int launch_bf16w_k(const LstmParams& p, int nwg, hipStream_t st) {
-  if (p.dry) return FNSSL_OK;   // fnssl_lstm_plan: report the family, launch nothing
+int launch_bf16w_k(const LstmParams& p, int nwg, const LaunchCtx& lc) {
   constexpr int KT = 1 + NB0 + NB2 + H / 16;
   const size_t lds = (size_t)NSLOT * KT * 1024 + (size_t)NW * (H / 16) * 1024;
-  auto k = lstm_bf16w_kernel<H, NW, NB0, NB2, FLAGS, NSLOT, NL, ABL>;
-  if (lds > 48 * 1024)
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, dim3(nwg), dim3((NW + NL) * 64), lds, st, p);
-  FNSSL_CHECK_LAUNCH("lstm_bf16w_kernel");
-  return FNSSL_OK;
+  return enqueue(lc, Kernel{lstm_bf16w_kernel<H, NW, NB0, NB2, FLAGS, NSLOT, NL, ABL>, (NW + NL) * 64, lds, "lstm_bf16w_kernel"}, nwg, p);
 }
 
 // kNoStatic when the shape / element types have no instantiation
-int launch_bf16w(const LstmParams& p, int H, int NW, int flags, int nwg, hipStream_t st);
+int launch_bf16w(const LstmParams& p, int H, int NW, int flags, int nwg, const LaunchCtx& lc);
 // cluster_bytes = the size of p.cluster_ws (the hand-off area of the cluster-resident kernel, lstm_bf16c.h)
-int forward_bf16w(LstmParams p, int H, int flags, size_t cluster_bytes, hipStream_t st, int* family = nullptr);
+int forward_bf16w(LstmParams p, int H, int flags, size_t cluster_bytes, const LaunchCtx& lc, int* family = nullptr);
 
 }  // namespace fnssl_lstm

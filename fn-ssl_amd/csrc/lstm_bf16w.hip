@@ -9,17 +9,17 @@
 namespace fnssl_lstm {
 
 bool bf16c_handles(const LstmParams& p, int H, int flags);           // lstm_bf16c.hip
-int forward_bf16c(LstmParams p, int H, int flags, size_t cluster_bytes, hipStream_t st);
+int forward_bf16c(LstmParams p, int H, int flags, size_t cluster_bytes, const LaunchCtx& lc);
 
 // NW = 2: two consumer waves + two loader waves on the SIMDs the launch leaves idle; NW = 4: four consumers that
 // fetch their own stream (H = 128 only: at H = 256 the ring plus four h staging areas exceed the LDS)
 #define TRYW(H_, NB0_, NB2_, FL_)                                                                                \
   if (H == H_ && p.c0 == 16 * NB0_ && p.c2 == 16 * NB2_ && flags == (FL_)) {                                    \
-    if (NW == 2) return launch_bf16w_k<H_, 2, NB0_, NB2_, FL_, 3, 2>(p, nwg, st);                                \
-    if (NW == 4 && H_ < 256) return launch_bf16w_k<H_ < 256 ? H_ : 128, 4, NB0_, NB2_, FL_, 3, 0>(p, nwg, st);   \
+    if (NW == 2) return launch_bf16w_k<H_, 2, NB0_, NB2_, FL_, 3, 2>(p, nwg, lc);                                \
+    if (NW == 4 && H_ < 256) return launch_bf16w_k<H_ < 256 ? H_ : 128, 4, NB0_, NB2_, FL_, 3, 0>(p, nwg, lc);   \
   }
 
-int launch_bf16w(const LstmParams& p, int H, int NW, int flags, int nwg, hipStream_t st) {
+int launch_bf16w(const LstmParams& p, int H, int NW, int flags, int nwg, const LaunchCtx& lc) {
   // IPDnet, hidden 256: full-band 128 <- 16 fp32 feature channels; narrow-band 256 <- [256 bf16 | 16 fp32];
   // full-band 128 <- [256 bf16 | 16 fp32]; outputs bf16 (the conv head reads bf16: fnssl_conv3x3_causal_bf16a).
   // (fp32 main input / output at H = 256 would need > 512 registers per lane: convert outside instead.)
@@ -33,17 +33,17 @@ int launch_bf16w(const LstmParams& p, int H, int NW, int flags, int nwg, hipStre
 // groups every shape runs with — larger workgroups were measured and do not pay, see forward_bf16w)
 #define TRYP(H_, NB0_, NB2_, FL_)                                                    \
   if (H == H_ && p.c0 == 16 * NB0_ && p.c2 == 16 * NB2_ && flags == (FL_))          \
-    return drain ? launch_bf16p_k<H_, NB0_, NB2_, FL_, 0, 2, true>(p, nwg, st) : launch_bf16p_k<H_, NB0_, NB2_, FL_>(p, nwg, st);
+    return drain ? launch_bf16p_k<H_, NB0_, NB2_, FL_, 0, 2, true>(p, nwg, lc) : launch_bf16p_k<H_, NB0_, NB2_, FL_>(p, nwg, lc);
 
 // pair-split kernels (lstm_bf16p.h): workgroup = ng groups of 32 sequences x 2 roles (ng = 2, or 5 for the H = 128 shapes)
-int launch_bf16p(const LstmParams& p, int H, int flags, int nwg, hipStream_t st) {
+int launch_bf16p(const LstmParams& p, int H, int flags, int nwg, const LaunchCtx& lc) {
 #ifdef FNSSL_BUILD_ABLATE   // timing ablations of the config-3 narrow-band kernel (wrong results): make ABLATE=1 only
   if (const char* e = getenv("FNSSL_BF16W_ABL")) {
     if (H == 256 && p.c0 == 256 && p.c2 == 16 && flags == kW_F2) {
       switch (atoi(e)) {
-        case 1: return launch_bf16p_k<256, 16, 1, kW_F2, 1>(p, nwg, st);
-        case 4: return launch_bf16p_k<256, 16, 1, kW_F2, 4>(p, nwg, st);
-        case 5: return launch_bf16p_k<256, 16, 1, kW_F2, 5>(p, nwg, st);
+        case 1: return launch_bf16p_k<256, 16, 1, kW_F2, 1>(p, nwg, lc);
+        case 4: return launch_bf16p_k<256, 16, 1, kW_F2, 4>(p, nwg, lc);
+        case 5: return launch_bf16p_k<256, 16, 1, kW_F2, 5>(p, nwg, lc);
         default: break;
       }
     }
@@ -57,30 +57,14 @@ int launch_bf16p(const LstmParams& p, int H, int flags, int nwg, hipStream_t st)
 }
 
 // One launch: every 32-sequence group of every direction.  Default: the pair-split kernels; FNSSL_BF16W_SOLO=1 keeps
-// the one-wave-per-group kernels of lstm_bf16w.h (A/B).
-int forward_bf16w(LstmParams p, int H, int flags, size_t cluster_bytes, hipStream_t st, int* family) {
-  const int ncu = fnssl::device_cus();
-  const int groups = (p.nseq + 31) / 32;
-  const long long total = (long long)groups * p.ndir;
-  p.task0 = 0;
-  p.task1 = groups;
-  // cluster-resident kernel (lstm_bf16c.h) for the shape it is built for: weights stay in LDS, h_t is exchanged through L2
-  // — followed by the pair-split launch below as its GUARDED fallback (include/fnssl.h, fnssl_lstm_forward)
-  bool guarded = false;
-  if (bf16c_handles(p, H, flags)) {
-    const int rc = forward_bf16c(p, H, flags, cluster_bytes, st);
-    if (rc == FNSSL_OK) {
-      if (family) *family = FNSSL_LSTM_FAMILY_BF16_CLUSTER;
-      if (p.dry) return FNSSL_OK;
-      guarded = true;
-      p.guard = reinterpret_cast<const unsigned*>(p.cluster_ws);
-    } else if (rc != kNoCluster) {
-      return rc;
-    }
-  }
+// the one-wave-per-group kernels of lstm_bf16w.h (A/B).  guard != nullptr: as the guarded fallback of the cluster kernel
+// (always the pair-split kernels; family = nullptr).
+static int forward_bf16w_plain(LstmParams p, int H, int flags, const unsigned* guard, const LaunchCtx& lc, int* family) {
+  const int groups = p.task1;
+  p.guard = guard;
   int rc;
-  if (!fnssl::tune(FNSSL_TUNE_BF16W_SOLO) || guarded) {
-    if (family && !guarded) *family = FNSSL_LSTM_FAMILY_BF16_PAIR;
+  if (!fnssl::tune(FNSSL_TUNE_BF16W_SOLO) || guard) {
+    if (family) *family = FNSSL_LSTM_FAMILY_BF16_PAIR;
     // Two 32-sequence groups per workgroup.  lstm_bf16p_kernel takes NG groups (template), and 3 / 4 / 5 were built and
     // measured at config 3 (profiles/r03/h_bf16p_groups_per_workgroup.txt) in the hope of turning the full-band layers'
     // 600 workgroups (2.34 rounds run as 3) into 400 / 300 / 240: bit-identical, never faster (full-band layers 13.1 ms
@@ -89,12 +73,12 @@ int forward_bf16w(LstmParams p, int H, int flags, size_t cluster_bytes, hipStrea
     // 128 B/clk, so the formulation is bound by LDS bandwidth, not by rounds.
     const int ng = 2;
     p.wgs_per_dir = (groups + ng - 1) / ng;
-    rc = launch_bf16p(p, H, flags, p.wgs_per_dir * p.ndir, st);
+    rc = launch_bf16p(p, H, flags, p.wgs_per_dir * p.ndir, lc);
   } else {
     if (family) *family = FNSSL_LSTM_FAMILY_BF16_SOLO;
-    const int nw = (total <= 2ll * ncu || H >= 256) ? 2 : 4;
+    const int nw = ((long long)groups * p.ndir <= 2ll * fnssl::device_cus() || H >= 256) ? 2 : 4;
     p.wgs_per_dir = (groups + nw - 1) / nw;
-    rc = launch_bf16w(p, H, nw, flags, p.wgs_per_dir * p.ndir, st);
+    rc = launch_bf16w(p, H, nw, flags, p.wgs_per_dir * p.ndir, lc);
   }
   if (rc == kNoStatic) {
     fnssl::set_error("lstm_forward: the wide bf16 path is not built for hidden %d, inputs (%d, %d), element mask %d", H,
@@ -102,6 +86,17 @@ int forward_bf16w(LstmParams p, int H, int flags, size_t cluster_bytes, hipStrea
     return FNSSL_E_INVALID;
   }
   return rc;
+}
+
+int forward_bf16w(LstmParams p, int H, int flags, size_t cluster_bytes, const LaunchCtx& lc, int* family) {
+  p.task0 = 0;
+  p.task1 = (p.nseq + 31) / 32;
+  // cluster-resident kernel (lstm_bf16c.h) for the shape it is built for: weights stay in LDS, h_t is exchanged through L2
+  // — followed by the pair-split launch as its GUARDED fallback (include/fnssl.h, fnssl_lstm_forward)
+  return cluster_then_fallback(
+      lc, bf16c_handles(p, H, flags), FNSSL_LSTM_FAMILY_BF16_CLUSTER, family, p.cluster_ws,
+      [&] { return forward_bf16c(p, H, flags, cluster_bytes, lc); },
+      [&](const unsigned* guard) { return forward_bf16w_plain(p, H, flags, guard, lc, guard ? nullptr : family); });
 }
 
 static unsigned short to_bf16w(float f) {   // round to nearest even

@@ -219,15 +219,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 }
 
 template <int H>
-int launch_bwd2_k(const BwdParams& p, int nwg, hipStream_t st) {
-  if (p.dry) return FNSSL_OK;
+int launch_bwd2_k(const BwdParams& p, int nwg, const LaunchCtx& lc) {
   const size_t lds = (size_t)2 * (4 * H / 16) * 1024 + (size_t)2 * (H / 16) * 1024;   // both groups' dA rows + carried dh
-  FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_bwd2_kernel<H>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(lstm_bwd2_kernel<H>, dim3(nwg), dim3(256), lds, st, p);
-  FNSSL_CHECK_LAUNCH("lstm_bwd2_kernel");
-  return FNSSL_OK;
+  return enqueue(lc, Kernel{lstm_bwd2_kernel<H>, 256, lds, "lstm_bwd2_kernel"}, nwg, p);
 }
 
-extern template int launch_bwd2_k<256>(const BwdParams&, int, hipStream_t);
+extern template int launch_bwd2_k<256>(const BwdParams&, int, const LaunchCtx&);
 
 }  // namespace fnssl_lstm

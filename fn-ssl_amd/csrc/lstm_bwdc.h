@@ -419,16 +419,10 @@ __global__ void __launch_bounds__(NW_ * 64) lstm_bwdc_kernel(const BwdParams p, 
 }
 
 template <int NW_ = kBwdcWaves, bool ABLRT = false, int XD_ = 8>
-int launch_bwdc_k(const BwdParams& p, const BwdClusterParams& cp, hipStream_t st) {
+int launch_bwdc_k(const BwdParams& p, const BwdClusterParams& cp, const LaunchCtx& lc) {
   const size_t lds = (size_t)(4 * 128 / 16) * 4096 + 64;        // 32 quads = 128 KiB, + the SIMD tokens
-  auto k = lstm_bwdc_kernel<NW_, ABLRT, XD_>;
-  FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int nwg = 8 * cp.clusters_per_xcd * cp.members;   // block b: XCD b & 7, index b >> 3 inside it
-  if (!cluster_grid_fits(reinterpret_cast<const void*>(k), NW_ * 64, lds, nwg)) return kNoCluster;
-  if (p.dry) return FNSSL_OK;   // fnssl_lstm_backward_plan: the family is reported only after the occupancy check, like the forward's
-  hipLaunchKernelGGL(k, dim3(nwg), dim3(NW_ * 64), lds, st, p, cp);
-  FNSSL_CHECK_LAUNCH("lstm_bwdc_kernel");
-  return FNSSL_OK;
+  return enqueue(lc, Kernel{lstm_bwdc_kernel<NW_, ABLRT, XD_>, NW_ * 64, lds, "lstm_bwdc_kernel", true}, nwg, p, cp);
 }
 
 }  // namespace fnssl_lstm

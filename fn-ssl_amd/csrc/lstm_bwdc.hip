@@ -34,7 +34,7 @@ bool bwdc_handles(const BwdParams& p, int H, BwdClusterParams& cp) {
 
 // ws = the cluster area of fnssl_lstm_backward's workspace (BwdWsLayout, lstm_train.hip), ws_bytes its size.  FNSSL_OK,
 // kNoCluster, or an error.
-int backward_cluster(const BwdParams& p, BwdClusterParams cp, void* ws, size_t ws_bytes, hipStream_t st) {
+int backward_cluster(const BwdParams& p, BwdClusterParams cp, void* ws, size_t ws_bytes, const LaunchCtx& lc) {
   cp.status = static_cast<unsigned*>(ws);
   cp.tags = cp.status + 64;
   cp.spin_limit = cluster_spin_limit();
@@ -44,12 +44,12 @@ int backward_cluster(const BwdParams& p, BwdClusterParams cp, void* ws, size_t w
   cp.simd_token = !fnssl::tune(FNSSL_TUNE_BWDC_NO_TOKEN);
   const size_t tag_bytes = (size_t)cp.clusters_per_dir * p.ndir * cp.groups_per_cluster * 16 * sizeof(unsigned);
   FNSSL_REQUIRE(256 + tag_bytes <= ws_bytes, "lstm_backward: the cluster kernel's tags exceed the workspace's cluster area");
-  if (!p.dry) FNSSL_HIP(hipMemsetAsync(ws, 0, 256 + tag_bytes, st));   // (dry: the launchers stop after their occupancy check)
+  if (!lc.dry) FNSSL_HIP(hipMemsetAsync(ws, 0, 256 + tag_bytes, lc.st));   // (dry: the launch stops after its occupancy check)
 #ifdef FNSSL_BUILD_ABLATE
-  if ((cp.ablate = env_int("FNSSL_BWDC_ABLATE", 1, 1 << 20)) != 0) return launch_bwdc_k<kBwdcWaves, true>(p, cp, st);
+  if ((cp.ablate = env_int("FNSSL_BWDC_ABLATE", 1, 1 << 20)) != 0) return launch_bwdc_k<kBwdcWaves, true>(p, cp, lc);
 #endif
-  if (fnssl::tune(FNSSL_TUNE_BWDC_WAVES16)) return launch_bwdc_k<16, false, 4>(p, cp, st);   // the first shape: 16 waves, 4-deep ring
-  return launch_bwdc_k<kBwdcWaves>(p, cp, st);
+  if (fnssl::tune(FNSSL_TUNE_BWDC_WAVES16)) return launch_bwdc_k<16, false, 4>(p, cp, lc);   // the first shape: 16 waves, 4-deep ring
+  return launch_bwdc_k<kBwdcWaves>(p, cp, lc);
 }
 
 }  // namespace fnssl_lstm

@@ -514,23 +514,14 @@ __global__ void __launch_bounds__(NW_ * 64) lstm_f32c_kernel(const LstmParams p,
 }
 
 template <int HH, int NV0, int NS0, int MODE, bool ABLRT = false, int DRIFT = 2, int NW_ = kF32cWaves, int GS = 1>
-int launch_f32c_k(const LstmParams& p, const F32ClusterParams& cp, hipStream_t st) {
+int launch_f32c_k(const LstmParams& p, const F32ClusterParams& cp, const LaunchCtx& lc) {
   constexpr int NS = HH / 16;
   constexpr int QPS = 1 + NV0 + NS0 + NS;
   const size_t lds = (size_t)QPS * 4096 + (GS > 1 ? (size_t)(NW_ / GS) * 8192 + 64 : 0);   // + the slots' gate records and counters
   static_assert(QPS * 4096 + (GS > 1 ? (NW_ / GS) * 8192 + 64 : 0) <= 160 * 1024, "LDS");
-  auto k = lstm_f32c_kernel<HH, NV0, NS0, MODE, ABLRT, DRIFT, NW_, GS>;
-  if (lds > 48 * 1024)
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int ncl = cp.clusters_per_dir * p.ndir;
   const int nwg = 8 * NS * ((ncl + 7) / 8);                  // block b: XCD b & 7, member (b >> 3) % NS, cluster ((b >> 3) / NS) * 8 + (b & 7)
-  // every member of every cluster must be resident at once: the grid may not exceed what the device says it can hold
-  // (the waits are bounded and the call carries a guarded fallback anyway — this only avoids a launch that cannot work)
-  if (!cluster_grid_fits(reinterpret_cast<const void*>(k), NW_ * 64, lds, nwg)) return kNoCluster;
-  if (p.dry) return FNSSL_OK;   // fnssl_lstm_plan: report the family, launch nothing
-  hipLaunchKernelGGL(k, dim3(nwg), dim3(NW_ * 64), lds, st, p, cp);
-  FNSSL_CHECK_LAUNCH("lstm_f32c_kernel");
-  return FNSSL_OK;
+  return enqueue(lc, Kernel{lstm_f32c_kernel<HH, NV0, NS0, MODE, ABLRT, DRIFT, NW_, GS>, NW_ * 64, lds, "lstm_f32c_kernel", true}, nwg, p, cp);
 }
 
 }  // namespace fnssl_lstm

@@ -80,7 +80,16 @@ bool f32c_handles(const LstmParams& p, int H, int mode) {
   return !fnssl::tune(FNSSL_TUNE_NO_F32_SMALL) || groups >= 12LL * ncu;
 }
 
-int forward_f32c(LstmParams p, int H, int mode, size_t cluster_bytes, hipStream_t st) {
+// the four input / output combinations of the H = 256 layers, NW_ waves per member, gate split GS
+template <int NW_, int GS>
+static int launch_f32c_h256(const LstmParams& p, const F32ClusterParams& cp, int mode, const LaunchCtx& lc) {
+  if (mode == (kHas2 | kSum)) return launch_f32c_k<256, 16, 1, kHas2 | kSum, false, 2, NW_, GS>(p, cp, lc);
+  if (mode == kHas2) return launch_f32c_k<256, 16, 1, kHas2, false, 2, NW_, GS>(p, cp, lc);
+  if (mode == kSum) return launch_f32c_k<256, 16, 0, kSum, false, 2, NW_, GS>(p, cp, lc);
+  return launch_f32c_k<256, 16, 0, 0, false, 2, NW_, GS>(p, cp, lc);
+}
+
+int forward_f32c(LstmParams p, int H, int mode, size_t cluster_bytes, const LaunchCtx& lc) {
   if (f32c_uniform(p, mode)) p.q_inner = p.nseq;   // one outer index: no group ever crosses (any q_inner, e.g. 12 frames)
   const int ncu = cluster_cus();
   const int members = H / 16;
@@ -95,7 +104,7 @@ int forward_f32c(LstmParams p, int H, int mode, size_t cluster_bytes, hipStream_
   cp.prio_mode = fnssl::tune(FNSSL_TUNE_F32C_PRIO, 9, 9) ? 0 : 2;   // see F32ClusterParams
   const size_t tag_bytes = (size_t)p.ndir * cp.clusters_per_dir * cp.groups_per_cluster * members * sizeof(unsigned);
   FNSSL_REQUIRE(256 + tag_bytes <= cluster_bytes, "lstm_forward: the cluster kernel's tags exceed the workspace's cluster area");
-  if (!p.dry) FNSSL_HIP(hipMemsetAsync(p.cluster_ws, 0, 256 + tag_bytes, st));
+  if (!lc.dry) FNSSL_HIP(hipMemsetAsync(p.cluster_ws, 0, 256 + tag_bytes, lc.st));
   // Gate split (lstm_f32c.h): only with ONE group per cluster (one 2-mic utterance, the full-band layers of a streaming
   // chunk) — there a step is the group's own matrix work plus its hand-off, and four SIMDs share the former.  With more
   // groups the waves that each own a group hide one another's hand-off latency, which two (four) slots working through
@@ -107,47 +116,33 @@ int forward_f32c(LstmParams p, int H, int mode, size_t cluster_bytes, hipStream_
   if (H == 256) {
     constexpr int W = kF32cWavesH256;
     if (p.reserve)
-      return p.c2 == 4 ? launch_f32c_k<256, 16, 1, kHas2 | kSave, false, 2, W>(p, cp, st) : launch_f32c_k<256, 16, 0, kSave, false, 2, W>(p, cp, st);
-    if (gsplit) {
-      if (mode == (kHas2 | kSum)) return launch_f32c_k<256, 16, 1, kHas2 | kSum, false, 2, kF32cWavesH256Split, 4>(p, cp, st);
-      if (mode == kHas2) return launch_f32c_k<256, 16, 1, kHas2, false, 2, kF32cWavesH256Split, 4>(p, cp, st);
-      if (mode == kSum) return launch_f32c_k<256, 16, 0, kSum, false, 2, kF32cWavesH256Split, 4>(p, cp, st);
-      return launch_f32c_k<256, 16, 0, 0, false, 2, kF32cWavesH256Split, 4>(p, cp, st);
-    }
+      return p.c2 == 4 ? launch_f32c_k<256, 16, 1, kHas2 | kSave, false, 2, W>(p, cp, lc) : launch_f32c_k<256, 16, 0, kSave, false, 2, W>(p, cp, lc);
+    if (gsplit) return launch_f32c_h256<kF32cWavesH256Split, 4>(p, cp, mode, lc);
     // Up to one group per wave of the held-row form (8 waves): a step is one group's chain per wave, and the held row's loads all
     // go out at once where the ring (depth 4) requests them block by block — one 4-mic utterance 15.4 against 16.1 ms (l_*, n_*)
-    if (cp.groups_per_cluster <= kF32cWavesH256Split) {
-      constexpr int W8 = kF32cWavesH256Split;
-      if (mode == (kHas2 | kSum)) return launch_f32c_k<256, 16, 1, kHas2 | kSum, false, 2, W8>(p, cp, st);
-      if (mode == kHas2) return launch_f32c_k<256, 16, 1, kHas2, false, 2, W8>(p, cp, st);
-      if (mode == kSum) return launch_f32c_k<256, 16, 0, kSum, false, 2, W8>(p, cp, st);
-      return launch_f32c_k<256, 16, 0, 0, false, 2, W8>(p, cp, st);
-    }
-    if (mode == (kHas2 | kSum)) return launch_f32c_k<256, 16, 1, kHas2 | kSum, false, 2, W>(p, cp, st);
-    if (mode == kHas2) return launch_f32c_k<256, 16, 1, kHas2, false, 2, W>(p, cp, st);
+    if (cp.groups_per_cluster <= kF32cWavesH256Split) return launch_f32c_h256<kF32cWavesH256Split, 1>(p, cp, mode, lc);
     // (drift bounds of 1 / 3 / 4 / none measured at the 'M'-pairing size, 96 groups per cluster: 60.5 / 58.3 / 58.4 / 58.6 ms per
     //  layer against 58.5 with the default 2 — profiles/r05/)
-    if (mode == kSum) return launch_f32c_k<256, 16, 0, kSum, false, 2, W>(p, cp, st);
-    return launch_f32c_k<256, 16, 0, 0, false, 2, W>(p, cp, st);
+    return launch_f32c_h256<W, 1>(p, cp, mode, lc);
   }
   if (gsplit && !p.reserve) {
-    if (p.c0 == 4) return launch_f32c_k<128, 0, 1, 0, false, 2, kF32cWaves, 4>(p, cp, st);
-    if (mode == kSum) return launch_f32c_k<128, 16, 0, kSum, false, 2, kF32cWaves, 4>(p, cp, st);
-    return launch_f32c_k<128, 16, 0, 0, false, 2, kF32cWaves, 4>(p, cp, st);
+    if (p.c0 == 4) return launch_f32c_k<128, 0, 1, 0, false, 2, kF32cWaves, 4>(p, cp, lc);
+    if (mode == kSum) return launch_f32c_k<128, 16, 0, kSum, false, 2, kF32cWaves, 4>(p, cp, lc);
+    return launch_f32c_k<128, 16, 0, 0, false, 2, kF32cWaves, 4>(p, cp, lc);
   }
 #ifdef FNSSL_BUILD_ABLATE   // timing ablations (wrong results): make ABLATE=1 only
   if (const int abl = env_int("FNSSL_F32C_ABL", 1, 1023)) {
     p.ablate = abl;
-    if (mode == kSum) return launch_f32c_k<128, 16, 0, kSum, true>(p, cp, st);
-    if (p.c0 == 4) return launch_f32c_k<128, 0, 1, 0, true>(p, cp, st);
+    if (mode == kSum) return launch_f32c_k<128, 16, 0, kSum, true>(p, cp, lc);
+    if (p.c0 == 4) return launch_f32c_k<128, 0, 1, 0, true>(p, cp, lc);
   }
   p.ablate = 0;
 #endif
-  if (p.reserve) return p.c0 == 4 ? launch_f32c_k<128, 0, 1, kSave>(p, cp, st) : launch_f32c_k<128, 16, 0, kSave>(p, cp, st);
-  if (p.c0 == 4) return launch_f32c_k<128, 0, 1, 0>(p, cp, st);
+  if (p.reserve) return p.c0 == 4 ? launch_f32c_k<128, 0, 1, kSave>(p, cp, lc) : launch_f32c_k<128, 16, 0, kSave>(p, cp, lc);
+  if (p.c0 == 4) return launch_f32c_k<128, 0, 1, 0>(p, cp, lc);
   // (drift bounds of 1 / 3 / 4 group-steps and 12 waves per member were measured in round 3: +0.5 / 0.0 / +1.2 ms, +1.5 ms)
-  if (mode == kSum) return launch_f32c_k<128, 16, 0, kSum>(p, cp, st);
-  return launch_f32c_k<128, 16, 0, 0>(p, cp, st);
+  if (mode == kSum) return launch_f32c_k<128, 16, 0, kSum>(p, cp, lc);
+  return launch_f32c_k<128, 16, 0, 0>(p, cp, lc);
 }
 
 }  // namespace fnssl_lstm

@@ -212,17 +212,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 }
 
 template <int H, int NV0, int NS2>
-int launch_fwd2_k(const LstmParams& p, int nwg, hipStream_t st) {
-  if (p.dry) return FNSSL_OK;
+int launch_fwd2_k(const LstmParams& p, int nwg, const LaunchCtx& lc) {
   const size_t lds = (size_t)2 * 2 * NV0 * 1024 + (size_t)2 * 2 * (H / 16) * 1024;
-  auto k = lstm_fwd2_kernel<H, NV0, NS2>;
-  FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, dim3(nwg), dim3(256), lds, st, p);
-  FNSSL_CHECK_LAUNCH("lstm_fwd2_kernel");
-  return FNSSL_OK;
+  return enqueue(lc, Kernel{lstm_fwd2_kernel<H, NV0, NS2>, 256, lds, "lstm_fwd2_kernel"}, nwg, p);
 }
 
-extern template int launch_fwd2_k<256, 16, 0>(const LstmParams&, int, hipStream_t);
-extern template int launch_fwd2_k<256, 16, 1>(const LstmParams&, int, hipStream_t);
+extern template int launch_fwd2_k<256, 16, 0>(const LstmParams&, int, const LaunchCtx&);
+extern template int launch_fwd2_k<256, 16, 1>(const LstmParams&, int, const LaunchCtx&);
 
 }  // namespace fnssl_lstm

@@ -2,5 +2,5 @@
 #include "lstm_kernel.h"
 
 namespace fnssl_lstm {
-template int launch_h<256>(int, const LstmParams&, int, int, hipStream_t);
+template int launch_h<256>(int, const LstmParams&, int, int, const LaunchCtx&);
 }  // namespace fnssl_lstm

@@ -4,7 +4,7 @@
 #include "lstm_kernel.h"
 
 namespace fnssl_lstm {
-template int launch_h<16>(int, const LstmParams&, int, int, hipStream_t);
-template int launch_h<32>(int, const LstmParams&, int, int, hipStream_t);
-template int launch_h<64>(int, const LstmParams&, int, int, hipStream_t);
+template int launch_h<16>(int, const LstmParams&, int, int, const LaunchCtx&);
+template int launch_h<32>(int, const LstmParams&, int, int, const LaunchCtx&);
+template int launch_h<64>(int, const LstmParams&, int, int, const LaunchCtx&);
 }  // namespace fnssl_lstm

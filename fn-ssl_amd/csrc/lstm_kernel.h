@@ -10,6 +10,7 @@
 
 #include "common.h"
 #include "tuning.h"
+#include "lstm_host.h"
 
 // HIP's __fadd_rn/__fmul_rn inline to plain fadd/fmul, which clang would still contract into
 // fma; every fused multiply-add in this file is written explicitly (__fmaf_rn), so turn the
@@ -47,7 +48,6 @@ struct LstmParams {
   // *guard != 0, i.e. only if the cluster kernel gave up on a hand-off; block 0 then counts the layer in *fallback_count.
   const unsigned* guard = nullptr;
   unsigned* fallback_count = nullptr;
-  int dry = 0;    // host only (fnssl_lstm_plan): the launch templates return without launching
 };
 
 // first statement of every kernel that can be a guarded fallback (uniform for the whole grid: nobody reaches a barrier)
@@ -87,11 +87,6 @@ template <int NS>
 __device__ __forceinline__ const char* dhdc_record(const float* scratch, int ntasks, int dir, int slot) {
   return reinterpret_cast<const char*>(scratch) + ((size_t)dir * (ntasks + kSpareTasks) + slot) * (2 * NS * 1024);
 }
-// host: one region of a workspace layout (lstm.hip, lstm_train.hip), in bytes from the workspace's start
-struct WsRegion {
-  size_t off, bytes;
-  size_t end() const { return off + bytes; }
-};
 
 // Reserve layout (written by the kSave forward, read by lstm_bwd_kernel): lane-private 1 KiB records
 //   reserve[(((dir * ntasks + group) * nsteps + t) * NS + slice) * 5 + {i, f, g, o, c}][lane] (float4)
@@ -638,33 +633,28 @@ __global__ void __launch_bounds__(NW * 64, (NW == 4 ? 3 : 1)) lstm_rec_kernel(co
 
 // ---- launcher ----------------------------------------------------------------
 template <int H, int NW, int M, int WMODE, int MODE, bool ABL = false, int SPLIT = 1>
-int launch_k(const LstmParams& p, int nwg, hipStream_t st) {
-  if (p.dry) return FNSSL_OK;   // fnssl_lstm_plan: report the family, launch nothing
+int launch_k(const LstmParams& p, int nwg, const LaunchCtx& lc) {
   const size_t lds = WMODE ? (size_t)2 * p.chq * SPLIT * 4096 : 0;
-  auto k = lstm_rec_kernel<H, NW, M, WMODE, MODE, ABL, SPLIT>;
-  if (lds > 48 * 1024)
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-  hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, st, p);
-  FNSSL_CHECK_LAUNCH("lstm_rec_kernel");
-  return FNSSL_OK;
+  return enqueue(lc, Kernel{lstm_rec_kernel<H, NW, M, WMODE, MODE, ABL, SPLIT>, NW * 64, lds, "lstm_rec_kernel"}, nwg, p);
 }
 
-template <int H, int NW, int M, int WMODE>
-int launch_t(const LstmParams& p, int mode, int nwg, hipStream_t st) {
+// SPLIT > 1: the split geometries for launches with fewer 16-sequence groups than SIMDs (single utterances, streaming
+// chunks): 2 waves per group in 4-wave workgroups, or 4 waves per group in 8-wave workgroups
+template <int H, int NW, int M, int WMODE, int SPLIT = 1>
+int launch_t(const LstmParams& p, int mode, int nwg, const LaunchCtx& lc) {
   switch (mode) {
-    case 0: return launch_k<H, NW, M, WMODE, 0>(p, nwg, st);
-    case kHas1: return launch_k<H, NW, M, WMODE, kHas1>(p, nwg, st);
-    case kHas2: return launch_k<H, NW, M, WMODE, kHas2>(p, nwg, st);
+    case 0: return launch_k<H, NW, M, WMODE, 0, false, SPLIT>(p, nwg, lc);
+    case kHas1: return launch_k<H, NW, M, WMODE, kHas1, false, SPLIT>(p, nwg, lc);
+    case kHas2: return launch_k<H, NW, M, WMODE, kHas2, false, SPLIT>(p, nwg, lc);
     case kSum:
-      if constexpr (H >= 128 && WMODE == 1 && ((NW == 12 && M == 4) || (NW == 16 && M == 2))) {
+      if constexpr (SPLIT == 1 && H >= 128 && WMODE == 1 && ((NW == 12 && M == 4) || (NW == 16 && M == 2))) {
 #ifdef FNSSL_BUILD_ABLATE
-        if (p.ablate) return launch_k<H, NW, M, WMODE, kSum, true>(p, nwg, st);
+        if (p.ablate) return launch_k<H, NW, M, WMODE, kSum, true>(p, nwg, lc);
 #endif
       }
-      return launch_k<H, NW, M, WMODE, kSum>(p, nwg, st);
-    case kHas2 | kSum: return launch_k<H, NW, M, WMODE, kHas2 | kSum>(p, nwg, st);
-    case kHas1 | kHas2: return launch_k<H, NW, M, WMODE, kHas1 | kHas2>(p, nwg, st);
+      return launch_k<H, NW, M, WMODE, kSum, false, SPLIT>(p, nwg, lc);
+    case kHas2 | kSum: return launch_k<H, NW, M, WMODE, kHas2 | kSum, false, SPLIT>(p, nwg, lc);
+    case kHas1 | kHas2: return launch_k<H, NW, M, WMODE, kHas1 | kHas2, false, SPLIT>(p, nwg, lc);
   }
   fnssl::set_error("lstm: input combination %d not built (src1 together with out_sum)", mode);
   return FNSSL_E_INVALID;
@@ -742,44 +732,28 @@ inline void choose_chunk(int qps, const Variant& v, int& chq, int& pad, int spli
   }
 }
 
-// Split geometries for launches with fewer 16-sequence groups than SIMDs (single utterances, streaming
-// chunks): 2 waves per group in 4-wave workgroups, or 4 waves per group in 8-wave workgroups.
-template <int H, int NW, int M, int SPLIT>
-int launch_split_t(const LstmParams& p, int mode, int nwg, hipStream_t st) {
-  switch (mode) {
-    case 0: return launch_k<H, NW, M, 1, 0, false, SPLIT>(p, nwg, st);
-    case kHas1: return launch_k<H, NW, M, 1, kHas1, false, SPLIT>(p, nwg, st);
-    case kHas2: return launch_k<H, NW, M, 1, kHas2, false, SPLIT>(p, nwg, st);
-    case kSum: return launch_k<H, NW, M, 1, kSum, false, SPLIT>(p, nwg, st);
-    case kHas2 | kSum: return launch_k<H, NW, M, 1, kHas2 | kSum, false, SPLIT>(p, nwg, st);
-    case kHas1 | kHas2: return launch_k<H, NW, M, 1, kHas1 | kHas2, false, SPLIT>(p, nwg, st);
-  }
-  fnssl::set_error("lstm: input combination %d not built (src1 together with out_sum)", mode);
-  return FNSSL_E_INVALID;
-}
-
 template <int H>
-int launch_split_h(int split, const LstmParams& p, int mode, int nwg, hipStream_t st) {
-  if (split == 2) return launch_split_t<H, 4, 4, 2>(p, mode, nwg, st);
-  if (split == 4) return launch_split_t<H, 8, 8, 4>(p, mode, nwg, st);
+int launch_split_h(int split, const LstmParams& p, int mode, int nwg, const LaunchCtx& lc) {
+  if (split == 2) return launch_t<H, 4, 4, 1, 2>(p, mode, nwg, lc);
+  if (split == 4) return launch_t<H, 8, 8, 1, 4>(p, mode, nwg, lc);
   fnssl::set_error("lstm: unsupported split %d", split);
   return FNSSL_E_INVALID;
 }
 
 template <int H>
-int launch_h(int variant, const LstmParams& p, int mode, int nwg, hipStream_t st) {
+int launch_h(int variant, const LstmParams& p, int mode, int nwg, const LaunchCtx& lc) {
   switch (variant) {
-    case 1: return launch_t<H, 4, 1, 0>(p, mode, nwg, st);
-    case 2: return launch_t<H, 4, 4, 1>(p, mode, nwg, st);
-    case 3: return launch_t<H, 8, 4, 1>(p, mode, nwg, st);
-    case 4: return launch_t<H, 12, 4, 1>(p, mode, nwg, st);
-    case 5: return launch_t<H, 16, 2, 1>(p, mode, nwg, st);
-    case 6: return launch_t<H, 8, 1, 0>(p, mode, nwg, st);
-    case 7: return launch_t<H, 12, 2, 1>(p, mode, nwg, st);
-    case 8: return launch_t<H, 16, 4, 1>(p, mode, nwg, st);
-    case 9: return launch_t<H, 13, 2, 1>(p, mode, nwg, st);
-    case 10: return launch_t<H, 14, 2, 1>(p, mode, nwg, st);
-    case 11: return launch_t<H, 15, 2, 1>(p, mode, nwg, st);
+    case 1: return launch_t<H, 4, 1, 0>(p, mode, nwg, lc);
+    case 2: return launch_t<H, 4, 4, 1>(p, mode, nwg, lc);
+    case 3: return launch_t<H, 8, 4, 1>(p, mode, nwg, lc);
+    case 4: return launch_t<H, 12, 4, 1>(p, mode, nwg, lc);
+    case 5: return launch_t<H, 16, 2, 1>(p, mode, nwg, lc);
+    case 6: return launch_t<H, 8, 1, 0>(p, mode, nwg, lc);
+    case 7: return launch_t<H, 12, 2, 1>(p, mode, nwg, lc);
+    case 8: return launch_t<H, 16, 4, 1>(p, mode, nwg, lc);
+    case 9: return launch_t<H, 13, 2, 1>(p, mode, nwg, lc);
+    case 10: return launch_t<H, 14, 2, 1>(p, mode, nwg, lc);
+    case 11: return launch_t<H, 15, 2, 1>(p, mode, nwg, lc);
   }
   fnssl::set_error("lstm: unknown variant %d", variant);
   return FNSSL_E_INVALID;

@@ -4,6 +4,6 @@
 #include "lstm_kernel.h"
 
 namespace fnssl_lstm {
-template int launch_split_h<128>(int, const LstmParams&, int, int, hipStream_t);
-template int launch_split_h<256>(int, const LstmParams&, int, int, hipStream_t);
+template int launch_split_h<128>(int, const LstmParams&, int, int, const LaunchCtx&);
+template int launch_split_h<256>(int, const LstmParams&, int, int, const LaunchCtx&);
 }  // namespace fnssl_lstm

@@ -292,20 +292,14 @@ __global__ void __launch_bounds__(NW * 64, (NW == 4 && !DIRECT ? 3 : 1)) lstm_sp
 
 template <int H, int NW, int M, int SPLIT, int NV0, int NS0, int NS2, int CHQ, int PAD, int MODE, bool DIRECT = false,
           int NV2 = 0>
-int launch_split_static_k(const LstmParams& p, int nwg, hipStream_t st) {
-  if (p.dry) return FNSSL_OK;   // fnssl_lstm_plan: report the family, launch nothing
+int launch_split_static_k(const LstmParams& p, int nwg, const LaunchCtx& lc) {
   const size_t lds = DIRECT ? 0 : (size_t)2 * CHQ * SPLIT * 4096;
   static_assert(2 * CHQ * SPLIT * 4096 <= 160 * 1024, "ring does not fit the LDS");
   auto k = lstm_split_static_kernel<H, NW, M, SPLIT, NV0, NS0, NS2, CHQ, PAD, MODE, DIRECT, NV2>;
-  if (lds > 48 * 1024)
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-  hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, st, p);
-  FNSSL_CHECK_LAUNCH("lstm_split_static_kernel");
-  return FNSSL_OK;
+  return enqueue(lc, Kernel{k, NW * 64, lds, "lstm_split_static_kernel"}, nwg, p);
 }
 
 // kNoStatic when (H, nw, split, c0, c2, mode, chunk cap) has no instantiation; max_chq = LDS budget in super-quads
-int launch_split_static(const LstmParams& p, int H, int nw, int split, int mode, int max_chq, int nwg, hipStream_t st);
+int launch_split_static(const LstmParams& p, int H, int nw, int split, int mode, int max_chq, int nwg, const LaunchCtx& lc);
 
 }  // namespace fnssl_lstm

@@ -4,15 +4,15 @@
 
 namespace fnssl_lstm {
 
-int launch_split_static_h256(const LstmParams& p, int H, int nw, int split, int mode, int max_chq, int nwg, hipStream_t st);
+int launch_split_static_h256(const LstmParams& p, int H, int nw, int split, int mode, int max_chq, int nwg, const LaunchCtx& lc);
 
 // (H, NW, M, SPLIT, NV0, NS0, NS2, CHQ, PAD): c0 = 16 NV0 + 4 NS0, c2 = 4 NS2; kSave always, kHas2 with NS2
 #define TRYS(H_, NW_, M_, S_, NV0_, NS0_, NS2_, CHQ_, PAD_)                                                        \
   if (H == H_ && nw == NW_ && split == S_ && p.c0 == 16 * NV0_ + 4 * NS0_ && p.c2 == 4 * NS2_ && CHQ_ <= max_chq &&  \
       mode == (kSave | (NS2_ ? kHas2 : 0)))                                                                          \
-    return launch_split_static_k<H_, NW_, M_, S_, NV0_, NS0_, NS2_, CHQ_, PAD_, kSave | (NS2_ ? kHas2 : 0)>(p, nwg, st);
+    return launch_split_static_k<H_, NW_, M_, S_, NV0_, NS0_, NS2_, CHQ_, PAD_, kSave | (NS2_ ? kHas2 : 0)>(p, nwg, lc);
 
-int launch_split_static_h128(const LstmParams& p, int H, int nw, int split, int mode, int max_chq, int nwg, hipStream_t st) {
+int launch_split_static_h128(const LstmParams& p, int H, int nw, int split, int mode, int max_chq, int nwg, const LaunchCtx& lc) {
   if (max_chq <= 0) max_chq = 1 << 20;
   // H = 128: full-band (25 quads; block 1: 10) and the offline narrow-band layers (25 / 26)
   TRYS(128, 4, 4, 2, 16, 0, 0, 2, 1)
@@ -24,9 +24,9 @@ int launch_split_static_h128(const LstmParams& p, int H, int nw, int split, int 
   return kNoStatic;
 }
 
-int launch_split_static(const LstmParams& p, int H, int nw, int split, int mode, int max_chq, int nwg, hipStream_t st) {
-  if (H == 128) return launch_split_static_h128(p, H, nw, split, mode, max_chq, nwg, st);
-  if (H == 256) return launch_split_static_h256(p, H, nw, split, mode, max_chq, nwg, st);
+int launch_split_static(const LstmParams& p, int H, int nw, int split, int mode, int max_chq, int nwg, const LaunchCtx& lc) {
+  if (H == 128) return launch_split_static_h128(p, H, nw, split, mode, max_chq, nwg, lc);
+  if (H == 256) return launch_split_static_h256(p, H, nw, split, mode, max_chq, nwg, lc);
   return kNoStatic;
 }
 

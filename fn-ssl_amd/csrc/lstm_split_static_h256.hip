@@ -9,20 +9,20 @@ namespace fnssl_lstm {
 #define TRYS(H_, NW_, M_, S_, NV0_, NS0_, NS2_, CHQ_, PAD_)                                                        \
   if (H == H_ && nw == NW_ && split == S_ && p.c0 == 16 * NV0_ + 4 * NS0_ && p.c2 == 4 * NS2_ && CHQ_ <= max_chq &&  \
       mode == (kSave | (NS2_ ? kHas2 : 0)))                                                                          \
-    return launch_split_static_k<H_, NW_, M_, S_, NV0_, NS0_, NS2_, CHQ_, PAD_, kSave | (NS2_ ? kHas2 : 0)>(p, nwg, st);
+    return launch_split_static_k<H_, NW_, M_, S_, NV0_, NS0_, NS2_, CHQ_, PAD_, kSave | (NS2_ ? kHas2 : 0)>(p, nwg, lc);
 
 // ring-free variants (4 waves per group): weights straight from L2 through the register pipeline
 #define TRYD(H_, NW_, S_, NV0_, NS0_, NS2_)                                                                        \
   if (H == H_ && nw == NW_ && split == S_ && p.c0 == 16 * NV0_ + 4 * NS0_ && p.c2 == 4 * NS2_ &&                     \
       mode == (kSave | (NS2_ ? kHas2 : 0)))                                                                          \
-    return launch_split_static_k<H_, NW_, 4, S_, NV0_, NS0_, NS2_, 1, 0, kSave | (NS2_ ? kHas2 : 0), true>(p, nwg, st);
+    return launch_split_static_k<H_, NW_, 4, S_, NV0_, NS0_, NS2_, 1, 0, kSave | (NS2_ ? kHas2 : 0), true>(p, nwg, lc);
 
 // inference (fused forward: residual output for the next layer), 4 waves per group, ring-free
 #define TRYI(NS2_, MODE_)                                                                                   \
   if (H == 256 && nw == 8 && split == 4 && p.c0 == 256 && p.c2 == 4 * NS2_ && mode == (MODE_))              \
-    return launch_split_static_k<256, 8, 4, 4, 16, 0, NS2_, 1, 0, MODE_, true>(p, nwg, st);
+    return launch_split_static_k<256, 8, 4, 4, 16, 0, NS2_, 1, 0, MODE_, true>(p, nwg, lc);
 
-int launch_split_static_h256(const LstmParams& p, int H, int nw, int split, int mode, int max_chq, int nwg, hipStream_t st) {
+int launch_split_static_h256(const LstmParams& p, int H, int nw, int split, int mode, int max_chq, int nwg, const LaunchCtx& lc) {
   if (max_chq <= 0) max_chq = 1 << 20;
   if (!fnssl::tune(FNSSL_TUNE_FWD_RING)) {
     TRYI(0, kSum)
@@ -31,7 +31,7 @@ int launch_split_static_h256(const LstmParams& p, int H, int nw, int split, int 
     TRYI(1, kHas2)
     // IPDnet narrow-band: [256 | 16-channel concatenated block]
     if (H == 256 && nw == 8 && split == 4 && p.c0 == 256 && p.c2 == 16 && mode == kHas2)
-      return launch_split_static_k<256, 8, 4, 4, 16, 0, 0, 1, 0, kHas2, true, 1>(p, nwg, st);
+      return launch_split_static_k<256, 8, 4, 4, 16, 0, 0, 1, 0, kHas2, true, 1>(p, nwg, lc);
     TRYD(256, 8, 4, 16, 0, 0)
     TRYD(256, 8, 4, 16, 0, 1)
   }

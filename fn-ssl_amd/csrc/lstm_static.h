@@ -270,53 +270,17 @@ __global__ void __launch_bounds__(NW * 64) lstm_static_kernel(const LstmParams p
 
 template <int H, int NW, int M, int NV0, int NS0, int NS2, int CHQ, int PAD, int MODE, bool ABL = false, int XD = 4,
           int NV2 = 0>
-int launch_static_k(const LstmParams& p, int nwg, hipStream_t st) {
-  if (p.dry) return FNSSL_OK;   // fnssl_lstm_plan: report the family, launch nothing
+int launch_static_k(const LstmParams& p, int nwg, const LaunchCtx& lc) {
   const size_t lds = (size_t)2 * CHQ * 4096;
   static_assert(2 * CHQ * 4096 <= 160 * 1024, "ring does not fit the LDS");
-  auto k = lstm_static_kernel<H, NW, M, NV0, NS0, NS2, CHQ, PAD, MODE, ABL, XD, NV2>;
-  if (lds > 48 * 1024)
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-  hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, st, p);
-  FNSSL_CHECK_LAUNCH("lstm_static_kernel");
-  return FNSSL_OK;
+  return enqueue(lc, Kernel{lstm_static_kernel<H, NW, M, NV0, NS0, NS2, CHQ, PAD, MODE, ABL, XD, NV2>, NW * 64, lds, "lstm_static_kernel"}, nwg, p);
 }
 
-// Return kNoStatic when no specialisation exists for (c0, c2, mode, NW).
-constexpr int kNoStatic = -100;
-// Returned by the cluster-kernel launchers when the device cannot hold every member workgroup at once (occupancy
-// query): the caller runs the per-wave / pair-split kernels instead, unguarded.
-constexpr int kNoCluster = -101;
-
-// Knobs of the cluster kernels' bounded waits (fnssl_tuning): CLUSTER_SPIN_LIMIT (spins before a wave gives up),
-// CLUSTER_TEST_STALL = m + 1 (fault injection: member m of cluster 0 exits at once, as if it never became resident).
-inline unsigned cluster_spin_limit() {
-  const int v = fnssl::tune(FNSSL_TUNE_CLUSTER_SPIN_LIMIT, 1, 1 << 30);
-  return v ? (unsigned)v : (1u << 20);
-}
-// compute units the cluster kernels may count on: the device's minus what the caller keeps busy elsewhere (RESERVED_CUS:
-// RCCL's all-reduce kernels under an overlapped backward), in whole XCD-uniform steps (a multiple of 8 CUs)
-inline int cluster_cus() {
-  const int ncu = fnssl::device_cus();
-  int r = fnssl::tune(FNSSL_TUNE_RESERVED_CUS, 1, ncu);
-  r = (r + 7) / 8 * 8;
-  return r >= ncu ? 0 : ncu - r;
-}
-// blocks the device can hold at once for this kernel (occupancy query x CUs) >= grid?  One query per call: cheap (host only).
-inline bool cluster_grid_fits(const void* kernel, int threads, size_t lds, int grid) {
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return (long long)per_cu * cluster_cus() >= grid;
-}
-inline int cluster_test_stall() { return fnssl::tune(FNSSL_TUNE_CLUSTER_TEST_STALL, 1, 1 << 20) - 1; }
-int launch_static_h128(const LstmParams& p, int mode, int NW, int nwg, hipStream_t st);
-int launch_static_h256(const LstmParams& p, int mode, int NW, int nwg, hipStream_t st);
-int launch_static3_h256(const LstmParams& p, int mode, int nwg, hipStream_t st);   // lstm_static3.h, pair-interleaved stream
-int launch_static4_h256(const LstmParams& p, int mode, int nwg, hipStream_t st);   // lstm_static4.h, quad-interleaved stream
-int launch_static_ipdnet(const LstmParams& p, int mode, int H, int NW, int nwg, hipStream_t st);
+// Each returns kNoStatic when no specialisation exists for (c0, c2, mode, NW).
+int launch_static_h128(const LstmParams& p, int mode, int NW, int nwg, const LaunchCtx& lc);
+int launch_static_h256(const LstmParams& p, int mode, int NW, int nwg, const LaunchCtx& lc);
+int launch_static3_h256(const LstmParams& p, int mode, int nwg, const LaunchCtx& lc);   // lstm_static3.h, pair-interleaved stream
+int launch_static4_h256(const LstmParams& p, int mode, int nwg, const LaunchCtx& lc);   // lstm_static4.h, quad-interleaved stream
+int launch_static_ipdnet(const LstmParams& p, int mode, int H, int NW, int nwg, const LaunchCtx& lc);
 
 }  // namespace fnssl_lstm

@@ -254,16 +254,10 @@ __global__ void __launch_bounds__(NW * 64) lstm_static3_kernel(const LstmParams 
 }
 
 template <int H, int NW, int M, int NV0, int NS2, int CHQ, int PAD, int MODE, int XD = 4>
-int launch_static3_k(const LstmParams& p, int nwg, hipStream_t st) {
-  if (p.dry) return FNSSL_OK;   // fnssl_lstm_plan: report the family, launch nothing
+int launch_static3_k(const LstmParams& p, int nwg, const LaunchCtx& lc) {
   const size_t lds = (size_t)2 * CHQ * 8192;
   static_assert(2 * CHQ * 8192 <= 160 * 1024, "ring does not fit the LDS");
-  auto k = lstm_static3_kernel<H, NW, M, NV0, NS2, CHQ, PAD, MODE, XD>;
-  if (lds > 48 * 1024)
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, st, p);
-  FNSSL_CHECK_LAUNCH("lstm_static3_kernel");
-  return FNSSL_OK;
+  return enqueue(lc, Kernel{lstm_static3_kernel<H, NW, M, NV0, NS2, CHQ, PAD, MODE, XD>, NW * 64, lds, "lstm_static3_kernel"}, nwg, p);
 }
 
 }  // namespace fnssl_lstm

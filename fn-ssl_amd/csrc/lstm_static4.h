@@ -303,16 +303,10 @@ __global__ void __launch_bounds__(NW * 64) lstm_static4_kernel(const LstmParams 
 }
 
 template <int H, int NW, int NV0, int NS2, int CHQ, int PAD, int MODE, int XD = 4, bool PF4 = false>
-int launch_static4_k(const LstmParams& p, int nwg, hipStream_t st) {
-  if (p.dry) return FNSSL_OK;   // fnssl_lstm_plan: report the family, launch nothing
+int launch_static4_k(const LstmParams& p, int nwg, const LaunchCtx& lc) {
   const size_t lds = (size_t)2 * CHQ * 16384;
   static_assert(2 * CHQ * 16384 <= 160 * 1024, "ring does not fit the LDS");
-  auto k = lstm_static4_kernel<H, NW, NV0, NS2, CHQ, PAD, MODE, XD, PF4>;
-  if (lds > 48 * 1024)
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, st, p);
-  FNSSL_CHECK_LAUNCH("lstm_static4_kernel");
-  return FNSSL_OK;
+  return enqueue(lc, Kernel{lstm_static4_kernel<H, NW, NV0, NS2, CHQ, PAD, MODE, XD, PF4>, NW * 64, lds, "lstm_static4_kernel"}, nwg, p);
 }
 
 }  // namespace fnssl_lstm

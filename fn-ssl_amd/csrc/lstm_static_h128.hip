@@ -6,9 +6,9 @@ namespace fnssl_lstm {
 
 #define TRY(NW_, M_, NV0_, NS0_, NS2_, CHQ_, PAD_, MODE_)                                              \
   if (NW == NW_ && p.c0 == 16 * NV0_ + 4 * NS0_ && p.c2 == 4 * NS2_ && NS2_ < 4 && mode == (MODE_))                  \
-    return launch_static_k<128, NW_, M_, NV0_, NS0_, NS2_, CHQ_, PAD_, MODE_>(p, nwg, st);
+    return launch_static_k<128, NW_, M_, NV0_, NS0_, NS2_, CHQ_, PAD_, MODE_>(p, nwg, lc);
 
-int launch_static_h128(const LstmParams& p, int mode, int NW, int nwg, hipStream_t st) {
+int launch_static_h128(const LstmParams& p, int mode, int NW, int nwg, const LaunchCtx& lc) {
   // block 1 full-band: 4 input channels, 10 quads per slice
   TRY(16, 4, 0, 1, 0, 10, 0, 0)
   TRY(15, 4, 0, 1, 0, 10, 0, 0)
@@ -17,7 +17,7 @@ int launch_static_h128(const LstmParams& p, int mode, int NW, int nwg, hipStream
   // blocks 2/3 full-band (and offline narrow-band 2/3): 256 channels, 25 quads (+3 pad = 4 x 7)
 #ifdef FNSSL_BUILD_ABLATE   // timing-ablation twin (wrong results by construction): only in `make ABLATE=1` builds
   if (p.ablate && NW == 16 && p.c0 == 256 && p.c2 == 0 && mode == kSum)
-    return launch_static_k<128, 16, 2, 16, 0, 0, 7, 3, kSum, true>(p, nwg, st);
+    return launch_static_k<128, 16, 2, 16, 0, 0, 7, 3, kSum, true>(p, nwg, lc);
 #endif
   // 26 virtual quads = 2 chunks of 13
   TRY(16, 4, 16, 0, 0, 13, 1, kSum)

@@ -39,7 +39,6 @@ struct BwdParams {
   // guarded fallback launch behind lstm_bwdc_kernel (lstm_bwdc.h): runs only if *guard != 0 (LstmParams.guard)
   const unsigned* guard = nullptr;
   unsigned* fallback_count = nullptr;   // optional device counter: block 0 of a guarded launch that does run counts the call
-  int dry = 0;                 // host only (fnssl_lstm_backward_plan): no launch
 };
 
 inline int bwd_co_pad(int c0g, int H) { return (c0g + H + 63) / 64 * 64; }
@@ -270,37 +269,30 @@ __global__ void __launch_bounds__(NW * 64) lstm_bwd_kernel(const BwdParams p) {
 }
 
 template <int H, int NW, int M, int SPLIT = 1, bool DIRECT = false>
-int launch_bwd_k(const BwdParams& p, int nwg, hipStream_t st) {
+int launch_bwd_k(const BwdParams& p, int nwg, const LaunchCtx& lc) {
   const size_t lds = DIRECT ? 0 : (size_t)2 * p.chq * SPLIT * 4096;
-  auto k = lstm_bwd_kernel<H, NW, M, SPLIT, DIRECT>;
-  if (p.dry) return FNSSL_OK;
-  if (lds > 48 * 1024)
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds));
-  hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, st, p);
-  FNSSL_CHECK_LAUNCH("lstm_bwd_kernel");
-  return FNSSL_OK;
+  return enqueue(lc, Kernel{lstm_bwd_kernel<H, NW, M, SPLIT, DIRECT>, NW * 64, lds, "lstm_bwd_kernel"}, nwg, p);
 }
 
 template <int H>
-int launch_bwd(int nw, int split, const BwdParams& p, int nwg, hipStream_t st) {
+int launch_bwd(int nw, int split, const BwdParams& p, int nwg, const LaunchCtx& lc) {
   if (split == 1) {
     switch (nw) {
-      case 4: return launch_bwd_k<H, 4, 4>(p, nwg, st);
-      case 8: return launch_bwd_k<H, 8, 4>(p, nwg, st);
-      case 12: return launch_bwd_k<H, 12, 4>(p, nwg, st);
+      case 4: return launch_bwd_k<H, 4, 4>(p, nwg, lc);
+      case 8: return launch_bwd_k<H, 8, 4>(p, nwg, lc);
+      case 12: return launch_bwd_k<H, 12, 4>(p, nwg, lc);
     }
   } else if (split == 4 && !fnssl::tune(FNSSL_TUNE_BWD_RING)) {
     // 4 waves per group: weights straight from L2 (narrow-band BPTT 31.8 -> 26.0 ms at config 4; with 2 waves
     // per group the LDS ring is as fast, r01 f_train_layers)
-    if (nw == 4) return launch_bwd_k<H, 4, 1, 4, true>(p, nwg, st);
-    if (nw == 8) return launch_bwd_k<H, 8, 1, 4, true>(p, nwg, st);
+    if (nw == 4) return launch_bwd_k<H, 4, 1, 4, true>(p, nwg, lc);
+    if (nw == 8) return launch_bwd_k<H, 8, 1, 4, true>(p, nwg, lc);
   } else if (split == 2 && nw == 4) {
-    return launch_bwd_k<H, 4, 8, 2>(p, nwg, st);
+    return launch_bwd_k<H, 4, 8, 2>(p, nwg, lc);
   } else if (split == 4 && nw == 4) {
-    return launch_bwd_k<H, 4, 8, 4>(p, nwg, st);
+    return launch_bwd_k<H, 4, 8, 4>(p, nwg, lc);
   } else if (split == 4 && nw == 8) {
-    return launch_bwd_k<H, 8, 8, 4>(p, nwg, st);
+    return launch_bwd_k<H, 8, 8, 4>(p, nwg, lc);
   }
   fnssl::set_error("lstm_backward: unsupported geometry (%d waves, split %d)", nw, split);
   return FNSSL_E_INVALID;
@@ -309,33 +301,33 @@ int launch_bwd(int nw, int split, const BwdParams& p, int nwg, hipStream_t st) {
 // (nw, split): 4 / 8 / 12 waves per workgroup with one group per wave, or the split geometries for launches
 // with fewer wave tasks than SIMDs: 2 or 4 waves per 16-sequence group (8 ring records staged per wave)
 template <int H, int MODE>
-int launch_save_m(int nw, int split, const LstmParams& p, int nwg, hipStream_t st) {
+int launch_save_m(int nw, int split, const LstmParams& p, int nwg, const LaunchCtx& lc) {
   if (split == 1) {
     switch (nw) {
-      case 4: return launch_k<H, 4, 4, 1, MODE>(p, nwg, st);
-      case 8: return launch_k<H, 8, 4, 1, MODE>(p, nwg, st);
-      case 12: return launch_k<H, 12, 4, 1, MODE>(p, nwg, st);
+      case 4: return launch_k<H, 4, 4, 1, MODE>(p, nwg, lc);
+      case 8: return launch_k<H, 8, 4, 1, MODE>(p, nwg, lc);
+      case 12: return launch_k<H, 12, 4, 1, MODE>(p, nwg, lc);
     }
   } else if (split == 2 && nw == 4) {
-    return launch_k<H, 4, 4, 1, MODE, false, 2>(p, nwg, st);
+    return launch_k<H, 4, 4, 1, MODE, false, 2>(p, nwg, lc);
   } else if (split == 4 && nw == 4) {
-    return launch_k<H, 4, 4, 1, MODE, false, 4>(p, nwg, st);
+    return launch_k<H, 4, 4, 1, MODE, false, 4>(p, nwg, lc);
   } else if (split == 4 && nw == 8) {
-    return launch_k<H, 8, 8, 1, MODE, false, 4>(p, nwg, st);
+    return launch_k<H, 8, 8, 1, MODE, false, 4>(p, nwg, lc);
   }
   fnssl::set_error("lstm_forward (training): unsupported geometry (%d waves, split %d)", nw, split);
   return FNSSL_E_INVALID;
 }
 
 template <int H>
-int launch_save(int nw, int split, const LstmParams& p, int mode, int nwg, hipStream_t st) {
-  return (mode & kHas2) ? launch_save_m<H, kSave | kHas2>(nw, split, p, nwg, st)
-                        : launch_save_m<H, kSave>(nw, split, p, nwg, st);
+int launch_save(int nw, int split, const LstmParams& p, int mode, int nwg, const LaunchCtx& lc) {
+  return (mode & kHas2) ? launch_save_m<H, kSave | kHas2>(nw, split, p, nwg, lc)
+                        : launch_save_m<H, kSave>(nw, split, p, nwg, lc);
 }
 
-extern template int launch_bwd<128>(int, int, const BwdParams&, int, hipStream_t);
-extern template int launch_bwd<256>(int, int, const BwdParams&, int, hipStream_t);
-extern template int launch_save<128>(int, int, const LstmParams&, int, int, hipStream_t);
-extern template int launch_save<256>(int, int, const LstmParams&, int, int, hipStream_t);
+extern template int launch_bwd<128>(int, int, const BwdParams&, int, const LaunchCtx&);
+extern template int launch_bwd<256>(int, int, const BwdParams&, int, const LaunchCtx&);
+extern template int launch_save<128>(int, int, const LstmParams&, int, int, const LaunchCtx&);
+extern template int launch_save<256>(int, int, const LstmParams&, int, int, const LaunchCtx&);
 
 }  // namespace fnssl_lstm

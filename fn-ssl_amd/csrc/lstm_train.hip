@@ -18,7 +18,7 @@ namespace fnssl_lstm {
 using fnssl::device_cus;
 
 bool bwdc_handles(const BwdParams& p, int H, BwdClusterParams& cp);                        // lstm_bwdc.hip
-int backward_cluster(const BwdParams& p, BwdClusterParams cp, void* ws, size_t ws_bytes, hipStream_t st);
+int backward_cluster(const BwdParams& p, BwdClusterParams cp, void* ws, size_t ws_bytes, const LaunchCtx& lc);
 
 struct Geometry {
   int nw, split, t0, t1;
@@ -74,7 +74,7 @@ static int plan_rounds(int tasks, int ndir, int max_split, int split4_groups_per
 }
 
 // Training forward: called by fnssl_lstm_forward when the descriptor carries a reserve buffer.
-int forward_save(LstmParams p, int H, int mode, hipStream_t st) {
+int forward_save(LstmParams p, int H, int mode, const LaunchCtx& lc) {
   return plan_rounds(p.ntasks, p.ndir, 4, H == 256 ? 6 : 2, [&](const Geometry& gm) {
     p.task0 = gm.t0;
     p.task1 = gm.t1;
@@ -87,18 +87,18 @@ int forward_save(LstmParams p, int H, int mode, hipStream_t st) {
       if ((!has2 && p.quads_per_slice == 33) || (has2 && p.c2 == 4 && p.quads_per_slice == 34)) {
         p.wgs_per_dir = (gm.t1 - gm.t0 + 1) / 2;
         const int nwg2 = p.wgs_per_dir * p.ndir;
-        return has2 ? launch_fwd2_k<256, 16, 1>(p, nwg2, st) : launch_fwd2_k<256, 16, 0>(p, nwg2, st);
+        return has2 ? launch_fwd2_k<256, 16, 1>(p, nwg2, lc) : launch_fwd2_k<256, 16, 0>(p, nwg2, lc);
       }
     }
     const Variant vr{gm.nw, (gm.split > 1 && gm.nw == 8) ? 8 : 4, 1};   // staging registers as in launch_save_m
     const int nwg = p.wgs_per_dir * p.ndir;
     if (gm.split > 1 && !fnssl::tune(FNSSL_TUNE_TRAIN_NO_STATIC)) {   // shape-specialised kernels first
-      const int rc = launch_split_static(p, H, gm.nw, gm.split, mode | kSave, lds_chunk_cap(nwg, gm.split), nwg, st);
+      const int rc = launch_split_static(p, H, gm.nw, gm.split, mode | kSave, lds_chunk_cap(nwg, gm.split), nwg, lc);
       if (rc != kNoStatic) return rc;
     }
     choose_chunk(p.quads_per_slice, vr, p.chq, p.pad, gm.split, gm.split > 1 ? lds_chunk_cap(nwg, gm.split) : 0);
-    return H == 128 ? launch_save<128>(gm.nw, gm.split, p, mode | kSave, nwg, st)
-                    : launch_save<256>(gm.nw, gm.split, p, mode | kSave, nwg, st);
+    return H == 128 ? launch_save<128>(gm.nw, gm.split, p, mode | kSave, nwg, lc)
+                    : launch_save<256>(gm.nw, gm.split, p, mode | kSave, nwg, lc);
   });
 }
 
@@ -121,7 +121,7 @@ static BwdWsLayout bwd_ws_layout(int nseq, int hidden, int ndir) {
   L.total = L.cluster.end();
   return L;
 }
-static int lstm_backward_impl(const fnssl_lstm_bwd_desc* d, void* stream, int dry, int* family);
+static int lstm_backward_impl(const fnssl_lstm_bwd_desc* d, const LaunchCtx& lc, int* family);
 
 extern "C" {
 
@@ -168,9 +168,11 @@ size_t fnssl_lstm_bwd_workspace_bytes(int nseq, int hidden, int ndir) {
   return bwd_ws_layout(nseq, hidden, ndir).total;
 }
 
-int fnssl_lstm_backward(const fnssl_lstm_bwd_desc* d, void* stream) { return lstm_backward_impl(d, stream, 0, nullptr); }
+int fnssl_lstm_backward(const fnssl_lstm_bwd_desc* d, void* stream) {
+  return lstm_backward_impl(d, LaunchCtx{fnssl::as_stream(stream), false}, nullptr);
+}
 
-int fnssl_lstm_backward_plan(const fnssl_lstm_bwd_desc* d, int* family) { return lstm_backward_impl(d, nullptr, 1, family); }
+int fnssl_lstm_backward_plan(const fnssl_lstm_bwd_desc* d, int* family) { return lstm_backward_impl(d, LaunchCtx{nullptr, true}, family); }
 
 int fnssl_lstm_backward_status(const void* workspace, size_t workspace_bytes, int nseq, int hidden, int ndir, void* stream,
                                unsigned* status) {
@@ -186,9 +188,7 @@ int fnssl_lstm_backward_status(const void* workspace, size_t workspace_bytes, in
 
 }  // extern "C"
 
-static int lstm_backward_impl(const fnssl_lstm_bwd_desc* d, void* stream, int dry, int* family) {
-  FNSSL_REQUIRE(d, "lstm_backward: null descriptor");
-  fnssl::TuningScope tuning_of_this_call(d->tuning);
+static int check_bwd_desc(const fnssl_lstm_bwd_desc* d, size_t ws_bytes) {
   const int H = d->hidden;
   FNSSL_REQUIRE(H == 128 || H == 256, "lstm_backward: hidden size %d unsupported (128/256)", H);
   FNSSL_REQUIRE(d->ndir == 1 || d->ndir == 2, "lstm_backward: ndir must be 1 or 2");
@@ -197,26 +197,20 @@ static int lstm_backward_impl(const fnssl_lstm_bwd_desc* d, void* stream, int dr
   FNSSL_REQUIRE(d->reserve && d->dh.p && d->da && d->wpack_bwd[0] && (d->ndir == 1 || d->wpack_bwd[1]) &&
                     (d->c0g == 0 || d->dx),
                 "lstm_backward: null pointer");
-  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  auto mult4 = [](long long v) { return (v & 3) == 0 && v >= 0; };
-  FNSSL_REQUIRE(aligned(d->reserve) && aligned(d->dh.p) && aligned(d->da) && aligned(d->dx) &&
-                    aligned(d->wpack_bwd[0]) && aligned(d->wpack_bwd[1]) && aligned(d->workspace),
+  FNSSL_REQUIRE(aligned16(d->reserve, d->dh.p, d->da, d->dx, d->wpack_bwd[0], d->wpack_bwd[1], d->workspace),
                 "lstm_backward: pointers must be 16-byte aligned");
-  FNSSL_REQUIRE(mult4(d->dh.so) && mult4(d->dh.si) && mult4(d->dh.st) && mult4(d->da_so) && mult4(d->da_si) &&
-                    mult4(d->da_st) && mult4(d->dx_so) && mult4(d->dx_si) && mult4(d->dx_st),
+  FNSSL_REQUIRE(mult4(d->dh) && nonneg(d->dh.so, d->dh.si, d->dh.st) && mult4(d->da_so, d->da_si, d->da_st) &&
+                    nonneg(d->da_so, d->da_si, d->da_st) && mult4(d->dx_so, d->dx_si, d->dx_st) &&
+                    nonneg(d->dx_so, d->dx_si, d->dx_st),
                 "lstm_backward: strides must be non-negative multiples of 4 floats");
-  auto extent_ok = [&](long long so, long long si, long long st, long long width) {
-    return ((long double)so + 16.0L * si + (long double)d->nsteps * st + width) * 4.0L < 4.0e9L;
-  };
-  FNSSL_REQUIRE(extent_ok(d->dh.so, d->dh.si, d->dh.st, 2 * H) && extent_ok(d->da_so, d->da_si, d->da_st, 8 * H) &&
-                    (d->c0g == 0 || extent_ok(d->dx_so, d->dx_si, d->dx_st, 2 * d->c0g)) &&
+  FNSSL_REQUIRE(extent_ok(d->dh, 2 * H, d->nsteps) && extent_ok(d->da_so, d->da_si, d->da_st, 8 * H, d->nsteps) &&
+                    (d->c0g == 0 || extent_ok(d->dx_so, d->dx_si, d->dx_st, 2 * d->c0g, d->nsteps)) &&
                     (long double)d->nsteps * (H / 16) * kReserveRecs * 1024 < 4.0e9L,
                 "lstm_backward: one sequence group must span < 4 GB");
-  const BwdWsLayout ws = bwd_ws_layout(d->nseq, H, d->ndir);
-  if (!d->workspace || d->workspace_bytes < ws.total) {
-    fnssl::set_error("lstm_backward: workspace %zu < %zu bytes", d->workspace_bytes, ws.total);
-    return FNSSL_E_WORKSPACE;
-  }
+  return check_workspace("lstm_backward", d->workspace, d->workspace_bytes, ws_bytes);
+}
+
+static BwdParams bwd_params(const fnssl_lstm_bwd_desc* d) {
   BwdParams p;
   p.reserve = d->reserve;
   p.dh = View{d->dh.p, d->dh.so, d->dh.si, d->dh.st};
@@ -232,34 +226,20 @@ static int lstm_backward_impl(const fnssl_lstm_bwd_desc* d, void* stream, int dr
   p.wpack[1] = d->wpack_bwd[1];
   p.scratch = static_cast<float*>(d->workspace);
   p.c0g = d->c0g;
-  p.co_pad = bwd_co_pad(d->c0g, H);
+  p.co_pad = bwd_co_pad(d->c0g, d->hidden);
   p.nseq = d->nseq;
   p.q_inner = d->q_inner;
   p.nsteps = d->nsteps;
   p.ndir = d->ndir;
   p.ntasks = (d->nseq + 15) / 16;
-  p.quads_per_slice = bwd_quads_per_slice(H);
-  p.dry = dry;
+  p.quads_per_slice = bwd_quads_per_slice(d->hidden);
   p.fallback_count = d->fallback_count;
-  hipStream_t st = dry ? nullptr : fnssl::as_stream(stream);
-  const double flops = 2.0 * 4 * H * (double)(d->c0g + H) * d->nseq * (double)d->nsteps * d->ndir;
-  fnssl::TimedLaunch tl(dry ? nullptr : H == 128 ? "lstm_bwd_h128" : "lstm_bwd_h256", st, flops);
-  if (family) *family = FNSSL_LSTM_FAMILY_BWD;
-  // full-band layers of a large enough shard: the cluster-resident kernel (lstm_bwdc.h), then — in the same call — the
-  // kernels below as its guarded fallback (they return at once unless the cluster kernel recorded a hand-off it gave up on)
-  BwdClusterParams cp{};
-  if (bwdc_handles(p, H, cp)) {
-    void* cws = static_cast<char*>(d->workspace) + ws.cluster.off;
-    const int rc = backward_cluster(p, cp, cws, ws.cluster.bytes, st);
-    if (rc == FNSSL_OK) {
-      if (family) *family = FNSSL_LSTM_FAMILY_BWD_CLUSTER;
-      if (dry) return FNSSL_OK;
-      p.guard = static_cast<const unsigned*>(cws);
-    } else if (rc != kNoCluster) {
-      return rc;
-    }
-  }
-  if (dry) return FNSSL_OK;
+  return p;
+}
+
+// the per-wave / split BPTT kernels: the whole layer, or (p.guard) the guarded fallback of the cluster kernel
+static int backward_rounds(BwdParams p, int H, const LaunchCtx& lc) {
+  if (lc.dry) return FNSSL_OK;   // (one family whatever the geometry: nothing more to plan)
   const int nso = p.co_pad / 64;
   const int max_split = nso % 4 == 0 ? 4 : nso % 2 == 0 ? 2 : 1;   // output slices divide among the waves
   return plan_rounds(p.ntasks, p.ndir, max_split, H == 256 ? 6 : 2, [&](const Geometry& gm) {
@@ -271,18 +251,41 @@ static int lstm_backward_impl(const fnssl_lstm_bwd_desc* d, void* stream, int dr
     // stream of weight records (lstm_bwd2.h)
     if (H == 256 && gm.split == 4 && gm.nw == 8 && nso % 4 == 0 && !fnssl::tune(FNSSL_TUNE_NO_BWD2)) {
       p.wgs_per_dir = (gm.t1 - gm.t0 + 1) / 2;
-      return launch_bwd2_k<256>(p, p.wgs_per_dir * p.ndir, st);
+      return launch_bwd2_k<256>(p, p.wgs_per_dir * p.ndir, lc);
     }
     const Variant vr{gm.nw, gm.split > 1 ? 8 : 4, 1};
     const int nwg = p.wgs_per_dir * p.ndir;
     choose_chunk(p.quads_per_slice, vr, p.chq, p.pad, gm.split, gm.split > 1 ? lds_chunk_cap(nwg, gm.split) : 0);
-    return H == 128 ? launch_bwd<128>(gm.nw, gm.split, p, nwg, st) : launch_bwd<256>(gm.nw, gm.split, p, nwg, st);
+    return H == 128 ? launch_bwd<128>(gm.nw, gm.split, p, nwg, lc) : launch_bwd<256>(gm.nw, gm.split, p, nwg, lc);
   });
+}
+
+static int lstm_backward_impl(const fnssl_lstm_bwd_desc* d, const LaunchCtx& lc, int* family) {
+  FNSSL_REQUIRE(d, "lstm_backward: null descriptor");
+  fnssl::TuningScope tuning_of_this_call(d->tuning);
+  const BwdWsLayout ws = bwd_ws_layout(d->nseq, d->hidden, d->ndir);
+  if (const int rc = check_bwd_desc(d, ws.total)) return rc;
+  const int H = d->hidden;
+  BwdParams p = bwd_params(d);
+  const double flops = 2.0 * 4 * H * (double)(d->c0g + H) * d->nseq * (double)d->nsteps * d->ndir;
+  fnssl::TimedLaunch tl(lc.dry ? nullptr : H == 128 ? "lstm_bwd_h128" : "lstm_bwd_h256", lc.st, flops);
+  if (family) *family = FNSSL_LSTM_FAMILY_BWD;
+  // full-band layers of a large enough shard: the cluster-resident kernel (lstm_bwdc.h), then — in the same call — the
+  // per-wave / split kernels as its guarded fallback
+  BwdClusterParams cp{};
+  void* cws = static_cast<char*>(d->workspace) + ws.cluster.off;
+  return cluster_then_fallback(
+      lc, bwdc_handles(p, H, cp), FNSSL_LSTM_FAMILY_BWD_CLUSTER, family, cws,
+      [&] { return backward_cluster(p, cp, cws, ws.cluster.bytes, lc); },
+      [&](const unsigned* guard) {
+        p.guard = guard;
+        return backward_rounds(p, H, lc);
+      });
 }
 
 // ---- the training kernels (forward with reserve, BPTT) for hidden size 128 (explicit instantiation, see lstm_train.h; hidden
 // size 256: lstm_train_h256.hip)
 namespace fnssl_lstm {
-template int launch_bwd<128>(int, int, const BwdParams&, int, hipStream_t);
-template int launch_save<128>(int, int, const LstmParams&, int, int, hipStream_t);
+template int launch_bwd<128>(int, int, const BwdParams&, int, const LaunchCtx&);
+template int launch_save<128>(int, int, const LstmParams&, int, int, const LaunchCtx&);
 }  // namespace fnssl_lstm

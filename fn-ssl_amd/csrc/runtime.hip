@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "tuning.h"
+#include "lstm_host.h"
 
 namespace fnssl {
 
@@ -151,6 +152,33 @@ TimedLaunch::~TimedLaunch() {
 }
 
 }  // namespace fnssl
+
+// ---- the launch path of the LSTM kernels (lstm_host.h) -------------------------------------------------------------
+namespace fnssl_lstm {
+
+// blocks the device can hold at once for this kernel (occupancy query x CUs) >= grid?  One query per call: cheap (host only).
+static bool cluster_grid_fits(const void* kernel, int threads, size_t lds, int grid) {
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return (long long)per_cu * cluster_cus() >= grid;
+}
+
+int enqueue_args(const LaunchCtx& lc, const void* fn, int threads, size_t lds, const char* name, bool cluster, int nwg, void** args) {
+  if (lc.dry && !cluster) return FNSSL_OK;   // a planning query: nothing to ask the runtime
+  if (lds > 48 * 1024) FNSSL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  // a cluster kernel's grid may not exceed what the device says it can hold (its waits are bounded and the call carries a
+  // guarded fallback anyway — this only avoids a launch that cannot work); a query reports the family only after this check
+  if (cluster && !cluster_grid_fits(fn, threads, lds, nwg)) return kNoCluster;
+  if (lc.dry) return FNSSL_OK;
+  (void)hipLaunchKernel(fn, dim3(nwg), dim3(threads), args, lds, lc.st);   // (FNSSL_CHECK_LAUNCH reads its status)
+  FNSSL_CHECK_LAUNCH(name);
+  return FNSSL_OK;
+}
+
+}  // namespace fnssl_lstm
 
 extern "C" int fnssl_tuning_set(const fnssl_tuning* t) {
   FNSSL_REQUIRE(!t || t->struct_bytes == sizeof(fnssl_tuning), "tuning_set: struct_bytes %u, this library's fnssl_tuning has %zu",

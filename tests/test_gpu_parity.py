@@ -1897,3 +1897,76 @@ def test_forward_survives_a_cluster_member_that_never_shows_up(dev, monkeypatch)
     assert torch.equal(again, want) and int(net.fallbacks.item()) == 6
     ops.release_workspaces()
     torch.cuda.empty_cache()
+
+
+# --------------------------------------------------------------------------- every exit of the LSTM routers
+# One descriptor per exit of the forward router (lstm.hip) and of the backward's (lstm_train.hip), "narrow" layout: nf
+# sequences x 2 steps, the fewest sequences that still select the exit on 256 CUs.  Columns: hidden, directions, sequences,
+# c0, c2, what else the call carries, tuning knobs -> expected (family, rounds) — a family name alone for a backward call.
+# The expected values are what the library answered BEFORE its host dispatch was restructured (same device): literals, so
+# that a routing change shows up here as a diff of this table.
+_ROUTER_EXITS = [
+    # H, ndir, nseq, c0, c2, extras, knobs, expected
+    (64, 1, 16, 4, 0, (), {}, ("generic", 1)),
+    # H = 128 rounds: [256 | 4] channels are no cluster shape; 513 groups x 2 directions = 5 waves per CU: past the split kernels
+    (128, 2, 8193, 256, 4, ("sum",), {}, ("static", 1)),
+    # H = 256: exactly one full-chip round of 12 waves per CU (3072 groups; one fewer and the cluster kernel takes it)
+    (256, 1, 49137, 256, 0, (), {}, ("static4", 1)),
+    (256, 1, 49137, 256, 0, (), {"no_static4": 1}, ("static3", 1)),
+    (256, 2, 16, 256, 0, (), {}, ("split_static", 1)),
+    (128, 1, 16, 256, 0, ("src1",), {}, ("split", 1)),
+    (128, 2, 16, 256, 0, (), {}, ("f32_cluster", 1)),
+    (128, 2, 16, 256, 0, ("sum",), {}, ("f32_cluster", 1)),
+    (256, 1, 16, 256, 0, ("carry",), {}, ("f32_cluster", 1)),
+    (128, 2, 16, 256, 4, ("reserve",), {}, ("train", 1)),
+    (128, 1, 32, 16, 0, ("wide",), {}, ("bf16_pair", 1)),
+    (256, 1, 32, 256, 16, ("wide",), {}, ("bf16_cluster", 1)),
+    (256, 2, 16, 0, 0, ("backward",), {}, "bwd"),
+    (128, 2, 16, 0, 0, ("backward",), {}, "bwd_cluster"),
+]
+
+
+def _router_exit(dev, H, ndir, nseq, c0, c2, extras, knobs):
+    """What fnssl_lstm_plan / fnssl_lstm_backward_plan answer for one row of _ROUTER_EXITS (nothing is launched, no
+    operand is dereferenced: the tensors are never initialised)."""
+    from fnssl import _lib, ops
+    lib = _lib.load()
+    tuning = _lib.make_tuning(base=_lib.Tuning(), **knobs)     # the row's knobs and no others, whatever the environment says
+    nt = 2
+
+    def act(c, dtype=torch.float32, rows=nt):
+        return torch.empty((1, rows, nseq, c), device=dev, dtype=dtype)
+
+    if "backward" in extras:
+        res = torch.empty(ops.lstm_reserve_floats(nseq, H, ndir, nt), device=dev)
+        bw = [torch.empty(int(lib.fnssl_lstm_bwd_packed_floats(0, H)), device=dev)] * ndir
+        return ops.lstm_backward("narrow", res, act(ndir * H), act(ndir * 4 * H), None, bw, H, 0, plan_only=True, tuning=tuning)
+    wide = "wide" in extras
+    kw = dict(tuning=tuning)
+    if wide:
+        w = [torch.empty(int(lib.fnssl_lstm_packed_floats_bf16w(c0, c2, H)), device=dev)] * ndir
+        x0, x2 = act(c0, torch.bfloat16 if c2 else torch.float32), act(c2) if c2 else None     # IPDnet: bf16 activations, fp32 features
+        out = act(ndir * H, torch.bfloat16)
+        kw.update(bf16=True, wide=True)
+    else:
+        w = [torch.empty(int(lib.fnssl_lstm_packed_floats(c0, c2, H)), device=dev)] * ndir
+        x0, x2 = act(c0), act(c2) if c2 else None
+        out = act(ndir * H, rows=nt + 1)[:, 1:]                 # (a streaming call reads h_{-1} from the row before `out`)
+    if "sum" in extras:
+        kw.update(skip=act(ndir * H), out_sum=act(ndir * H, rows=nt + 1)[:, 1:])
+    if "reserve" in extras:
+        kw.update(reserve=torch.empty(ops.lstm_reserve_floats(nseq, H, ndir, nt), device=dev))
+    if "carry" in extras:
+        kw.update(carry_workspace=ops.lstm_state_workspace(nseq, H, dev), carry=True)
+    return ops.lstm_plan("narrow", x0, act(c0) if "src1" in extras else None, x2, w, H, out, **kw)
+
+
+def test_every_router_exit_reports_its_family_and_rounds(dev):
+    ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+    assert ncu == 256, "the table's sequence counts select these exits on 256 CUs, this device has %d" % ncu
+    from fnssl import ops
+    got = [_router_exit(dev, *row[:-1]) for row in _ROUTER_EXITS]
+    ops.release_workspaces()
+    torch.cuda.empty_cache()
+    assert got == [row[-1] for row in _ROUTER_EXITS], "\n".join(
+        "%s: got %s, expected %s" % (row[:-1], g, row[-1]) for row, g in zip(_ROUTER_EXITS, got) if g != row[-1])
