@@ -9,7 +9,7 @@ device:
     validation_step / test_step :156-180   the loss, then ``get_metric`` (``IPDnet.Module.PredDOA``): the template search of
                                  all tracks and ACC / MDR / FAR / MAE / RMSE on device, logged as ``valid/<m>`` / ``test/<m>``
     configure_optimizers :292-301   Adam(lr 5e-4) + ExponentialLR(0.975)
-    predict_step      :182-186
+    predict_step      :182-186   and ``predict_stream``, the same from a stream of samples (fnssl/stream.py)
 
 ``pytorch_lightning`` is optional: with it ``MyModel`` is a ``LightningModule``, without it an ``nn.Module`` whose
 methods are called directly.  The constructor is the reference's plus a trailing ``arch``: ``None`` builds ``IPDnet()``
@@ -125,6 +125,18 @@ class MyModel(_Base):
         """batch [nb, nch, ns] -> the first utterance's prediction [nt // 12, 512, nmic - 1, max_source] (:182-186)."""
         data_batch = self.data_preprocess(mic_sig_batch=batch.permute(0, 2, 1))
         return self.forward(data_batch[0])[0]
+
+    @torch.no_grad()
+    def predict_stream(self, chunk, state=None):
+        """Online ``predict_step``: chunk [nb, nch, n] = the NEXT n samples (any n) -> (preds, state).  ``preds`` is what
+        ``predict_step`` returns on the whole signal for the segments this chunk completes — the first utterance's
+        [new segments, 512, nmic - 1, max_source] — or None when it completes none; ``state`` (None for the first chunk) is
+        the ``fnssl.stream.OnlineLocalizer`` that carries the sample tail, the normalisation and the network state."""
+        from fnssl import stream
+        if state is None:
+            state = stream.OnlineLocalizer(self.arch, stream.StreamFrontEnd("array", chunk.shape[1], sample_length=280, eps=1e-6))
+        pred, _ = state.push(chunk.permute(0, 2, 1).to(self.dev))
+        return (None if pred is None else pred[0]), state
 
     def cal_loss(self, pred_batch=None, gt_batch=None, batch_idx=None):
         """Frame-level PIT-MSE (:196-206) — one HIP kernel that emits its own gradient; a scalar with a ``grad_fn``."""

@@ -10,34 +10,22 @@
 //     sums (the reference re-launches ~5 kernels per frame, utils.py:30-44);
 //   * pack_kernel: gathers the two mics of a pair, divides by (mu + eps), drops
 //     the DC bin and writes float4 = [Re i, Re j, Im i, Im j] per (pair, t, f).
+// The per-frame arithmetic (window, radix-4 transform, bin split, means, recursion step, division) lives in
+// frontend_core.h, which frontend_stream.hip inlines too: the streamed front end gives the bits of these kernels.
 #include <cmath>
 #include <cstdlib>
 
 #include "common.h"
+#include "frontend_core.h"
 #include "tuning.h"
 
 namespace {
 
-constexpr int kWin = FNSSL_WIN_LEN;   // 512
-constexpr int kHop = FNSSL_HOP;       // 256
-constexpr int kBins = FNSSL_NBIN;     // 257
-constexpr int kNF = FNSSL_NF;         // 256
+using namespace fnssl_frontend;   // frontend_core.h: the arithmetic shared with frontend_stream.hip
+
 constexpr int kFramesPerBlock = 4;    // one wave each
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 __device__ __forceinline__ unsigned bitrev8(unsigned x) { return __brev(x) >> 24; }
-
-// Orders this wave's LDS writes before its later LDS reads (a wave's LDS operations complete in order; this keeps the
-// compiler from moving them across and waits for the outstanding ones) without stopping the other waves.
-__device__ __forceinline__ void wave_lds_sync() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
 
 // sig[b*sb + n*sn + c*sc] -> spec [nb, nch, nt, 257] (re, im), magsum [nb, nch, nt]
 // CENTER = torch.stft(center=True): frame t covers samples t*hop - 256 .. t*hop + 255 of the signal extended by
@@ -126,42 +114,14 @@ stft_kernel(const float* __restrict__ sig, int nb, int nch, int nt, int ns, int 
   if (active && lane == 0 && magsum) magsum[fr] = msum;
 }
 
-__device__ __forceinline__ void pair_of(int p, int nch, int ch_mode, int& mi, int& mj) {
-  if (ch_mode == FNSSL_CH_MODE_M) {
-    mi = 0;
-    mj = p + 1;
-    return;
-  }
-  int i = 0, left = p;
-  while (left >= nch - 1 - i) {   // row i holds nch-1-i pairs (Module.py:397-402)
-    left -= nch - 1 - i;
-    ++i;
-  }
-  mi = i;
-  mj = i + 1 + left;
-}
-
 // mu[pair, t]: mu_t = a_t * mu_{t-1} + b_t * mean_t, mean_t = (S_i + S_j) / 514.
 // One WAVE per pair: the lanes form the per-frame means and the products b_t * mean_t in parallel (coalesced reads)
 // into LDS, lane 0 runs the nt-step recursion on LDS operands (a dependent chain of one multiply and one add per
-// frame instead of nt round trips to memory), the lanes write mu back coalesced.  Products and the sum are rounded
-// separately like the reference's tensor ops (utils.py:33-41); frames beyond kEmaTile continue from the carried mu.
+// frame instead of nt round trips to memory), the lanes write mu back coalesced.  b_t * mean_t is rounded on its own, the
+// step a_t * mu + (b_t * mean_t) is one fma (ema_scan_tile, frontend_core.h); frames beyond kEmaTile continue from the
+// carried mu.
 constexpr int kEmaTile = 1024;
 constexpr int kEmaWaves = 4;
-
-__device__ __forceinline__ void ema_scan_tile(float* bm, const float* ca_t, int n, float& m, int lane) {
-  // bm[0..n) holds b_t * mean_t on entry and mu_t on exit; ca_t[0..n) the a_t of the same frames
-  wave_lds_sync();
-  if (lane == 0) {
-    float mm = m;
-    for (int t = 0; t < n; ++t) {
-      mm = __fadd_rn(__fmul_rn(ca_t[t], mm), bm[t]);
-      bm[t] = mm;
-    }
-    m = mm;
-  }
-  wave_lds_sync();
-}
 
 __global__ void __launch_bounds__(kEmaWaves * 64)
 ema_kernel(const float* __restrict__ magsum, const float* __restrict__ ca, const float* __restrict__ cb, int nb,
@@ -179,8 +139,7 @@ ema_kernel(const float* __restrict__ magsum, const float* __restrict__ ca, const
   for (int t0 = 0; t0 < nt; t0 += kEmaTile) {
     const int n = min(kEmaTile, nt - t0);
     for (int t = lane; t < n; t += 64) {
-      const float mean = __fdiv_rn(__fadd_rn(si[t0 + t], sj[t0 + t]), (float)(2 * kBins));
-      bm_s[wave][t] = __fmul_rn(cb[t0 + t], mean);
+      bm_s[wave][t] = ema_term(cb[t0 + t], pair_mean(si[t0 + t], sj[t0 + t]));
       ca_s[wave][t] = ca[t0 + t];
     }
     ema_scan_tile(bm_s[wave], ca_s[wave], n, m, lane);
@@ -203,9 +162,7 @@ pack_kernel(const float2* __restrict__ spec, const float* __restrict__ mu, int n
   pair_of(p, nch, ch_mode, mi, mj);
   const float2 xi = spec[(((long long)b * nch + mi) * nt + t) * kBins + f + 1];
   const float2 xj = spec[(((long long)b * nch + mj) * nt + t) * kBins + f + 1];
-  const float den = __fadd_rn(mu[idx * nt + t], eps);
-  const float4 o = make_float4(__fdiv_rn(xi.x, den), __fdiv_rn(xj.x, den), __fdiv_rn(xi.y, den),
-                               __fdiv_rn(xj.y, den));
+  const float4 o = pair_feature(xi, xj, feature_den(mu[idx * nt + t], eps));
   if (LAYOUT == 0) {
     reinterpret_cast<float4*>(x)[(idx * nt + t) * kNF + f] = o;
   } else {
@@ -251,15 +208,11 @@ ema_array_kernel(const float* __restrict__ magsum, const float* __restrict__ ca,
   const int b = blockIdx.x * kEmaWaves + wave;
   if (b >= nb) return;
   const float* s = magsum + (long long)b * nch * nt;
-  const float cnt = (float)(nch * kBins);
   float m = 0.f;
   for (int t0 = 0; t0 < nt; t0 += kEmaTile) {
     const int n = min(kEmaTile, nt - t0);
     for (int t = lane; t < n; t += 64) {
-      float acc = s[t0 + t];
-      for (int c = 1; c < nch; ++c) acc = __fadd_rn(acc, s[(long long)c * nt + t0 + t]);
-      const float mean = __fdiv_rn(acc, cnt);
-      bm_s[wave][t] = __fmul_rn(cb[t0 + t], mean);
+      bm_s[wave][t] = ema_term(cb[t0 + t], array_mean(s + t0 + t, nt, nch));
       ca_s[wave][t] = ca[t0 + t];
     }
     ema_scan_tile(bm_s[wave], ca_s[wave], n, m, lane);
@@ -278,10 +231,10 @@ pack_array_kernel(const float2* __restrict__ spec, const float* __restrict__ mu,
   const int f = threadIdx.x;
   const int t = (int)(row % nt);
   const long long b = row / nt;
-  const float den = __fadd_rn(mu[row], eps);
+  const float den = feature_den(mu[row], eps);
   for (int c = 0; c < nch; ++c) {
     const float2 v = spec[((b * nch + c) * nt + t) * kBins + f + 1];
-    const float re = __fdiv_rn(v.x, den), im = __fdiv_rn(v.y, den);
+    const float re = feature(v.x, den), im = feature(v.y, den);
     if (LAYOUT == 0) {
       // staged: bin-major 4-byte stores straight to x were 2 nch partial writes of a 64-byte stride per lane
       row_lds[f * (2 * nch) + c] = re;
@@ -320,10 +273,10 @@ pack_array_planes_kernel(const float2* __restrict__ spec, const float* __restric
     for (int r = 0; r < 8; ++r) {
       const int tt = tl + 8 * r, t = t0 + tt;
       if (t < nt) {
-        const float den = __fadd_rn(mu[b * nt + t], eps);
+        const float den = feature_den(mu[b * nt + t], eps);
         const float2 v = spec[((b * nch + c) * nt + t) * kBins + f0 + fl + 1];
-        re_t[fl][tt] = __fdiv_rn(v.x, den);
-        im_t[fl][tt] = __fdiv_rn(v.y, den);
+        re_t[fl][tt] = feature(v.x, den);
+        im_t[fl][tt] = feature(v.y, den);
       }
     }
   }
@@ -359,38 +312,6 @@ pack_array_planes_kernel(const float2* __restrict__ spec, const float* __restric
 //     the pair path's spectrum + magnitude-sum pass.
 constexpr int kXsStride = kWin + 1;
 
-__device__ __forceinline__ unsigned digitrev4_8(unsigned m) {      // reverse the four base-4 digits of an 8-bit index
-  return ((m & 3u) << 6) | ((m & 12u) << 2) | ((m & 48u) >> 2) | ((m & 192u) >> 6);
-}
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 w) { return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
-
-// 256-point complex FFT in place in z[256] (digit-reversed on entry, natural order on exit); tw[k] = exp(-2 pi i k / 512)
-__device__ __forceinline__ void fft256_radix4(float2* z, const float2* tw, int lane) {
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const int L = 1 << (2 * s);
-    const int j = lane & (L - 1);
-    const int base = ((lane >> (2 * s)) << (2 * s + 2)) + j;
-    const int step = j * (128 >> (2 * s));                    // W_{4L}^j = tw[j * 512 / (4 L)]
-    const float2 a0 = z[base];
-    float2 a1 = z[base + L], a2 = z[base + 2 * L], a3 = z[base + 3 * L];
-    if (s > 0) {
-      a1 = cmul(a1, tw[step]);
-      a2 = cmul(a2, tw[2 * step]);
-      a3 = cmul(a3, tw[3 * step]);
-    }
-    const float2 t0 = make_float2(a0.x + a2.x, a0.y + a2.y), t1 = make_float2(a0.x - a2.x, a0.y - a2.y);
-    const float2 t2 = make_float2(a1.x + a3.x, a1.y + a3.y);
-    const float2 t3 = make_float2(a1.y - a3.y, a3.x - a1.x);  // -i (a1 - a3)
-    z[base] = make_float2(t0.x + t2.x, t0.y + t2.y);
-    z[base + L] = make_float2(t1.x + t3.x, t1.y + t3.y);
-    z[base + 2 * L] = make_float2(t0.x - t2.x, t0.y - t2.y);
-    z[base + 3 * L] = make_float2(t1.x - t3.x, t1.y - t3.y);   // a butterfly is in place: only the NEXT stage reads across lanes
-    wave_lds_sync();
-  }
-}
-
 struct RowParams {
   const float* sig;
   int nb, nch, nt, ns, hop, center;
@@ -412,18 +333,13 @@ template <int MODE, int NW>
 __global__ void __launch_bounds__(NW * 64) stft_rows_kernel(const RowParams p) {
   constexpr int kRowWaves = NW;
   extern __shared__ __attribute__((aligned(16))) float smem_rows[];
-  float2* tw = reinterpret_cast<float2*>(smem_rows);                    // [384]
+  float2* tw = reinterpret_cast<float2*>(smem_rows);                    // [kTwiddles]
   float* hann = smem_rows + 768;                                          // [512]
   float2* zbuf = reinterpret_cast<float2*>(smem_rows + 768 + 512);        // [4][256]
   float* xs = smem_rows + 768 + 512 + kRowWaves * 512;                    // [nch][513]
   float* row = xs + p.nch * kXsStride;                                    // MODE 2: [256][2 nch]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int k = tid; k < 384; k += kRowWaves * 64) {
-    float sn_, cs_;
-    sincospif(-(float)k / 256.0f, &sn_, &cs_);
-    tw[k] = make_float2(cs_, sn_);
-  }
-  for (int n = tid; n < kWin; n += kRowWaves * 64) hann[n] = 0.5f - 0.5f * cospif((float)n / 256.0f);
+  fill_tables(tw, hann, tid, kRowWaves * 64);
   // Persistent workgroup: it walks frames blockIdx.x, + gridDim.x, ...; the NEXT frame's samples are requested into
   // registers before the current frame is transformed (a workgroup per frame left the ~2 us of HBM latency of its own
   // fetch exposed: one workgroup fits a CU) and are written to the LDS image after it.
@@ -488,43 +404,25 @@ __global__ void __launch_bounds__(NW * 64) stft_rows_kernel(const RowParams p) {
     const int t = (int)(fr % p.nt);
     const long long b = fr / p.nt;
     float den = 1.f;
-    if (MODE == 2) den = __fadd_rn(p.mu[b * p.nt + t], p.eps);
+    if (MODE == 2) den = feature_den(p.mu[b * p.nt + t], p.eps);
     for (int c = wave; c < p.nch; c += kRowWaves) {
       const float* xc = xs + c * kXsStride;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int m = lane + 64 * r;
-        z[digitrev4_8(m)] = make_float2(hann[2 * m] * xc[2 * m], hann[2 * m + 1] * xc[2 * m + 1]);
+        window_store(z, hann, m, xc[2 * m], xc[2 * m + 1]);
       }
       wave_lds_sync();
       fft256_radix4(z, tw, lane);
-      // split: X[k] = E[k] + W512^k O[k],  E = (Z[k] + conj Z[N-k])/2,  O = (Z[k] - conj Z[N-k])/(2i)
       const long long cf = (b * p.nch + c) * p.nt + t;
-      float msum = 0.f;
-#pragma unroll
-      for (int r = 0; r < 5; ++r) {
-        const int k = lane + 64 * r;
-        if (k <= 256) {
-          const float2 zk = z[k & 255];
-          const float2 zn = z[(256 - k) & 255];
-          const float er = 0.5f * (zk.x + zn.x), ei = 0.5f * (zk.y - zn.y);
-          const float dr = 0.5f * (zk.x - zn.x), di = 0.5f * (zk.y + zn.y);
-          const float orr = di, oi = -dr;
-          const float2 w = k < 256 ? tw[k] : make_float2(-1.f, 0.f);
-          const float xr = er + (orr * w.x - oi * w.y);
-          const float xi = ei + (orr * w.y + oi * w.x);
-          if (MODE == 0) p.spec[cf * kBins + k] = make_float2(xr, xi);
-          if (MODE != 2) msum += sqrtf(xr * xr + xi * xi);
-          if (MODE == 2 && k >= 1) {
-            row[(k - 1) * 2 * p.nch + c] = __fdiv_rn(xr, den);
-            row[(k - 1) * 2 * p.nch + p.nch + c] = __fdiv_rn(xi, den);
-          }
+      const float msum = split_bins<MODE != 2>(z, tw, lane, [&](int k, float xr, float xi) {
+        if (MODE == 0) p.spec[cf * kBins + k] = make_float2(xr, xi);
+        if (MODE == 2 && k >= 1) {
+          row[(k - 1) * 2 * p.nch + c] = feature(xr, den);
+          row[(k - 1) * 2 * p.nch + p.nch + c] = feature(xi, den);
         }
-      }
-      if (MODE != 2) {
-        msum = wave_sum(msum);
-        if (lane == 0) p.magsum[cf] = msum;
-      }
+      });
+      if (MODE != 2 && lane == 0) p.magsum[cf] = msum;
       wave_lds_sync();                                         // z is reused by this wave's next channel
     }
     if (MODE == 2) {

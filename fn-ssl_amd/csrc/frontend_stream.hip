@@ -1,0 +1,226 @@
+// The front end for a stream of microphone samples: ONE launch per pushed chunk takes the new samples to normalised
+// network features, continuing the recursive magnitude normalisation from a carried mu, and produces the bits
+// fnssl_stft_ex + fnssl_pair_features / fnssl_array_features (layout 0) give on the whole signal.
+//
+// The hop-256 transform is not centred, so frame t is a function of samples [256 t, 256 t + 512) alone; the recursion is a
+// sequential chain per microphone pair (pair mode) or per utterance (array mode).  Frame t's features need mu_t, which
+// needs every channel's magnitude sum up to t, so ONE workgroup serves an utterance and the dependency stays inside its
+// barriers: per tile of kStreamTile frames
+//   A  the waves transform the tile's (frame, channel) windows side by side (frontend_core.h: the whole-signal kernels'
+//      own window, radix-4 transform and bin split), keep bins 1..256 and the wave-reduced sum_k |X[k]|;
+//   B  one wave per chain forms the tile's means and runs the recursion from the carried mu (ema_scan_tile);
+//   C  all threads divide by (mu_t + eps) and write the feature rows.
+// The tile's spectra live in LDS while they fit (12 frames x 4 channels = 96 KiB beside the transform staging) and in a
+// caller-owned scratch inside the state otherwise (8 channels: 192 KiB): written in A, re-read in C by other waves of the
+// SAME workgroup behind the workgroup barrier, whose workgroup-scope release / acquire is all that needs (one CU, one L1).
+#include <cstdint>
+
+#include "common.h"
+#include "frontend_core.h"
+
+namespace {
+
+using namespace fnssl_frontend;
+
+constexpr int kStreamWaves = 16;
+constexpr int kStreamThreads = kStreamWaves * 64;
+constexpr int kStreamTile = 12;            // frames per pass: the chunk the online models consume
+constexpr int kStreamMaxCh = 16;
+constexpr size_t kLdsBudget = 160 * 1024;
+constexpr size_t kStateAlign = 256;
+
+struct StreamParams {
+  const float* sig;        // first sample of frame `frame0`
+  long long sb, sn, sc;
+  int nch, nchain, ch_mode;
+  int frame0, nframes, tile, sample_length;
+  const float* ca;         // [sample_length + 1], indexed by min(t, sample_length)
+  const float* cb;
+  float eps;
+  float* mu;               // [nb, nchain], carried
+  float2* scratch;         // nullptr: spectra in LDS; else [nb][tile * nch * 256]
+  float* x;                // pair: [nb * np, nframes, 256, 4]; array: [nb, nframes, 256, 2 nch]
+};
+
+// floats of the fixed LDS carve; the spectra ([tile * nch * 256] float2) follow when they fit
+__host__ __device__ inline int fixed_lds_floats(int nch, int nchain, int tile) {
+  const int n = 2 * kTwiddles + kWin + kStreamWaves * 512 + tile * nch + nchain * tile + tile + nchain;
+  return (n + 3) & ~3;
+}
+
+size_t spectra_bytes(int nch, int tile) { return (size_t)tile * nch * kNF * sizeof(float2); }
+
+bool spectra_in_lds(int nch, int nchain, int tile) {
+  return fixed_lds_floats(nch, nchain, tile) * sizeof(float) + spectra_bytes(nch, tile) <= kLdsBudget;
+}
+
+template <int ARRAY>
+__global__ void __launch_bounds__(kStreamThreads) stream_frontend_kernel(const StreamParams p) {
+  extern __shared__ __attribute__((aligned(16))) float smem_stream[];
+  float2* tw = reinterpret_cast<float2*>(smem_stream);                  // [kTwiddles]
+  float* hann = smem_stream + 2 * kTwiddles;                            // [512]
+  float2* zbuf = reinterpret_cast<float2*>(hann + kWin);                // [kStreamWaves][256]
+  float* msum_s = hann + kWin + kStreamWaves * 512;                     // [tile][nch]
+  float* bm_s = msum_s + p.tile * p.nch;                                // [nchain][tile]: b_t * mean_t, then mu_t
+  float* ca_s = bm_s + p.nchain * p.tile;                               // [tile]
+  float* mu_s = ca_s + p.tile;                                          // [nchain]: the carried mu
+  float2* spec = reinterpret_cast<float2*>(smem_stream + fixed_lds_floats(p.nch, p.nchain, p.tile));
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long b = blockIdx.x;
+  if (p.scratch) spec = p.scratch + b * p.tile * p.nch * kNF;
+  fill_tables(tw, hann, tid, kStreamThreads);
+  for (int i = tid; i < p.nchain; i += kStreamThreads) mu_s[i] = p.mu[b * p.nchain + i];
+  float2* z = zbuf + wave * 256;
+  const float* ub = p.sig + b * p.sb;
+  const int rowlen = kNF * 2 * p.nch;                                   // array mode: floats of a frame's feature row
+  for (int f0 = 0; f0 < p.nframes; f0 += p.tile) {
+    const int n = min(p.tile, p.nframes - f0);
+    __syncthreads();               // tables and mu_s ready; the previous tile's pack is done with spec / bm_s
+    for (int i = tid; i < n; i += kStreamThreads) ca_s[i] = p.ca[min(p.frame0 + f0 + i, p.sample_length)];
+    // A: transforms, one wave per (frame, channel)
+    for (int w = wave; w < n * p.nch; w += kStreamWaves) {
+      const int f = w / p.nch, c = w - f * p.nch;
+      const float* xc = ub + (long long)c * p.sc + (long long)(f0 + f) * kHop * p.sn;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = lane + 64 * r;
+        window_store(z, hann, m, xc[(long long)(2 * m) * p.sn], xc[(long long)(2 * m + 1) * p.sn]);
+      }
+      wave_lds_sync();
+      fft256_radix4(z, tw, lane);
+      float2* so = spec + (long long)w * kNF;                           // bins 1..256 of (f, c)
+      const float msum = split_bins<true>(z, tw, lane, [&](int k, float xr, float xi) {
+        if (k >= 1) so[k - 1] = make_float2(xr, xi);
+      });
+      if (lane == 0) msum_s[w] = msum;
+      wave_lds_sync();                                                  // z is reused by this wave's next window
+    }
+    if (p.scratch) __threadfence_block();   // spectra staged in memory: release them to the workgroup's other waves
+    __syncthreads();
+    // B: the recursion, one wave per chain
+    for (int ch = wave; ch < p.nchain; ch += kStreamWaves) {
+      float* bm = bm_s + ch * p.tile;
+      int mi = 0, mj = 0;
+      if (!ARRAY) pair_of(ch, p.nch, p.ch_mode, mi, mj);
+      for (int t = lane; t < n; t += 64) {
+        const float* s = msum_s + t * p.nch;
+        const float mean = ARRAY ? array_mean(s, 1, p.nch) : pair_mean(s[mi], s[mj]);
+        bm[t] = ema_term(p.cb[min(p.frame0 + f0 + t, p.sample_length)], mean);
+      }
+      float m = mu_s[ch];
+      ema_scan_tile(bm, ca_s, n, m, lane);
+      if (lane == 0) mu_s[ch] = m;
+    }
+    __syncthreads();
+    // C: features
+    if (ARRAY) {
+      // the tile's rows [n][256][Re ch 0.. | Im ch 0..] are one contiguous piece of x: float4 stores
+      float* o = p.x + (b * p.nframes + f0) * (long long)rowlen;
+      const int total = n * rowlen;                                     // multiple of 4
+      for (int e0 = 4 * tid; e0 < total; e0 += 4 * kStreamThreads) {
+        float v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int e = e0 + q;
+          const int f = e / rowlen, rem = e - f * rowlen;
+          const int k = rem / (2 * p.nch), cc = rem - k * 2 * p.nch;
+          const int c = cc < p.nch ? cc : cc - p.nch;
+          const float2 s = spec[((long long)f * p.nch + c) * kNF + k];
+          v[q] = feature(cc < p.nch ? s.x : s.y, feature_den(bm_s[f], p.eps));
+        }
+        *reinterpret_cast<float4*>(o + e0) = make_float4(v[0], v[1], v[2], v[3]);
+      }
+    } else {
+      const int k = tid & (kNF - 1);
+      for (int row = tid >> 8; row < p.nchain * n; row += kStreamThreads / kNF) {
+        const int ch = row / n, f = row - ch * n;
+        int mi, mj;
+        pair_of(ch, p.nch, p.ch_mode, mi, mj);
+        const float2 xi = spec[((long long)f * p.nch + mi) * kNF + k];
+        const float2 xj = spec[((long long)f * p.nch + mj) * kNF + k];
+        const float4 o = pair_feature(xi, xj, feature_den(bm_s[ch * p.tile + f], p.eps));
+        reinterpret_cast<float4*>(p.x)[((b * p.nchain + ch) * p.nframes + f0 + f) * kNF + k] = o;
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < p.nchain; i += kStreamThreads) p.mu[b * p.nchain + i] = mu_s[i];
+}
+
+int chains(int nch, int mode, int ch_mode) { return mode == FNSSL_STREAM_ARRAY ? 1 : fnssl_num_pairs(nch, ch_mode); }
+
+size_t mu_bytes(int nb, int nchain) {
+  return ((size_t)nb * nchain * sizeof(float) + kStateAlign - 1) / kStateAlign * kStateAlign;
+}
+
+bool bad_shape(int nb, int nch, int mode, int ch_mode) {
+  if (mode != FNSSL_STREAM_PAIR && mode != FNSSL_STREAM_ARRAY) return true;
+  if (mode == FNSSL_STREAM_PAIR && ch_mode != FNSSL_CH_MODE_M && ch_mode != FNSSL_CH_MODE_MM) return true;
+  return nb <= 0 || nch < (mode == FNSSL_STREAM_PAIR ? 2 : 1) || nch > kStreamMaxCh;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t fnssl_stream_frontend_state_bytes(int nb, int nch, int mode, int ch_mode, int max_new_frames) {
+  if (bad_shape(nb, nch, mode, ch_mode) || max_new_frames <= 0) return 0;
+  const int nchain = chains(nch, mode, ch_mode);
+  const int tile = max_new_frames < kStreamTile ? max_new_frames : kStreamTile;
+  return mu_bytes(nb, nchain) + (spectra_in_lds(nch, nchain, tile) ? 0 : (size_t)nb * spectra_bytes(nch, tile));
+}
+
+int fnssl_stream_frontend(const float* sig, int nb, int ns, int nch, long long sb, long long sn, long long sc, int mode,
+                          int ch_mode, int frame0, int nframes, const float* coef_a, const float* coef_b,
+                          int sample_length, float eps, void* state, size_t state_bytes, float* x, void* stream) {
+  FNSSL_REQUIRE(sig && coef_a && coef_b && state && x, "stream_frontend: null pointer");
+  FNSSL_REQUIRE(mode == FNSSL_STREAM_PAIR || mode == FNSSL_STREAM_ARRAY, "stream_frontend: mode %d", mode);
+  FNSSL_REQUIRE(mode == FNSSL_STREAM_ARRAY || ch_mode == FNSSL_CH_MODE_M || ch_mode == FNSSL_CH_MODE_MM,
+                "stream_frontend: ch_mode %d", ch_mode);
+  FNSSL_REQUIRE(nb > 0, "stream_frontend: empty batch (nb %d)", nb);
+  FNSSL_REQUIRE(nch >= (mode == FNSSL_STREAM_PAIR ? 2 : 1), "stream_frontend: %d channels (pair mode needs >= 2)", nch);
+  FNSSL_REQUIRE(nch <= kStreamMaxCh, "stream_frontend: at most %d channels (%d given)", kStreamMaxCh, nch);
+  FNSSL_REQUIRE(nframes > 0, "stream_frontend: frame count %d", nframes);
+  FNSSL_REQUIRE(frame0 >= 0 && (long long)frame0 + nframes < (1ll << 31), "stream_frontend: first frame %d", frame0);
+  FNSSL_REQUIRE(sample_length > 0, "stream_frontend: sample_length %d", sample_length);
+  FNSSL_REQUIRE((long long)ns >= (long long)(nframes - 1) * kHop + kWin,
+                "stream_frontend: %d frames need %lld samples, the window has %d", nframes,
+                (long long)(nframes - 1) * kHop + kWin, ns);
+  const size_t need = fnssl_stream_frontend_state_bytes(nb, nch, mode, ch_mode, nframes);
+  FNSSL_REQUIRE(state_bytes >= need, "stream_frontend: state of %zu bytes, fnssl_stream_frontend_state_bytes asks for %zu",
+                state_bytes, need);
+  FNSSL_REQUIRE(((uintptr_t)sig | (uintptr_t)coef_a | (uintptr_t)coef_b) % 4 == 0 && (uintptr_t)state % 16 == 0 &&
+                    (uintptr_t)x % 16 == 0,
+                "stream_frontend: misaligned pointer (samples and coefficients 4 bytes, state and output 16)");
+  StreamParams p{};
+  p.sig = sig;
+  p.sb = sb; p.sn = sn; p.sc = sc;
+  p.nch = nch;
+  p.nchain = chains(nch, mode, ch_mode);
+  p.ch_mode = ch_mode;
+  p.frame0 = frame0;
+  p.nframes = nframes;
+  p.tile = nframes < kStreamTile ? nframes : kStreamTile;
+  p.sample_length = sample_length;
+  p.ca = coef_a;
+  p.cb = coef_b;
+  p.eps = eps;
+  p.mu = static_cast<float*>(state);
+  const bool in_lds = spectra_in_lds(nch, p.nchain, p.tile);
+  p.scratch = in_lds ? nullptr : reinterpret_cast<float2*>(static_cast<char*>(state) + mu_bytes(nb, p.nchain));
+  p.x = x;
+  const size_t lds = fixed_lds_floats(nch, p.nchain, p.tile) * sizeof(float) + (in_lds ? spectra_bytes(nch, p.tile) : 0);
+  hipStream_t st = fnssl::as_stream(stream);
+  const void* fn = mode == FNSSL_STREAM_ARRAY ? reinterpret_cast<const void*>(stream_frontend_kernel<1>)
+                                              : reinterpret_cast<const void*>(stream_frontend_kernel<0>);
+  if (lds > 48 * 1024) FNSSL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  fnssl::TimedLaunch tl("stream_frontend", st);
+  if (mode == FNSSL_STREAM_ARRAY)
+    hipLaunchKernelGGL(stream_frontend_kernel<1>, dim3((unsigned)nb), dim3(kStreamThreads), lds, st, p);
+  else
+    hipLaunchKernelGGL(stream_frontend_kernel<0>, dim3((unsigned)nb), dim3(kStreamThreads), lds, st, p);
+  FNSSL_CHECK_LAUNCH("stream_frontend_kernel");
+  return FNSSL_OK;
+}
+
+}  // extern "C"

@@ -33,6 +33,7 @@ LIB_PATH = os.environ.get("FNSSL_LIB_PATH", LIB_PATH)
 
 ABI_VERSION = 19
 CH_MODE = {"M": 0, "MM": 1}
+STREAM_MODE = {"pair": 0, "array": 1}       # include/fnssl.h: FNSSL_STREAM_PAIR / FNSSL_STREAM_ARRAY
 # kernel families fnssl_lstm_plan reports (include/fnssl.h: FNSSL_LSTM_FAMILY_*)
 LSTM_FAMILY = {1: "generic", 2: "static", 3: "static2 (retired)", 4: "split", 5: "split_static", 6: "f32_cluster",
                7: "static3", 8: "bf16", 9: "bf16_solo", 10: "bf16_pair", 11: "bf16_cluster", 12: "train", 13: "bwd", 14: "bwd_cluster",
@@ -64,6 +65,7 @@ SYMBOLS = [
     "fnssl_sn_mamba", "fnssl_sn_head", "fnssl_sn_forward_workspace_bytes", "fnssl_sn_state_floats", "fnssl_sn_forward",
     "fnssl_ipd2doa_tracks", "fnssl_doa_metrics",
     "fnssl_doa_metrics_ex", "fnssl_ipd2doa_mse_tracks", "fnssl_ipdnet2_targets",
+    "fnssl_stream_frontend_state_bytes", "fnssl_stream_frontend",
 ]
 
 
@@ -208,6 +210,9 @@ def load():
     lib.fnssl_stft_ex.argtypes = [vp, i, i, i, ll, ll, ll, i, i, vp, vp, vp]
     lib.fnssl_array_frontend.argtypes = [vp, i, i, i, ll, ll, ll, i, i, vp, vp, f, vp, vp, vp, vp]
     lib.fnssl_forgetting_coefs.argtypes = [i, i, vp, vp]
+    lib.fnssl_stream_frontend_state_bytes.argtypes = [i, i, i, i, i]
+    lib.fnssl_stream_frontend_state_bytes.restype = sz
+    lib.fnssl_stream_frontend.argtypes = [vp, i, i, i, ll, ll, ll, i, i, i, i, vp, vp, i, f, vp, sz, vp, vp]
     lib.fnssl_pair_features.argtypes = [vp, vp, vp, vp, i, i, i, i, f, vp, vp, i, vp]
     lib.fnssl_nchw_to_seq.argtypes = [vp, i, i, i, i, vp, vp]
     lib.fnssl_lstm_packed_floats.argtypes = [i, i, i]

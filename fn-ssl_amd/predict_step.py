@@ -246,3 +246,16 @@ class MyModel(_Base):
         sig = batch.permute(0, 2, 1).to(self.dev)
         x0 = ops.preprocess(sig, self.ch_mode, 1e-6, layout=0)
         return self.arch.forward_seq(x0)
+
+    @torch.no_grad()
+    @ops.on_device
+    def predict_stream(self, chunk, state=None):
+        """Online ``predict_step``: chunk [nb, nch, n] = the NEXT n samples (any n) -> (preds, state).  ``preds`` is what
+        ``predict_step`` returns on the whole signal for the segments this chunk completes, [nb*np, new segments, 512], or
+        None when it completes none; ``state`` (None for the first chunk) is the ``fnssl.stream.OnlineLocalizer`` that
+        carries the sample tail, the normalisation and the network state."""
+        from fnssl import stream
+        if state is None:
+            state = stream.OnlineLocalizer(self.arch, stream.StreamFrontEnd("pair", chunk.shape[1], self.ch_mode, 298, 1e-6))
+        pred, _ = state.push(chunk.permute(0, 2, 1).to(self.dev))
+        return pred, state

@@ -763,6 +763,40 @@ int fnssl_array_frontend(const float* sig, int nb, int ns, int nch, long long sb
                          int hop, int center, const float* coef_a, const float* coef_b, float eps,
                          float* magsum, float* mu, float* x, void* stream);
 
+/* ---- streamed front end (additive: FNSSL_ABI_VERSION stays 19) --------------------------------------------------------
+ * Microphone samples in, network features out, chunk by chunk, with the bits of the whole-signal path: the hop-256
+ * transform is not centred, so frame t is a function of samples [256 t, 256 t + 512) alone, and the recursive
+ * normalisation continues from the mu carried in the state.  One launch per call, one workgroup per utterance.
+ *   FNSSL_STREAM_PAIR   FN-SSL: mu per microphone pair (ch_mode as fnssl_pair_features), mean_t = (S_i + S_j) / 514,
+ *                       x [nb * np, nframes, 256, 4]      = layout 0 of fnssl_pair_features, frames [frame0, frame0 + nframes)
+ *   FNSSL_STREAM_ARRAY  IPDnet: mu per utterance over all channels (ch_mode ignored),
+ *                       x [nb, nframes, 256, 2 * nch]     = layout 0 of fnssl_array_features
+ */
+#define FNSSL_STREAM_PAIR 0
+#define FNSSL_STREAM_ARRAY 1
+
+/* Bytes of the caller-owned state for calls of up to max_new_frames frames each (the size stops growing at 12 frames):
+ * the carried mu ([nb, np] or [nb]) and, where a 12-frame tile of spectra does not fit the LDS (more than 5 channels),
+ * the scratch they are staged in.  The caller ZEROES it before the first chunk (mu_{-1} = 0) and leaves it alone between
+ * calls.  0 for an invalid shape (nb <= 0, nch < 2 in pair mode, nch > 16, bad mode / ch_mode, max_new_frames <= 0). */
+size_t fnssl_stream_frontend_state_bytes(int nb, int nch, int mode, int ch_mode, int max_new_frames);
+
+/*
+ *   sig            the FIRST sample of frame `frame0`; sample n of channel c of utterance b at sig[b*sb + n*sn + c*sc]
+ *                  (any strides, as fnssl_stft_ex); ns = samples addressable per channel, >= 256 * (nframes - 1) + 512
+ *   frame0         absolute index of the first frame of this call (0 for the first chunk); nframes > 0, any count
+ *   coef_a/b       DEVICE [sample_length + 1] = fnssl_forgetting_coefs(sample_length + 1, sample_length, ...): frame t
+ *                  reads entry min(t, sample_length) (the coefficients are constant from t = sample_length on, and
+ *                  b_t there is NOT always the float of the frames before it).  Zero tables with eps = 1 give the
+ *                  reference's un-normalised features (nor_flag = False).
+ *   state          fnssl_stream_frontend_state_bytes(nb, nch, mode, ch_mode, >= nframes) bytes, 16-byte aligned
+ *   x              16-byte aligned, written whole
+ * Everything is validated before the launch (FNSSL_E_INVALID + fnssl_last_error).
+ */
+int fnssl_stream_frontend(const float* sig, int nb, int ns, int nch, long long sb, long long sn, long long sc, int mode,
+                          int ch_mode, int frame0, int nframes, const float* coef_a, const float* coef_b,
+                          int sample_length, float eps, void* state, size_t state_bytes, float* x, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* IPDnet head (next row 8f-3): causal 3x3 Conv2d + time pooling              */
 /* ------------------------------------------------------------------------- */
