@@ -66,6 +66,8 @@ int forward_bf16c(LstmParams p, int H, int flags, size_t cluster_bytes, const La
   // batch into MORE clusters of 17 - 20 tiles costs 3 + 2 while they still fit one launch (config 3's full-band layers: 1200
   // tiles, 50 clusters x 24 on 200 CUs -> 60 x 20 on 240).  The smallest count with the lowest cost is taken; 16 tiles or fewer
   // per cluster (2 + 2) would need a third more CUs than the batch's 17 tiles per cluster bound allows the workspace (lstm.hip).
+  // (tests/lstm_bf16_f64_ref.py restates this cut — narrow_clusters, full_band_clusters — to pick the boundary groups it
+  //  checks: keep the two in step; its host test pins the restatement on the sizes named in these comments)
   const int tiles = (p.nseq + 31) / 32, np = cluster_parts(H);
   int cl_per_dir = (tiles + 8 * np - 1) / (8 * np);
   auto cost = [&](int cl) {

@@ -76,6 +76,7 @@ static int forward_bf16w_plain(LstmParams p, int H, int flags, const unsigned* g
     rc = launch_bf16p(p, H, flags, p.wgs_per_dir * p.ndir, lc);
   } else {
     if (family) *family = FNSSL_LSTM_FAMILY_BF16_SOLO;
+    // (restated as _solo_waves in tests/test_gpu_lstm_bf16_f64.py, which runs both layouts: keep the two in step)
     const int nw = ((long long)groups * p.ndir <= 2ll * fnssl::device_cus() || H >= 256) ? 2 : 4;
     p.wgs_per_dir = (groups + nw - 1) / nw;
     rc = launch_bf16w(p, H, nw, flags, p.wgs_per_dir * p.ndir, lc);
