@@ -1,5 +1,5 @@
 // Shared host-side plumbing for libfnssl_hip.so: error reporting across the C
-// ABI (no exceptions), launch checking and optional per-kernel HIP-event timing.
+// ABI (no exceptions) and optional per-kernel HIP-event timing (the launch path is host.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -49,11 +49,8 @@ int device_cus();
     }                                                                                \
   } while (0)
 
-#define FNSSL_CHECK_LAUNCH(what)                                                     \
-  do {                                                                               \
-    hipError_t e__ = hipGetLastError();                                              \
-    if (e__ != hipSuccess) {                                                         \
-      fnssl::set_error("launch of %s failed: %s", what, hipGetErrorString(e__));     \
-      return FNSSL_E_HIP;                                                            \
-    }                                                                                \
+// return a failed call's code (variadic: the call may hold commas outside parentheses)
+#define FNSSL_TRY(...)                             \
+  do {                                             \
+    if (const int rc__ = (__VA_ARGS__)) return rc__; \
   } while (0)

@@ -469,48 +469,14 @@ static int conv_run(int bf, bool anti, const float* xa, long long a_sb, long lon
   const size_t lds = (size_t)2 * p.chq * 4096;
   const double flops = 2.0 * 9 * (ca + cb) * (double)cout * nb * nf * (double)nt;
   fnssl::TimedLaunch tl(bf ? "conv3x3_bf16" : (anti ? "conv3x3_dgrad" : "conv3x3"), fnssl::as_stream(stream), flops);
-  if (bf == 2) {
-    if (NT == 8) {
-      auto k = conv3x3_bf16_kernel<8, NW, M, true>;
-      if (lds > 48 * 1024)
-        FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, fnssl::as_stream(stream), p);
-    } else {
-      auto k = conv3x3_bf16_kernel<4, NW, M, true>;
-      if (lds > 48 * 1024)
-        FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, fnssl::as_stream(stream), p);
-    }
-  } else if (bf) {
-    if (NT == 8) {
-      auto k = conv3x3_bf16_kernel<8, NW, M>;
-      if (lds > 48 * 1024)
-        FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, fnssl::as_stream(stream), p);
-    } else {
-      auto k = conv3x3_bf16_kernel<4, NW, M>;
-      if (lds > 48 * 1024)
-        FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, fnssl::as_stream(stream), p);
-    }
-  } else if (anti) {
-    auto k = NT == 8 ? conv3x3_kernel<8, NW, M, true> : conv3x3_kernel<4, NW, M, true>;
-    if (lds > 48 * 1024)
-      FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, fnssl::as_stream(stream), p);
-  } else if (NT == 8) {
-    auto k = conv3x3_kernel<8, NW, M>;
-    if (lds > 48 * 1024)
-      FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, fnssl::as_stream(stream), p);
-  } else {
-    auto k = conv3x3_kernel<4, NW, M>;
-    if (lds > 48 * 1024)
-      FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k, dim3(nwg), dim3(NW * 64), lds, fnssl::as_stream(stream), p);
-  }
-  FNSSL_CHECK_LAUNCH("conv3x3_kernel");
-  return FNSSL_OK;
+  // the kernels' fourth argument: segment A arrives as bf16 (bf16 kernels), the anti-causal form (fp32 kernels)
+  return fnssl::with_value<8, 4>(NT, [&](auto NT_) {
+    constexpr int NTC = NT_;
+    return fnssl::with_bool(bf ? bf == 2 : anti, [&](auto X) {
+      const auto k = bf ? conv3x3_bf16_kernel<NTC, NW, M, X> : conv3x3_kernel<NTC, NW, M, X>;
+      return enqueue(fnssl::as_stream(stream), Kernel{k, NW * 64, lds, bf ? "conv3x3_bf16_kernel" : "conv3x3_kernel"}, nwg, p);
+    });
+  });
 }
 
 int fnssl_conv3x3_causal(const float* xa, long long a_sb, long long a_sf, long long a_st, int ca, const float* xb,
@@ -556,10 +522,8 @@ int fnssl_avgpool_time(const float* x, int rows, int nt, int c, int k, float* y,
   if (total == 0) return FNSSL_OK;
   FNSSL_REQUIRE((total + 255) / 256 < (1ll << 31), "avgpool_time: too large");
   fnssl::TimedLaunch tl("avgpool_time", fnssl::as_stream(stream));
-  hipLaunchKernelGGL(pool_t_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, fnssl::as_stream(stream),
-                     reinterpret_cast<const float4*>(x), rows, nt, c / 4, k, reinterpret_cast<float4*>(y));
-  FNSSL_CHECK_LAUNCH("pool_t_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{pool_t_kernel, 256, 0, "pool_t_kernel"}, (unsigned)((total + 255) / 256),
+                 reinterpret_cast<const float4*>(x), rows, nt, c / 4, k, reinterpret_cast<float4*>(y));
 }
 
 }  // extern "C"

@@ -518,10 +518,7 @@ int fnssl_conv3x3_causal_bf16x(const void* xa_bf16, long long a_sb, long long a_
   p.abl = 0;
   auto k = conv3x3_bf16x_kernel<false>;
 #endif
-  FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k, dim3(8 * per), dim3(512), lds, fnssl::as_stream(stream), p);
-  FNSSL_CHECK_LAUNCH("conv3x3_bf16x_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{k, 512, lds, "conv3x3_bf16x_kernel"}, 8 * per, p);
 }
 
 int fnssl_avgpool_time_bf16(const float* x, int rows, int nt, int c, int k, void* y_bf16, void* stream) {
@@ -530,10 +527,8 @@ int fnssl_avgpool_time_bf16(const float* x, int rows, int nt, int c, int k, void
   if (total == 0) return FNSSL_OK;
   FNSSL_REQUIRE((total + 255) / 256 < (1ll << 31), "avgpool_time_bf16: too large");
   fnssl::TimedLaunch tl("avgpool_time", fnssl::as_stream(stream));
-  hipLaunchKernelGGL(pool_t_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, fnssl::as_stream(stream),
-                     reinterpret_cast<const float4*>(x), rows, nt, c / 4, k, reinterpret_cast<uint2*>(y_bf16));
-  FNSSL_CHECK_LAUNCH("pool_t_bf16_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{pool_t_bf16_kernel, 256, 0, "pool_t_bf16_kernel"}, (unsigned)((total + 255) / 256),
+                 reinterpret_cast<const float4*>(x), rows, nt, c / 4, k, reinterpret_cast<uint2*>(y_bf16));
 }
 
 }  // extern "C"

@@ -23,7 +23,10 @@
 #include <cstring>
 #include <vector>
 
-#include "common.h"
+#include "host.h"
+
+using fnssl::enqueue;
+using fnssl::Kernel;
 
 namespace fnssl {
 int conv3x3_anticausal_f32(const float* xa, long long a_sb, long long a_sf, long long a_st, int ca, const float* xb,
@@ -301,11 +304,9 @@ int fnssl_conv3x3_act_pool_backward(const float* dp, const float* y, int nb, int
   const long long total = rows * nt * (c / 4);
   FNSSL_REQUIRE((total + 255) / 256 < (1ll << 31), "conv3x3_act_pool_backward: too large");
   fnssl::TimedLaunch tl("conv_act_pool_bwd", fnssl::as_stream(stream));
-  hipLaunchKernelGGL(act_pool_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, fnssl::as_stream(stream),
-                     reinterpret_cast<const v4f*>(dp), reinterpret_cast<const v4f*>(y), rows, nt, c / 4, k, act,
-                     reinterpret_cast<v4f*>(dz));
-  FNSSL_CHECK_LAUNCH("act_pool_bwd_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{act_pool_bwd_kernel, 256, 0, "act_pool_bwd_kernel"},
+                 (unsigned)((total + 255) / 256), reinterpret_cast<const v4f*>(dp), reinterpret_cast<const v4f*>(y), rows, nt,
+                 c / 4, k, act, reinterpret_cast<v4f*>(dz));
 }
 
 int fnssl_conv3x3_causal_backward_data(const float* dz, long long z_sb, long long z_sf, long long z_st, int cout,
@@ -378,15 +379,13 @@ int fnssl_conv3x3_weight_grads(const float* dz, long long z_sb, long long z_sf, 
   const int nitems = p.slabs * p.mtiles * p.ntiles;
   {
     fnssl::TimedLaunch tl("conv3x3_wgrad", st, 2.0 * (double)p.rows * cout * p.ncol);
-    hipLaunchKernelGGL(conv_wgrad_kernel, dim3(nitems), dim3(kThreads), 0, st, p);
-    FNSSL_CHECK_LAUNCH("conv_wgrad_kernel");
+    FNSSL_TRY(enqueue(st, Kernel{conv_wgrad_kernel, kThreads, 0, "conv_wgrad_kernel"}, nitems, p));
   }
   const long long total = (long long)cout * p.ncol;
   {
     fnssl::TimedLaunch tl("conv3x3_wgrad_reduce", st);
-    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p.part,
-                       p.slabs, cout, p.cin, dw);
-    FNSSL_CHECK_LAUNCH("conv_wgrad_reduce_kernel");
+    FNSSL_TRY(enqueue(st, Kernel{conv_wgrad_reduce_kernel, 256, 0, "conv_wgrad_reduce_kernel"}, (unsigned)((total + 255) / 256),
+                      p.part, p.slabs, cout, p.cin, dw));
   }
   return FNSSL_OK;
 }

@@ -10,7 +10,10 @@
 // maximum (torch.argmax tie rule), the projection ratio is a second reduction and the
 // residual is updated in place; nothing leaves the chip between sources.
 // HBM-bound and tiny (800 workgroups x 37 x 3072 MACs at config 2).
-#include "common.h"
+#include "host.h"
+
+using fnssl::enqueue;
+using fnssl::Kernel;
 
 namespace {
 
@@ -124,10 +127,8 @@ int fnssl_ipd2doa(const float* pred, long long sb, long long sp, long long st, l
   FNSSL_REQUIRE(lds <= 60 * 1024, "ipd2doa: 2nf*np = %d does not fit the LDS budget", nf2 * np);
   FNSSL_REQUIRE((long long)nb * nt < (1ll << 31), "ipd2doa: too many segments");
   fnssl::TimedLaunch tl("ipd2doa", fnssl::as_stream(stream));
-  hipLaunchKernelGGL(ipd2doa_kernel, dim3(nb * nt), dim3(256), lds, fnssl::as_stream(stream), pred, sb, sp, st, sk, 0ll, bank,
-                     nb, np, nt, nf2, ncand, nsrc, unk_num, ss, idx, vad);
-  FNSSL_CHECK_LAUNCH("ipd2doa_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{ipd2doa_kernel, 256, lds, "ipd2doa_kernel"}, nb * nt, pred, sb, sp, st, sk, 0ll,
+                 bank, nb, np, nt, nf2, ncand, nsrc, unk_num, ss, idx, vad);
 }
 
 // All tracks of IPDnet's output in one launch (reference: PredDOA.pred2DOA calling pred2DOA_track once per track,
@@ -146,10 +147,8 @@ int fnssl_ipd2doa_tracks(const float* pred, long long sb, long long sp, long lon
   FNSSL_REQUIRE(lds <= 60 * 1024, "ipd2doa_tracks: 2nf*np = %d does not fit the LDS budget", nf2 * np);
   FNSSL_REQUIRE((long long)nb * nt < (1ll << 31), "ipd2doa_tracks: too many segments");
   fnssl::TimedLaunch tl("ipd2doa_tracks", fnssl::as_stream(stream));
-  hipLaunchKernelGGL(ipd2doa_kernel, dim3(nb * nt, ntrack), dim3(256), lds, fnssl::as_stream(stream), pred, sb, sp, st, sk, sr,
-                     bank, nb, np, nt, nf2, ncand, nsrc, unk_num, ss, idx, vad);
-  FNSSL_CHECK_LAUNCH("ipd2doa_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{ipd2doa_kernel, 256, lds, "ipd2doa_kernel"}, dim3(nb * nt, ntrack), pred, sb,
+                 sp, st, sk, sr, bank, nb, np, nt, nf2, ncand, nsrc, unk_num, ss, idx, vad);
 }
 
 }  // extern "C"
@@ -230,10 +229,8 @@ extern "C" int fnssl_dpipd_targets(const float* doa, const float* vad, int nb, i
   FNSSL_REQUIRE(np >= 1 && np <= 64, "dpipd_targets: %d microphone pairs (at most 64)", np);
   FNSSL_REQUIRE(nbins >= 2 && bin0 >= 0 && nf_used >= 1 && bin0 + nf_used <= nbins && fre_max > 0.f && speed > 0.f,
                 "dpipd_targets: bins [%d, %d) of %d", bin0, bin0 + nf_used, nbins);
-  hipLaunchKernelGGL(dpipd_targets_kernel, dim3(nb * nseg), dim3(256), 0, fnssl::as_stream(stream), doa, vad, nb, nseg, nvad, ns,
-                     mic_loc, nmic, ch_mode, np, bin0, nf_used, nbins, fre_max, speed, use_vad, ipd, vad_mean);
-  FNSSL_CHECK_LAUNCH("dpipd_targets_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{dpipd_targets_kernel, 256, 0, "dpipd_targets_kernel"}, nb * nseg, doa, vad, nb,
+                 nseg, nvad, ns, mic_loc, nmic, ch_mode, np, bin0, nf_used, nbins, fre_max, speed, use_vad, ipd, vad_mean);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -327,12 +324,9 @@ extern "C" int fnssl_doa_peaks(const float* ss, int nframes, int nele, int nazi,
   FNSSL_REQUIRE(ss && idx && val && count, "doa_peaks: null pointer");
   const size_t lds = (size_t)nele * nazi * 2 * sizeof(float);
   FNSSL_REQUIRE(lds <= 96 * 1024, "doa_peaks: a %d x %d grid does not fit the LDS budget", nele, nazi);
-  if (lds > 48 * 1024)
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(doa_peaks_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   fnssl::TimedLaunch tl("doa_peaks", fnssl::as_stream(stream));
-  hipLaunchKernelGGL(doa_peaks_kernel, dim3(nframes), dim3(256), lds, fnssl::as_stream(stream), ss, nele, nazi, nsrc, idx, val, count);
-  FNSSL_CHECK_LAUNCH("doa_peaks_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{doa_peaks_kernel, 256, lds, "doa_peaks_kernel"}, nframes, ss, nele, nazi, nsrc,
+                 idx, val, count);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -440,8 +434,6 @@ extern "C" int fnssl_ipd2doa_mse_tracks(const float* pred, long long sb, long lo
   if (nt == 0) return FNSSL_OK;
   FNSSL_REQUIRE(pred && bank && ss && idx && vad, "ipd2doa_mse_tracks: null pointer");
   fnssl::TimedLaunch tl("ipd2doa_mse_tracks", fnssl::as_stream(stream));
-  hipLaunchKernelGGL(ipd2doa_mse_kernel, dim3(nb * nt, ntrack), dim3(256), lds, fnssl::as_stream(stream), pred, sb, sp, st, sk,
-                     sr, bank, nb, np, nt, nf2, ncand, nsrc, unk_num, ss, idx, vad);
-  FNSSL_CHECK_LAUNCH("ipd2doa_mse_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{ipd2doa_mse_kernel, 256, lds, "ipd2doa_mse_kernel"}, dim3(nb * nt, ntrack),
+                 pred, sb, sp, st, sk, sr, bank, nb, np, nt, nf2, ncand, nsrc, unk_num, ss, idx, vad);
 }

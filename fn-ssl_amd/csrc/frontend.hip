@@ -15,9 +15,12 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "common.h"
+#include "host.h"
 #include "frontend_core.h"
 #include "tuning.h"
+
+using fnssl::enqueue;
+using fnssl::Kernel;
 
 namespace {
 
@@ -443,34 +446,22 @@ size_t rows_lds_bytes(int nch, int mode) {
   return (size_t)(768 + 512 + rows_waves(nch) * 512 + nch * kXsStride + (mode == 2 ? kNF * 2 * nch : 0)) * sizeof(float);
 }
 
-template <int MODE, int NW>
-int launch_rows_nw(const RowParams& p, const char* name, hipStream_t st) {
-  const size_t lds = rows_lds_bytes(p.nch, MODE);
-  const long long nframes = (long long)p.nb * p.nt;
-  // persistent: as many workgroups as fit the chip at once (LDS- and wave-limited), each walking its share of frames
-  const int per_cu_lds = (int)((160 * 1024) / lds), per_cu_waves = 32 / NW;
-  const int per_cu = per_cu_lds < per_cu_waves ? (per_cu_lds > 0 ? per_cu_lds : 1) : per_cu_waves;
-  long long nblk = (long long)fnssl::device_cus() * per_cu;
-  if (nblk > nframes) nblk = nframes;
-  if (lds > 48 * 1024)
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stft_rows_kernel<MODE, NW>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  fnssl::TimedLaunch tl(name, st);
-  hipLaunchKernelGGL((stft_rows_kernel<MODE, NW>), dim3((unsigned)nblk), dim3(NW * 64), lds, st, p);
-  FNSSL_CHECK_LAUNCH("stft_rows_kernel");
-  return FNSSL_OK;
-}
-
 template <int MODE>
 int launch_rows(const RowParams& p, const char* name, hipStream_t st) {
-  FNSSL_REQUIRE(p.nch <= kRowsMaxCh && rows_lds_bytes(p.nch, MODE) <= 160 * 1024,
-                "front end: the frame-row kernels take at most %d channels (%d given)", kRowsMaxCh, p.nch);
-  FNSSL_REQUIRE((long long)p.nb * p.nt < (1ll << 31), "front end: too many frames");
-  switch (rows_waves(p.nch)) {
-    case 4: return launch_rows_nw<MODE, 4>(p, name, st);
-    case 8: return launch_rows_nw<MODE, 8>(p, name, st);
-    default: return launch_rows_nw<MODE, 16>(p, name, st);
-  }
+  const size_t lds = rows_lds_bytes(p.nch, MODE);
+  FNSSL_REQUIRE(p.nch <= kRowsMaxCh && lds <= 160 * 1024, "front end: the frame-row kernels take at most %d channels (%d given)",
+                kRowsMaxCh, p.nch);
+  const long long nframes = (long long)p.nb * p.nt;
+  FNSSL_REQUIRE(nframes < (1ll << 31), "front end: too many frames");
+  return fnssl::with_value<4, 8, 16>(rows_waves(p.nch), [&](auto NW) {
+    // persistent: as many workgroups as fit the chip at once (LDS- and wave-limited), each walking its share of frames
+    const int per_cu_lds = (int)((160 * 1024) / lds), per_cu_waves = 32 / NW;
+    const int per_cu = per_cu_lds < per_cu_waves ? (per_cu_lds > 0 ? per_cu_lds : 1) : per_cu_waves;
+    long long nblk = (long long)fnssl::device_cus() * per_cu;
+    if (nblk > nframes) nblk = nframes;
+    fnssl::TimedLaunch tl(name, st);
+    return enqueue(st, Kernel{stft_rows_kernel<MODE, NW>, NW * 64, lds, "stft_rows_kernel"}, (unsigned)nblk, p);
+  });
 }
 
 }  // namespace
@@ -531,14 +522,10 @@ int fnssl_stft_ex(const float* sig, int nb, int ns, int nch, long long sb, long 
   const long long nblk = (nframes + kFramesPerBlock - 1) / kFramesPerBlock;
   FNSSL_REQUIRE(nblk < (1ll << 31), "stft: too many frames");
   fnssl::TimedLaunch tl("stft", fnssl::as_stream(stream));
-  if (center)
-    hipLaunchKernelGGL(stft_kernel<true>, dim3((unsigned)nblk), dim3(kFramesPerBlock * 64), 0, fnssl::as_stream(stream),
-                       sig, nb, nch, nt, ns, hop, sb, sn, sc, reinterpret_cast<float2*>(spec), magsum);
-  else
-    hipLaunchKernelGGL(stft_kernel<false>, dim3((unsigned)nblk), dim3(kFramesPerBlock * 64), 0, fnssl::as_stream(stream),
-                       sig, nb, nch, nt, ns, hop, sb, sn, sc, reinterpret_cast<float2*>(spec), magsum);
-  FNSSL_CHECK_LAUNCH("stft_kernel");
-  return FNSSL_OK;
+  return fnssl::with_bool(center, [&](auto CENTER) {
+    return enqueue(fnssl::as_stream(stream), Kernel{stft_kernel<CENTER>, kFramesPerBlock * 64, 0, "stft_kernel"}, (unsigned)nblk, sig,
+                   nb, nch, nt, ns, hop, sb, sn, sc, reinterpret_cast<float2*>(spec), magsum);
+  });
 }
 
 int fnssl_stft(const float* sig, int nb, int ns, int nch, long long sb, long long sn, long long sc, float* spec,
@@ -558,23 +545,18 @@ int fnssl_pair_features(const float* spec, const float* magsum, const float* coe
   {
     fnssl::TimedLaunch tl("ema", st);
     const int n = nb * np;
-    hipLaunchKernelGGL(ema_kernel, dim3((n + kEmaWaves - 1) / kEmaWaves), dim3(kEmaWaves * 64), 0, st, magsum, coef_a,
-                       coef_b, nb, nch, np, nt, ch_mode, mu);
-    FNSSL_CHECK_LAUNCH("ema_kernel");
+    FNSSL_TRY(enqueue(st, Kernel{ema_kernel, kEmaWaves * 64, 0, "ema_kernel"}, (n + kEmaWaves - 1) / kEmaWaves, magsum, coef_a,
+                      coef_b, nb, nch, np, nt, ch_mode, mu));
   }
   {
     fnssl::TimedLaunch tl("pack", st);
     const long long rows = (long long)nb * np * nt;
     FNSSL_REQUIRE(rows < (1ll << 31), "pair_features: too many rows");
-    if (layout == 0)
-      hipLaunchKernelGGL(pack_kernel<0>, dim3((unsigned)rows), dim3(256), 0, st,
-                         reinterpret_cast<const float2*>(spec), mu, nb, nch, np, nt, ch_mode, eps, x);
-    else
-      hipLaunchKernelGGL(pack_kernel<1>, dim3((unsigned)rows), dim3(256), 0, st,
-                         reinterpret_cast<const float2*>(spec), mu, nb, nch, np, nt, ch_mode, eps, x);
-    FNSSL_CHECK_LAUNCH("pack_kernel");
+    return fnssl::with_value<0, 1>(layout, [&](auto LAYOUT) {
+      return enqueue(st, Kernel{pack_kernel<LAYOUT>, 256, 0, "pack_kernel"}, (unsigned)rows, reinterpret_cast<const float2*>(spec), mu,
+                     nb, nch, np, nt, ch_mode, eps, x);
+    });
   }
-  return FNSSL_OK;
 }
 
 int fnssl_array_features(const float* spec, const float* magsum, const float* coef_a, const float* coef_b,
@@ -585,32 +567,22 @@ int fnssl_array_features(const float* spec, const float* magsum, const float* co
   hipStream_t st = fnssl::as_stream(stream);
   {
     fnssl::TimedLaunch tl("ema", st);
-    hipLaunchKernelGGL(ema_array_kernel, dim3((nb + kEmaWaves - 1) / kEmaWaves), dim3(kEmaWaves * 64), 0, st, magsum,
-                       coef_a, coef_b, nb, nch, nt, mu);
-    FNSSL_CHECK_LAUNCH("ema_array_kernel");
+    FNSSL_TRY(enqueue(st, Kernel{ema_array_kernel, kEmaWaves * 64, 0, "ema_array_kernel"}, (nb + kEmaWaves - 1) / kEmaWaves,
+                      magsum, coef_a, coef_b, nb, nch, nt, mu));
   }
   {
     fnssl::TimedLaunch tl("pack", st);
     const long long rows = (long long)nb * nt;
     FNSSL_REQUIRE(rows < (1ll << 31), "array_features: too many rows");
-    {
-      const size_t lds = (size_t)kNF * 2 * nch * sizeof(float);
-      FNSSL_REQUIRE(lds <= 160 * 1024, "array_features: %d channels do not fit the staging row", nch);
-      if (lds > 48 * 1024)
-        FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(pack_array_kernel<0>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    const size_t lds = (size_t)kNF * 2 * nch * sizeof(float);
+    FNSSL_REQUIRE(lds <= 160 * 1024, "array_features: %d channels do not fit the staging row", nch);
     if (layout == 0)
-      hipLaunchKernelGGL(pack_array_kernel<0>, dim3((unsigned)rows), dim3(256), (size_t)kNF * 2 * nch * sizeof(float), st,
-                         reinterpret_cast<const float2*>(spec), mu, nch, nt, eps, x);
-    else {
-      FNSSL_REQUIRE((long long)nb * nch < 65536, "array_features: nb * nch too large for one launch");
-      hipLaunchKernelGGL(pack_array_planes_kernel, dim3((nt + 63) / 64, kNF / 32, nb * nch), dim3(256), 0, st,
-                         reinterpret_cast<const float2*>(spec), mu, nch, nt, eps, x);
-    }
-    FNSSL_CHECK_LAUNCH("pack_array_kernel");
+      return enqueue(st, Kernel{pack_array_kernel<0>, 256, lds, "pack_array_kernel"}, (unsigned)rows,
+                     reinterpret_cast<const float2*>(spec), mu, nch, nt, eps, x);
+    FNSSL_REQUIRE((long long)nb * nch < 65536, "array_features: nb * nch too large for one launch");
+    return enqueue(st, Kernel{pack_array_planes_kernel, 256, 0, "pack_array_planes_kernel"}, dim3((nt + 63) / 64, kNF / 32, nb * nch),
+                   reinterpret_cast<const float2*>(spec), mu, nch, nt, eps, x);
   }
-  return FNSSL_OK;
 }
 
 int fnssl_array_frontend(const float* sig, int nb, int ns, int nch, long long sb, long long sn, long long sc, int hop,
@@ -632,15 +604,11 @@ int fnssl_array_frontend(const float* sig, int nb, int ns, int nch, long long sb
   p.mu = mu;
   p.eps = eps;
   p.x = x;
-  {
-    const int rc = launch_rows<1>(p, "stft", st);
-    if (rc != FNSSL_OK) return rc;
-  }
+  FNSSL_TRY(launch_rows<1>(p, "stft", st));
   {
     fnssl::TimedLaunch tl("ema", st);
-    hipLaunchKernelGGL(ema_array_kernel, dim3((nb + kEmaWaves - 1) / kEmaWaves), dim3(kEmaWaves * 64), 0, st, magsum,
-                       coef_a, coef_b, nb, nch, nt, mu);
-    FNSSL_CHECK_LAUNCH("ema_array_kernel");
+    FNSSL_TRY(enqueue(st, Kernel{ema_array_kernel, kEmaWaves * 64, 0, "ema_array_kernel"}, (nb + kEmaWaves - 1) / kEmaWaves,
+                      magsum, coef_a, coef_b, nb, nch, nt, mu));
   }
   return launch_rows<2>(p, "pack", st);
 }
@@ -649,10 +617,8 @@ int fnssl_nchw_to_seq(const float* x, int n, int c, int nf, int nt, float* y, vo
   FNSSL_REQUIRE(x && y && n > 0 && c > 0 && nf > 0 && nt > 0, "nchw_to_seq: bad arguments");
   FNSSL_REQUIRE((long long)n * c < 65536, "nchw_to_seq: n*c too large for one launch");
   fnssl::TimedLaunch tl("nchw_to_seq", fnssl::as_stream(stream));
-  hipLaunchKernelGGL(nchw_to_seq_kernel, dim3((nt + 31) / 32, (nf + 31) / 32, n * c), dim3(256), 0,
-                     fnssl::as_stream(stream), x, c, nf, nt, y);
-  FNSSL_CHECK_LAUNCH("nchw_to_seq_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{nchw_to_seq_kernel, 256, 0, "nchw_to_seq_kernel"},
+                 dim3((nt + 31) / 32, (nf + 31) / 32, n * c), x, c, nf, nt, y);
 }
 
 }  // extern "C"

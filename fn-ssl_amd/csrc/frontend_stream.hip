@@ -15,8 +15,11 @@
 // SAME workgroup behind the workgroup barrier, whose workgroup-scope release / acquire is all that needs (one CU, one L1).
 #include <cstdint>
 
-#include "common.h"
+#include "host.h"
 #include "frontend_core.h"
+
+using fnssl::enqueue;
+using fnssl::Kernel;
 
 namespace {
 
@@ -211,16 +214,10 @@ int fnssl_stream_frontend(const float* sig, int nb, int ns, int nch, long long s
   p.x = x;
   const size_t lds = fixed_lds_floats(nch, p.nchain, p.tile) * sizeof(float) + (in_lds ? spectra_bytes(nch, p.tile) : 0);
   hipStream_t st = fnssl::as_stream(stream);
-  const void* fn = mode == FNSSL_STREAM_ARRAY ? reinterpret_cast<const void*>(stream_frontend_kernel<1>)
-                                              : reinterpret_cast<const void*>(stream_frontend_kernel<0>);
-  if (lds > 48 * 1024) FNSSL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   fnssl::TimedLaunch tl("stream_frontend", st);
-  if (mode == FNSSL_STREAM_ARRAY)
-    hipLaunchKernelGGL(stream_frontend_kernel<1>, dim3((unsigned)nb), dim3(kStreamThreads), lds, st, p);
-  else
-    hipLaunchKernelGGL(stream_frontend_kernel<0>, dim3((unsigned)nb), dim3(kStreamThreads), lds, st, p);
-  FNSSL_CHECK_LAUNCH("stream_frontend_kernel");
-  return FNSSL_OK;
+  return fnssl::with_bool(mode == FNSSL_STREAM_ARRAY, [&](auto ARRAY) {
+    return enqueue(st, Kernel{stream_frontend_kernel<ARRAY>, kStreamThreads, lds, "stream_frontend_kernel"}, (unsigned)nb, p);
+  });
 }
 
 }  // extern "C"

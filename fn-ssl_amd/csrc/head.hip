@@ -3,7 +3,10 @@
 // (Model.py:70-71,88-89).  HBM-bound: the head reads the last narrow-band
 // output once (1 KiB rows, one wave per (pair, bin, segment), float4 per lane)
 // and reduces 256 channels with wavefront shuffles.
-#include "common.h"
+#include "host.h"
+
+using fnssl::enqueue;
+using fnssl::Kernel;
 
 namespace {
 
@@ -82,10 +85,8 @@ int fnssl_head(const float* x, int nb, int nf, int nt, const float* w, const flo
   const long long nblk = (nitems + 3) / 4;
   FNSSL_REQUIRE(nblk < (1ll << 31), "head: too many items");
   fnssl::TimedLaunch tl("head", fnssl::as_stream(stream));
-  hipLaunchKernelGGL(head_kernel, dim3((unsigned)nblk), dim3(256), 0, fnssl::as_stream(stream), x, nb, nf, nt,
-                     nt2, w, b, out);
-  FNSSL_CHECK_LAUNCH("head_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{head_kernel, 256, 0, "head_kernel"}, (unsigned)nblk, x, nb, nf, nt, nt2, w, b,
+                 out);
 }
 
 int fnssl_linear(const float* x, int m, int k, const float* wt, const float* b, int n_out, float* y,
@@ -94,10 +95,8 @@ int fnssl_linear(const float* x, int m, int k, const float* wt, const float* b, 
   FNSSL_REQUIRE(m >= 0 && k > 0 && n_out > 0 && k <= 8192, "linear: bad shape (m %d, k %d, n %d)", m, k, n_out);
   if (m == 0) return FNSSL_OK;
   fnssl::TimedLaunch tl("linear", fnssl::as_stream(stream));
-  hipLaunchKernelGGL(linear_kernel, dim3(m), dim3(192), k * sizeof(float), fnssl::as_stream(stream), x, k, wt, b,
-                     n_out, y);
-  FNSSL_CHECK_LAUNCH("linear_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{linear_kernel, 192, k * sizeof(float), "linear_kernel"}, m, x, k, wt, b, n_out,
+                 y);
 }
 
 }  // extern "C"

@@ -11,11 +11,15 @@
 //
 // All three are HBM- or latency-bound and small beside the network's step; they exist so that a batch of
 // (waveforms, {doa, dp_signal}) becomes a loss without a host round trip.
-#include "common.h"
+#include "host.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+
+using fnssl::aligned16;
+using fnssl::enqueue;
+using fnssl::Kernel;
 
 namespace {
 
@@ -352,7 +356,6 @@ targets2_kernel(const float* __restrict__ doa, const float* __restrict__ distanc
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 
@@ -400,20 +403,11 @@ int fnssl_pit_mse_loss(const float* pred, const long long* pred_strides, const f
   fnssl::TimedLaunch tl("pit_mse", st);
   float* row_min = static_cast<float*>(workspace);
   const float gscale = 2.0f / (float)n_total;
-#define FNSSL_PIT_LAUNCH(N)                                                                                              \
-  hipLaunchKernelGGL(pit_row_kernel<N>, dim3((unsigned)rows), dim3(256), 0, st, pred, ps, pkind, gt, gkind, nt2, nm1, (int)D, \
-                     gscale, dpred, row_min, perm_out)
-  switch (nsrc) {
-    case 1: FNSSL_PIT_LAUNCH(1); break;
-    case 2: FNSSL_PIT_LAUNCH(2); break;
-    case 3: FNSSL_PIT_LAUNCH(3); break;
-    default: FNSSL_PIT_LAUNCH(4); break;
-  }
-#undef FNSSL_PIT_LAUNCH
-  FNSSL_CHECK_LAUNCH("pit_row_kernel");
-  hipLaunchKernelGGL(pit_loss_kernel, dim3(1), dim3(256), 0, st, row_min, (int)rows, (float)n_total, loss, accumulate);
-  FNSSL_CHECK_LAUNCH("pit_loss_kernel");
-  return FNSSL_OK;
+  FNSSL_TRY(fnssl::with_value<1, 2, 3, 4>(nsrc, [&](auto N) {
+    return enqueue(st, Kernel{pit_row_kernel<N>, 256, 0, "pit_row_kernel"}, (unsigned)rows, pred, ps, pkind, gt, gkind, nt2, nm1, (int)D,
+                   gscale, dpred, row_min, perm_out);
+  }));
+  return enqueue(st, Kernel{pit_loss_kernel, 256, 0, "pit_loss_kernel"}, 1, row_min, (int)rows, (float)n_total, loss, accumulate);
 }
 
 int fnssl_dp_vad(const float* mix_spec, const float* dp_spec, int nb, int nch, int nsrc, int nt, float* dp_vad, void* stream) {
@@ -424,10 +418,8 @@ int fnssl_dp_vad(const float* mix_spec, const float* dp_spec, int nb, int nch, i
   FNSSL_REQUIRE((long long)nb * nseg * nsrc <= 0x7fffffffLL, "dp_vad: %d x %d x %d outputs is out of range", nb, nseg, nsrc);
   hipStream_t st = fnssl::as_stream(stream);
   fnssl::TimedLaunch tl("dp_vad", st);
-  hipLaunchKernelGGL(dp_vad_kernel, dim3(nb * nseg * nsrc), dim3(256), 0, st, reinterpret_cast<const float2*>(mix_spec),
-                     reinterpret_cast<const float2*>(dp_spec), nch, nsrc, nt, nseg, dp_vad);
-  FNSSL_CHECK_LAUNCH("dp_vad_kernel");
-  return FNSSL_OK;
+  return enqueue(st, Kernel{dp_vad_kernel, 256, 0, "dp_vad_kernel"}, nb * nseg * nsrc, reinterpret_cast<const float2*>(mix_spec),
+                 reinterpret_cast<const float2*>(dp_spec), nch, nsrc, nt, nseg, dp_vad);
 }
 
 int fnssl_ipdnet_targets(const float* doa, const float* dp_vad, int nb, int nseg, int nsrc, const float* mic_loc, int nmic,
@@ -443,10 +435,8 @@ int fnssl_ipdnet_targets(const float* doa, const float* dp_vad, int nb, int nseg
   FNSSL_REQUIRE(vad_th == vad_th, "ipdnet_targets: the VAD threshold is NaN");
   hipStream_t st = fnssl::as_stream(stream);
   fnssl::TimedLaunch tl("ipdnet_targets", st);
-  hipLaunchKernelGGL(targets_kernel, dim3(nb * nseg), dim3(256), 0, st, doa, dp_vad, mic_loc, non_source, nsrc, nmic - 1, bin0,
-                     nf_used, nbins, fre_max, speed, vad_th, ipd);
-  FNSSL_CHECK_LAUNCH("targets_kernel");
-  return FNSSL_OK;
+  return enqueue(st, Kernel{targets_kernel, 256, 0, "targets_kernel"}, nb * nseg, doa, dp_vad, mic_loc, non_source, nsrc,
+                 nmic - 1, bin0, nf_used, nbins, fre_max, speed, vad_th, ipd);
 }
 
 int fnssl_ipdnet2_targets(const float* doa, const float* distance, const float* vad, int nb, int nseg, int nsrc,
@@ -462,10 +452,8 @@ int fnssl_ipdnet2_targets(const float* doa, const float* distance, const float* 
   FNSSL_REQUIRE(vad_th == vad_th, "ipdnet2_targets: the VAD threshold is NaN");
   hipStream_t st = fnssl::as_stream(stream);
   fnssl::TimedLaunch tl("ipdnet2_targets", st);
-  hipLaunchKernelGGL(targets2_kernel, dim3(nb * nseg), dim3(256), 0, st, doa, distance, vad, mic_loc, non_source, nsrc, nmic - 1,
-                     bin0, nf_used, nbins, fre_max, speed, vad_th, ipd);
-  FNSSL_CHECK_LAUNCH("targets2_kernel");
-  return FNSSL_OK;
+  return enqueue(st, Kernel{targets2_kernel, 256, 0, "targets2_kernel"}, nb * nseg, doa, distance, vad, mic_loc, non_source, nsrc,
+                 nmic - 1, bin0, nf_used, nbins, fre_max, speed, vad_th, ipd);
 }
 
 }  // extern "C"

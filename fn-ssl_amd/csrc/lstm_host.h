@@ -1,12 +1,10 @@
-// Host-only side of the LSTM kernels, shared by every family: the one launch path (LDS limit, occupancy check of a cluster
-// kernel, planning queries, launch — the launch_*_k templates beside the kernels keep their static_assert, LDS and grid
-// formulas and the kernel's address), the cluster-then-guarded-fallback protocol, and the descriptor checks.
+// Host-only side of the LSTM kernels, shared by every family: what only they need on top of the library's launch path
+// (host.h, re-exported here — the launch_*_k templates beside the kernels keep their static_assert, LDS and grid formulas
+// and the kernel's address): the shape-table codes, the cluster knobs, the cluster-then-guarded-fallback protocol, and the
+// extent checks.
 #pragma once
 
-#include <cstdint>
-#include <type_traits>
-
-#include "common.h"
+#include "host.h"
 #include "tuning.h"
 
 namespace fnssl_lstm {
@@ -16,33 +14,12 @@ constexpr int kNoStatic = -100;    // returned by a shape table: no specialisati
 // runs the per-wave / pair-split kernels instead, unguarded
 constexpr int kNoCluster = -101;
 
-// dry = a planning query (fnssl_lstm_plan, fnssl_lstm_backward_plan): every decision of the real call is taken, nothing
-// is enqueued and the stream is never touched
-struct LaunchCtx {
-  hipStream_t st;
-  bool dry;
-};
-
-template <class... P>
-struct Kernel {
-  void (*fn)(P...);
-  int threads;            // per workgroup
-  size_t lds;             // dynamic LDS bytes
-  const char* name;       // for error messages
-  bool cluster = false;   // every workgroup of the grid must be resident at once
-};
-template <class... P>
-Kernel(void (*)(P...), int, size_t, const char*, bool = false) -> Kernel<P...>;
-
-// runtime.hip.  dry -> FNSSL_OK at once; else raise the LDS limit (above 48 KB), launch, check.  A cluster kernel: raise the
-// limit (the occupancy query needs it), kNoCluster unless `nwg` workgroups fit the device at once, then as above.
-int enqueue_args(const LaunchCtx& lc, const void* fn, int threads, size_t lds, const char* name, bool cluster, int nwg, void** args);
-
-template <class... P>
-int enqueue(const LaunchCtx& lc, const Kernel<P...>& k, int nwg, const std::common_type_t<P>&... args) {
-  void* argv[] = {const_cast<void*>(static_cast<const void*>(&args))...};
-  return enqueue_args(lc, reinterpret_cast<const void*>(k.fn), k.threads, k.lds, k.name, k.cluster, nwg, argv);
-}
+using fnssl::aligned16;
+using fnssl::check_workspace;
+using fnssl::enqueue;
+using fnssl::Kernel;
+using fnssl::LaunchCtx;
+using fnssl::WsRegion;
 
 // Knobs of the cluster kernels' bounded waits (fnssl_tuning): CLUSTER_SPIN_LIMIT (spins before a wave gives up),
 // CLUSTER_TEST_STALL = m + 1 (fault injection: member m of cluster 0 exits at once, as if it never became resident).
@@ -83,16 +60,6 @@ int cluster_then_fallback(const LaunchCtx& lc, bool handles, int cluster_family,
 }
 
 // ---- descriptor checks ------------------------------------------------------------------------------------------------
-// one region of a workspace layout (lstm.hip, lstm_train.hip), in bytes from the workspace's start
-struct WsRegion {
-  size_t off, bytes;
-  size_t end() const { return off + bytes; }
-};
-
-template <class... T>
-bool aligned16(const T*... p) {
-  return (((reinterpret_cast<uintptr_t>(p) & 15) == 0) && ...);
-}
 inline bool mult4(long long so, long long si, long long st) { return ((so | si | st) & 3) == 0; }
 inline bool mult4(const fnssl_view& v) { return mult4(v.so, v.si, v.st); }
 inline bool nonneg(long long so, long long si, long long st) { return so >= 0 && si >= 0 && st >= 0; }
@@ -101,11 +68,5 @@ inline bool extent_ok(long long so, long long si, long long st, long long width,
   return nonneg(so, si, st) && ((long double)so + 16.0L * si + (long double)nsteps * st + width) * 4.0L < 4.0e9L;
 }
 inline bool extent_ok(const fnssl_view& v, long long width, int nsteps) { return extent_ok(v.so, v.si, v.st, width, nsteps); }
-// FNSSL_E_WORKSPACE (with the message) unless the caller's workspace holds `need` bytes
-inline int check_workspace(const char* who, const void* workspace, size_t bytes, size_t need) {
-  if (workspace && bytes >= need) return FNSSL_OK;
-  fnssl::set_error("%s: workspace %zu < %zu bytes", who, bytes, need);
-  return FNSSL_E_WORKSPACE;
-}
 
 }  // namespace fnssl_lstm

@@ -28,7 +28,10 @@
 // in the same order, so exact ties fall the same way (tests/test_doa_metrics_host.py compares the restatement with
 // scipy on tie-heavy matrices where scipy is installed).  Among valid pairs, totals that differ only by rounding are
 // not protected: the fixtures keep them apart.
-#include "common.h"
+#include "host.h"
+
+using fnssl::enqueue;
+using fnssl::Kernel;
 
 namespace {
 
@@ -347,15 +350,13 @@ extern "C" int fnssl_doa_metrics_ex(const float* doa_gt, const long long* doa_gt
   hipStream_t s = fnssl::as_stream(stream);
   {
     fnssl::TimedLaunch tl("doa_metrics_utt", s);
-    hipLaunchKernelGGL(doa_metrics_utt_kernel, dim3(nb), dim3(64), 0, s, dg, vg, de, ve, nt, ns_gt, ns_est, mode, ae_modes, ae_th,
-                       vad_th_gt, vad_th_est, use_vad, gt_radians, est_radians, est_below, ratio_eps, large_number, eps, per_utt, k_gt,
-                       k_est, k_corr);
-    FNSSL_CHECK_LAUNCH("doa_metrics_utt_kernel");
+    FNSSL_TRY(enqueue(s, Kernel{doa_metrics_utt_kernel, 64, 0, "doa_metrics_utt_kernel"}, nb, dg, vg, de, ve, nt, ns_gt, ns_est,
+                      mode, ae_modes, ae_th, vad_th_gt, vad_th_est, use_vad, gt_radians, est_radians, est_below, ratio_eps,
+                      large_number, eps, per_utt, k_gt, k_est, k_corr));
   }
   fnssl::TimedLaunch tl("doa_metrics_batch", s);
-  hipLaunchKernelGGL(doa_metrics_batch_kernel, dim3(1), dim3(64), 0, s, per_utt, k_gt, k_corr, nb, mode, ae_modes, metrics);
-  FNSSL_CHECK_LAUNCH("doa_metrics_batch_kernel");
-  return FNSSL_OK;
+  return enqueue(s, Kernel{doa_metrics_batch_kernel, 64, 0, "doa_metrics_batch_kernel"}, 1, per_utt, k_gt, k_corr, nb, mode,
+                 ae_modes, metrics);
 }
 
 // The entry point of before the _ex form: estimates active ABOVE their threshold, bare K_gt denominators, one unit for

@@ -153,32 +153,36 @@ TimedLaunch::~TimedLaunch() {
 
 }  // namespace fnssl
 
-// ---- the launch path of the LSTM kernels (lstm_host.h) -------------------------------------------------------------
-namespace fnssl_lstm {
+// ---- the launch path of every kernel (host.h) ----------------------------------------------------------------------
+namespace fnssl {
 
 // blocks the device can hold at once for this kernel (occupancy query x CUs) >= grid?  One query per call: cheap (host only).
-static bool cluster_grid_fits(const void* kernel, int threads, size_t lds, int grid) {
+static bool cluster_grid_fits(const void* kernel, int threads, size_t lds, long long nwg) {
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds) != hipSuccess) {
     (void)hipGetLastError();
     return false;
   }
-  return (long long)per_cu * cluster_cus() >= grid;
+  return (long long)per_cu * fnssl_lstm::cluster_cus() >= nwg;
 }
 
-int enqueue_args(const LaunchCtx& lc, const void* fn, int threads, size_t lds, const char* name, bool cluster, int nwg, void** args) {
+int enqueue_args(const LaunchCtx& lc, const void* fn, int threads, size_t lds, const char* name, bool cluster, dim3 grid, void** args) {
   if (lc.dry && !cluster) return FNSSL_OK;   // a planning query: nothing to ask the runtime
   if (lds > 48 * 1024) FNSSL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   // a cluster kernel's grid may not exceed what the device says it can hold (its waits are bounded and the call carries a
   // guarded fallback anyway — this only avoids a launch that cannot work); a query reports the family only after this check
-  if (cluster && !cluster_grid_fits(fn, threads, lds, nwg)) return kNoCluster;
+  if (cluster && !cluster_grid_fits(fn, threads, lds, (long long)grid.x * grid.y * grid.z)) return fnssl_lstm::kNoCluster;
   if (lc.dry) return FNSSL_OK;
-  (void)hipLaunchKernel(fn, dim3(nwg), dim3(threads), args, lds, lc.st);   // (FNSSL_CHECK_LAUNCH reads its status)
-  FNSSL_CHECK_LAUNCH(name);
+  (void)hipLaunchKernel(fn, grid, dim3(threads), args, lds, lc.st);   // (its status is read just below)
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error("launch of %s failed: %s", name, hipGetErrorString(e));
+    return FNSSL_E_HIP;
+  }
   return FNSSL_OK;
 }
 
-}  // namespace fnssl_lstm
+}  // namespace fnssl
 
 extern "C" int fnssl_tuning_set(const fnssl_tuning* t) {
   FNSSL_REQUIRE(!t || t->struct_bytes == sizeof(fnssl_tuning), "tuning_set: struct_bytes %u, this library's fnssl_tuning has %zu",
@@ -216,16 +220,12 @@ __global__ void __launch_bounds__(64) occupy_kernel(unsigned* stop, long long ma
 extern "C" int fnssl_occupy_cus(int nblocks, int lds_bytes, unsigned* stop, int max_ms, void* stream) {
   FNSSL_REQUIRE(nblocks > 0 && nblocks <= 4096 && lds_bytes >= 0 && lds_bytes <= 160 * 1024 && max_ms > 0 && max_ms <= 60000,
                 "occupy_cus: nblocks %d, lds %d B, limit %d ms", nblocks, lds_bytes, max_ms);
-  if (lds_bytes > 48 * 1024)
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(occupy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
   int rate_khz = 100000;   // wall_clock64 ticks: the constant "wall clock" counter, 100 MHz on gfx9
   int dev = 0;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev);
   if (rate_khz <= 0) rate_khz = 100000;
-  hipLaunchKernelGGL(occupy_kernel, dim3(nblocks), dim3(64), (size_t)lds_bytes, fnssl::as_stream(stream), stop,
-                     (long long)max_ms * rate_khz);
-  FNSSL_CHECK_LAUNCH("occupy_kernel");
-  return FNSSL_OK;
+  return fnssl::enqueue(fnssl::as_stream(stream), fnssl::Kernel{occupy_kernel, 64, (size_t)lds_bytes, "occupy_kernel"}, nblocks, stop,
+                        (long long)max_ms * rate_khz);
 }
 
 extern "C" const char* fnssl_tuning_name(int index) {
@@ -281,8 +281,9 @@ int fnssl_mfma_f32_peak_clocks(float* out, size_t out_floats, int iters, int wav
   const int nblk = fnssl::device_cus() * waves_per_simd;
   FNSSL_REQUIRE(out_floats >= (size_t)nblk * 256, "mfma_f32_peak: out needs %zu floats", (size_t)nblk * 256);
   FNSSL_REQUIRE(!clocks || clocks_len >= (size_t)nblk * 3, "mfma_f32_peak: clocks needs %zu entries", (size_t)nblk * 3);
-  hipLaunchKernelGGL(mfma_f32_peak_kernel, dim3(nblk), dim3(256), 0, fnssl::as_stream(stream), out, iters, clocks);
-  FNSSL_CHECK_LAUNCH("mfma_f32_peak_kernel");
+  if (const int rc = fnssl::enqueue(fnssl::as_stream(stream), fnssl::Kernel{mfma_f32_peak_kernel, 256, 0, "mfma_f32_peak_kernel"}, nblk,
+                                    out, iters, clocks))
+    return rc;
   *flop = (double)nblk * 4 * (double)iters * 64 * (2.0 * 16 * 16 * 4);
   return FNSSL_OK;
 }

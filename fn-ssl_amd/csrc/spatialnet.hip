@@ -28,7 +28,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "host.h"
 #include "tuning.h"
 
 namespace {
@@ -1782,17 +1782,40 @@ inline bool out_ok(const float* p, long long sb, long long st, long long sf) {
 }
 inline unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256); }
 
-struct MambaWs {
-  float *xz, *dbl, *y;
+using fnssl::check_workspace;
+using fnssl::enqueue;
+using fnssl::Kernel;
+using fnssl::with_bool;
+using fnssl::with_value;
+using fnssl::WsRegion;
+
+// The regions of a workspace, front to back: the one description behind its size, its check and its carve-up.
+struct MambaWsLayout {            // fnssl_sn_mamba, npts = nb * nt * nf points
+  WsRegion xz, dbl, y;            // [npts, 2E], [npts, XP], [npts, E]
+  size_t total;
+  explicit MambaWsLayout(long long npts) {
+    const size_t pt = (size_t)npts * sizeof(float);
+    xz = {0, pt * 2 * E};
+    dbl = {xz.end(), pt * XP};
+    y = {dbl.end(), pt * E};
+    total = y.end();
+  }
 };
-inline size_t mamba_ws_floats(long long npts) { return (size_t)npts * (2 * E + XP + E); }
-inline MambaWs carve_mamba(float* ws, long long npts) {
-  MambaWs m;
-  m.xz = ws;
-  m.dbl = ws + npts * (2 * E);
-  m.y = m.dbl + npts * XP;
-  return m;
-}
+struct SnWsLayout {               // fnssl_sn_forward
+  WsRegion a0, a1, a2, a3;        // [nb, nt, nf, H], [nb, nt, nf/2, H], [nb, nt, nf/16, H], [nb, nt/ratio, nf/16, H]
+  WsRegion mamba;                 // MambaWsLayout of the widest block
+  size_t total;                   // with the slack for rounding the caller's pointer up to 256 bytes
+  SnWsLayout(int nb, int nf, int nt, int ratio) {
+    const size_t fr = (size_t)nb * nt, row = H * sizeof(float);
+    const int nfc = nf / 16, nt2 = nt / ratio;
+    a0 = {0, fr * nf * row};
+    a1 = {a0.end(), fr * (nf / 2) * row};
+    a2 = {a1.end(), fr * nfc * row};
+    a3 = {a2.end(), (size_t)nb * (nt2 > 0 ? nt2 : 1) * nfc * row};
+    mamba = {a3.end(), MambaWsLayout((long long)nb * nt * nfc).total};
+    total = mamba.end() + 256;
+  }
+};
 
 }  // namespace
 
@@ -1815,10 +1838,8 @@ int fnssl_sn_layernorm(const float* x, long long rows, int h, const float* w, co
   if (rows == 0) return FNSSL_OK;
   FNSSL_REQUIRE((rows + 3) / 4 < (1ll << 31), "sn_layernorm: too many rows");
   fnssl::TimedLaunch tl("sn_layernorm", fnssl::as_stream(stream));
-  hipLaunchKernelGGL(sn_layernorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, fnssl::as_stream(stream), x,
-                     rows, h, w, b, eps, y);
-  FNSSL_CHECK_LAUNCH("sn_layernorm_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{sn_layernorm_kernel, 256, 0, "sn_layernorm_kernel"}, (unsigned)((rows + 3) / 4), x,
+                 rows, h, w, b, eps, y);
 }
 
 int fnssl_sn_encoder(const float* x, long long x_sb, long long x_sc, long long x_sf, long long x_st, int nb, int cin,
@@ -1844,36 +1865,27 @@ int fnssl_sn_encoder(const float* x, long long x_sb, long long x_sc, long long x
     FNSSL_REQUIRE(!bf || (kk <= 160 && off32), "sn_encoder: FNSSL_PRECISION_BF16 needs cin * 5 <= 160 (cin %d) and 32-bit offsets",
                   cin);
     if ((bf || !fnssl::tune(FNSSL_TUNE_SN_SCALAR)) && kk <= 160 && off32) {
-#define FNSSL_SN_ENC_P(KP, BF, PIPE)                                                                                \
-  do {                                                                                                              \
-    const size_t lds = (size_t)(w_lds_floats<KP, H, BF>() + H) * sizeof(float);                                     \
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sn_encoder_mfma_kernel<KP, BF, PIPE>),              \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                          \
-    hipLaunchKernelGGL((sn_encoder_mfma_kernel<KP, BF, PIPE>), dim3(mfma_grid(npts, 2)), dim3(512), lds, s, x, x_sb, \
-                       x_sc, x_sf, x_st, cin, nf, nt, npts, wT, bias, state_in, out, o_sb, o_st, o_sf);             \
-  } while (0)
-#define FNSSL_SN_ENC(KP, BF)                                                                                        \
-  do {                                                                                                              \
-    if (!state_in && nt >= KE - 1 && pos32) FNSSL_SN_ENC_P(KP, BF, true); else FNSSL_SN_ENC_P(KP, BF, false);       \
-  } while (0)
-      if (kk <= 80) {
-        if (bf) FNSSL_SN_ENC(80, true); else FNSSL_SN_ENC(80, false);
-      } else {
-        if (bf) FNSSL_SN_ENC(160, true); else FNSSL_SN_ENC(160, false);
-      }
-#undef FNSSL_SN_ENC_P
-#undef FNSSL_SN_ENC
+      const bool pipe = !state_in && nt >= KE - 1 && pos32;
+      FNSSL_TRY(with_value<80, 160>(kk <= 80 ? 80 : 160, [&](auto KP_) {
+        constexpr int KP = KP_;
+        return with_bool(bf, [&](auto BF_) {
+          constexpr bool BF = BF_;
+          return with_bool(pipe, [&](auto PIPE) {
+            const size_t lds = (size_t)(w_lds_floats<KP, H, BF>() + H) * sizeof(float);
+            return enqueue(s, Kernel{sn_encoder_mfma_kernel<KP, BF, PIPE>, 512, lds, "sn_encoder_mfma_kernel"}, mfma_grid(npts, 2), x,
+                           x_sb, x_sc, x_sf, x_st, cin, nf, nt, npts, wT, bias, state_in, out, o_sb, o_st, o_sf);
+          });
+        });
+      }));
     } else {
-      hipLaunchKernelGGL(sn_encoder_kernel, dim3(blocks_of(npts)), dim3(256), 0, s, x, x_sb, x_sc, x_sf, x_st, cin, nf, nt,
-                         npts, wT, bias, state_in, out, o_sb, o_st, o_sf);
+      FNSSL_TRY(enqueue(s, Kernel{sn_encoder_kernel, 256, 0, "sn_encoder_kernel"}, blocks_of(npts), x, x_sb, x_sc, x_sf, x_st, cin, nf,
+                        nt, npts, wT, bias, state_in, out, o_sb, o_st, o_sf));
     }
-    FNSSL_CHECK_LAUNCH("sn_encoder_kernel");
   }
   if (state_out) {
     const long long nrows = (long long)nb * cin * nf;
-    hipLaunchKernelGGL(sn_encoder_state_kernel, dim3(blocks_of(nrows)), dim3(256), 0, s, x, x_sb, x_sc, x_sf, x_st, cin,
-                       nf, nt, nrows, state_in, state_out);
-    FNSSL_CHECK_LAUNCH("sn_encoder_state_kernel");
+    FNSSL_TRY(enqueue(s, Kernel{sn_encoder_state_kernel, 256, 0, "sn_encoder_state_kernel"}, blocks_of(nrows), x, x_sb, x_sc, x_sf,
+                      x_st, cin, nf, nt, nrows, state_in, state_out));
   }
   return FNSSL_OK;
 }
@@ -1900,30 +1912,16 @@ int fnssl_sn_fconv(const fnssl_btf_view* x, int nb, int nt, int nf, const fnssl_
   const size_t lds = (size_t)(NG * (bf ? w_lds_floats<64, 16, true>() : w_lds_floats<64, 16, false>()) + 4 * H +
                               (256 + 4 * (256 >> lg)) * 100) * sizeof(float);
   const long long cus = fnssl::device_cus();
-#define FNSSL_SN_FCONV_M(P, BF)                                                                                   \
-  do {                                                                                                            \
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sn_fconv_mfma_kernel<P, BF>),                     \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                      \
-    hipLaunchKernelGGL((sn_fconv_mfma_kernel<P, BF>), dim3((unsigned)(nblk < cus ? nblk : cus)), dim3(1024), lds, s, *x, \
-                       nt, nf, lg, nframes, nblk, *w, residual, out, o_sb, o_st, o_sf);                           \
-  } while (0)
-#define FNSSL_SN_FCONV(P)                                                                                         \
-  if (mfma) {                                                                                                     \
-    if (bf) FNSSL_SN_FCONV_M(P, true); else FNSSL_SN_FCONV_M(P, false);                                           \
-  } else                                                                                                          \
-    hipLaunchKernelGGL(sn_fconv_kernel<P>, dim3((unsigned)nblk), dim3(256), 0, s, *x, nt, nf, lg, nframes, *w, residual, \
-                       out, o_sb, o_st, o_sf)
-  if (pool == 1) {
-    FNSSL_SN_FCONV(1);
-  } else if (pool == 2) {
-    FNSSL_SN_FCONV(2);
-  } else {
-    FNSSL_SN_FCONV(8);
-  }
-#undef FNSSL_SN_FCONV
-#undef FNSSL_SN_FCONV_M
-  FNSSL_CHECK_LAUNCH("sn_fconv_kernel");
-  return FNSSL_OK;
+  return with_value<1, 2, 8>(pool, [&](auto P_) {
+    constexpr int P = P_;
+    if (!mfma)
+      return enqueue(s, Kernel{sn_fconv_kernel<P>, 256, 0, "sn_fconv_kernel"}, (unsigned)nblk, *x, nt, nf, lg, nframes, *w, residual,
+                     out, o_sb, o_st, o_sf);
+    return with_bool(bf, [&](auto BF) {
+      return enqueue(s, Kernel{sn_fconv_mfma_kernel<P, BF>, 1024, lds, "sn_fconv_mfma_kernel"}, (unsigned)(nblk < cus ? nblk : cus), *x,
+                     nt, nf, lg, nframes, nblk, *w, residual, out, o_sb, o_st, o_sf);
+    });
+  });
 }
 
 int fnssl_sn_full(const fnssl_btf_view* x, int nb, int nt, int nf, const fnssl_sn_full_w* w, int residual, float* out,
@@ -1943,40 +1941,24 @@ int fnssl_sn_full(const fnssl_btf_view* x, int nb, int nt, int nf, const fnssl_s
   // the matrix-pipe kernel exists for 16, 64 and 128 bins; elsewhere the products stay exact fp32 in both modes
   const bool bf = precision == FNSSL_PRECISION_BF16 && (nf == 16 || nf == 64 || nf == 128);
   const bool mfma = (bf || !fnssl::tune(FNSSL_TUNE_SN_SCALAR)) && (nf == 16 || nf == 64 || nf == 128);
-  if (mfma) {
-    const long long cus = fnssl::device_cus();
-    const unsigned grid = (unsigned)(nblk < cus ? nblk : cus);
-    const size_t lds = (size_t)((nf / 16) * (nf / 16) * 256 + 16 * 256 + 3 * H + 16 + nf + 2 * 256 * 8) * sizeof(float);
-#define FNSSL_SN_FULL_P(NFV, BF)                                                                                   \
-  do {                                                                                                             \
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sn_full_mfma_kernel<NFV, BF>),                     \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                       \
-    hipLaunchKernelGGL((sn_full_mfma_kernel<NFV, BF>), dim3(grid), dim3(1024), lds, s, *x, nt, nframes, nblk, *w,  \
-                       residual, out, o_sb, o_st, o_sf);                                                           \
-  } while (0)
-#define FNSSL_SN_FULL(NFV)                                                                                         \
-  do {                                                                                                             \
-    if (bf) FNSSL_SN_FULL_P(NFV, true); else FNSSL_SN_FULL_P(NFV, false);                                          \
-  } while (0)
-    if (nf == 16)
-      FNSSL_SN_FULL(16);
-    else if (nf == 64)
-      FNSSL_SN_FULL(64);
-    else
-      FNSSL_SN_FULL(128);
-#undef FNSSL_SN_FULL
-#undef FNSSL_SN_FULL_P
-  } else {
-    hipLaunchKernelGGL(sn_full_kernel, dim3((unsigned)nblk), dim3(256), 0, s, *x, nt, nf, lg, nframes, *w, residual, out,
-                       o_sb, o_st, o_sf);
-  }
-  FNSSL_CHECK_LAUNCH("sn_full_kernel");
-  return FNSSL_OK;
+  if (!mfma)
+    return enqueue(s, Kernel{sn_full_kernel, 256, 0, "sn_full_kernel"}, (unsigned)nblk, *x, nt, nf, lg, nframes, *w, residual, out,
+                   o_sb, o_st, o_sf);
+  const long long cus = fnssl::device_cus();
+  const unsigned grid = (unsigned)(nblk < cus ? nblk : cus);
+  const size_t lds = (size_t)((nf / 16) * (nf / 16) * 256 + 16 * 256 + 3 * H + 16 + nf + 2 * 256 * 8) * sizeof(float);
+  return with_value<16, 64, 128>(nf, [&](auto NFV_) {
+    constexpr int NFV = NFV_;
+    return with_bool(bf, [&](auto BF) {
+      return enqueue(s, Kernel{sn_full_mfma_kernel<NFV, BF>, 1024, lds, "sn_full_mfma_kernel"}, grid, *x, nt, nframes, nblk, *w,
+                     residual, out, o_sb, o_st, o_sf);
+    });
+  });
 }
 
 size_t fnssl_sn_mamba_workspace_bytes(int nb, int nt, int nf) {
   if (nb <= 0 || nt <= 0 || nf <= 0) return 0;
-  return mamba_ws_floats((long long)nb * nt * nf) * sizeof(float);
+  return MambaWsLayout((long long)nb * nt * nf).total;
 }
 
 int fnssl_sn_mamba(const fnssl_btf_view* x, int nb, int nt, int nf, const fnssl_sn_mamba_w* w, int residual,
@@ -1991,105 +1973,69 @@ int fnssl_sn_mamba(const fnssl_btf_view* x, int nb, int nt, int nf, const fnssl_
   FNSSL_REQUIRE(time_pool >= 1 && time_pool <= 16, "sn_mamba: time_pool must be in [1, 16]");
   FNSSL_REQUIRE(!carry || (conv_state && ssm_state), "sn_mamba: carry needs both state buffers");
   const long long npts = (long long)nb * nt * nf, nseq = (long long)nb * nf;
-  if (workspace_bytes < fnssl_sn_mamba_workspace_bytes(nb, nt, nf) || !workspace) {
-    fnssl::set_error("sn_mamba: workspace %zu < %zu bytes", workspace_bytes, fnssl_sn_mamba_workspace_bytes(nb, nt, nf));
-    return FNSSL_E_WORKSPACE;
-  }
+  const MambaWsLayout ws(npts);
+  FNSSL_TRY(check_workspace("sn_mamba", workspace, workspace_bytes, ws.total));
   FNSSL_REQUIRE(blocks_of(npts) < (1u << 31) && nseq < (1ll << 31), "sn_mamba: too many points");
-  const MambaWs m = carve_mamba(static_cast<float*>(workspace), npts);
+  float *const xz = ws.xz.floats(workspace), *const dbl = ws.dbl.floats(workspace), *const y = ws.y.floats(workspace);
   hipStream_t s = fnssl::as_stream(stream);
   const bool bf = precision == FNSSL_PRECISION_BF16;
   const bool mfma = bf || !fnssl::tune(FNSSL_TUNE_SN_SCALAR);   // A/B (fp32 only): the scalar-operand kernels
   {
     fnssl::TimedLaunch tl("sn_mamba_in", s, 2.0 * npts * H * 2 * E);
-    if (mfma) {
-      const unsigned nwg = mfma_grid(npts, 1, 16);
-      if (bf) {
-        const size_t lds = (size_t)w_lds_floats<H, 2 * E, true>() * sizeof(float);
-        FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sn_mamba_in_mfma_kernel<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(sn_mamba_in_mfma_kernel<true>, dim3(nwg), dim3(1024), lds, s, *x, nt, nf, npts, w->ln_w,
-                           w->ln_b, w->winT, m.xz);
-      } else {
-        const size_t lds = (size_t)w_lds_floats<H, 2 * E, false>() * sizeof(float);
-        FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sn_mamba_in_mfma_kernel<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(sn_mamba_in_mfma_kernel<false>, dim3(nwg), dim3(1024), lds, s, *x, nt, nf, npts, w->ln_w,
-                           w->ln_b, w->winT, m.xz);
-      }
-    } else {
-      hipLaunchKernelGGL(sn_mamba_in_kernel, dim3(blocks_of(npts), 4), dim3(256), 0, s, *x, nt, nf, npts, w->ln_w, w->ln_b,
-                         w->winT, m.xz);
-    }
-    FNSSL_CHECK_LAUNCH("sn_mamba_in_kernel");
+    if (mfma)
+      FNSSL_TRY(with_bool(bf, [&](auto BF) {
+        const size_t lds = (size_t)w_lds_floats<H, 2 * E, BF>() * sizeof(float);
+        return enqueue(s, Kernel{sn_mamba_in_mfma_kernel<BF>, 1024, lds, "sn_mamba_in_mfma_kernel"}, mfma_grid(npts, 1, 16), *x, nt, nf,
+                       npts, w->ln_w, w->ln_b, w->winT, xz);
+      }));
+    else
+      FNSSL_TRY(enqueue(s, Kernel{sn_mamba_in_kernel, 256, 0, "sn_mamba_in_kernel"}, dim3(blocks_of(npts), 4), *x, nt, nf, npts,
+                        w->ln_w, w->ln_b, w->winT, xz));
   }
   {
     fnssl::TimedLaunch tl("sn_mamba_xproj", s, 2.0 * npts * E * (XP - 2 + KC));
     if (mfma && !carry) {                                 // whole sequences: conv + x_proj in one pass, u not materialised
       const long long tiles = nseq * ((nt + 12) / 13);
-      if (bf) {
-        constexpr size_t lds = (size_t)(w_lds_floats<E, 48, true>() + E * KC + E) * sizeof(float);
-        hipLaunchKernelGGL(sn_mamba_convx_mfma_kernel<true>, dim3(mfma_grid(tiles * 16, 4)), dim3(512), lds, s, m.xz, nt, nseq,
-                           w->conv_w, w->conv_b, w->wxT, m.dbl);
-      } else {
-        constexpr size_t lds = (size_t)(w_lds_floats<E, 48, false>() + E * KC + E) * sizeof(float);
-        hipLaunchKernelGGL(sn_mamba_convx_mfma_kernel<false>, dim3(mfma_grid(tiles * 16, 4)), dim3(512), lds, s, m.xz, nt, nseq,
-                           w->conv_w, w->conv_b, w->wxT, m.dbl);
-      }
+      FNSSL_TRY(with_bool(bf, [&](auto BF) {
+        constexpr size_t lds = (size_t)(w_lds_floats<E, 48, BF>() + E * KC + E) * sizeof(float);
+        return enqueue(s, Kernel{sn_mamba_convx_mfma_kernel<BF>, 512, lds, "sn_mamba_convx_mfma_kernel"}, mfma_grid(tiles * 16, 4), xz,
+                       nt, nseq, w->conv_w, w->conv_b, w->wxT, dbl);
+      }));
     } else if (mfma) {
       const long long nq = npts * (E / 4);
       FNSSL_REQUIRE(blocks_of(nq) < (1u << 31), "sn_mamba: too many points");
-      hipLaunchKernelGGL(sn_mamba_conv_kernel, dim3(blocks_of(nq)), dim3(256), 0, s, m.xz, nt, npts, w->conv_w, w->conv_b,
-                         carry ? conv_state : nullptr, m.y);
-      FNSSL_CHECK_LAUNCH("sn_mamba_conv_kernel");
-      constexpr size_t lds_bf = (size_t)w_lds_floats<E, 48, true>() * sizeof(float);
-      constexpr size_t lds_f32 = (size_t)w_lds_floats<E, 48, false>() * sizeof(float);
-      if (bf)
-        hipLaunchKernelGGL(sn_mamba_xproj_mfma_kernel<true>, dim3(mfma_grid(npts, 4)), dim3(512), lds_bf, s, m.y, npts,
-                           w->wxT, m.dbl);
-      else
-        hipLaunchKernelGGL(sn_mamba_xproj_mfma_kernel<false>, dim3(mfma_grid(npts, 4)), dim3(512), lds_f32, s, m.y, npts,
-                           w->wxT, m.dbl);
+      FNSSL_TRY(enqueue(s, Kernel{sn_mamba_conv_kernel, 256, 0, "sn_mamba_conv_kernel"}, blocks_of(nq), xz, nt, npts, w->conv_w,
+                        w->conv_b, carry ? conv_state : nullptr, y));
+      FNSSL_TRY(with_bool(bf, [&](auto BF) {
+        constexpr size_t lds = (size_t)w_lds_floats<E, 48, BF>() * sizeof(float);
+        return enqueue(s, Kernel{sn_mamba_xproj_mfma_kernel<BF>, 512, lds, "sn_mamba_xproj_mfma_kernel"}, mfma_grid(npts, 4), y, npts,
+                       w->wxT, dbl);
+      }));
     } else {
-      hipLaunchKernelGGL(sn_mamba_xproj_kernel, dim3(blocks_of(npts)), dim3(256), 0, s, m.xz, nt, npts, w->conv_w, w->conv_b,
-                         w->wxT, carry ? conv_state : nullptr, m.dbl);
+      FNSSL_TRY(enqueue(s, Kernel{sn_mamba_xproj_kernel, 256, 0, "sn_mamba_xproj_kernel"}, blocks_of(npts), xz, nt, npts, w->conv_w,
+                        w->conv_b, w->wxT, carry ? conv_state : nullptr, dbl));
     }
-    FNSSL_CHECK_LAUNCH("sn_mamba_xproj_kernel");
   }
   {
     fnssl::TimedLaunch tl("sn_mamba_scan", s, (double)npts * E * (7.0 * NST + 2 * RK + 2 * KC));
-    hipLaunchKernelGGL(sn_mamba_scan_kernel, dim3((unsigned)nseq), dim3(E), 0, s, m.xz, m.dbl, nt, w->conv_w, w->conv_b,
-                       w->wdt, w->bdt, w->a, w->d, conv_state, ssm_state, carry, m.y, mfma && carry ? 1 : 0);
-    FNSSL_CHECK_LAUNCH("sn_mamba_scan_kernel");
+    FNSSL_TRY(enqueue(s, Kernel{sn_mamba_scan_kernel, E, 0, "sn_mamba_scan_kernel"}, (unsigned)nseq, xz, dbl, nt, w->conv_w, w->conv_b,
+                      w->wdt, w->bdt, w->a, w->d, conv_state, ssm_state, carry, y, mfma && carry ? 1 : 0));
   }
-  {
-    const int nt2 = nt / time_pool;
-    const long long nout = nseq * nt2;
-    if (nout > 0) {
-      fnssl::TimedLaunch tl("sn_mamba_out", s, 2.0 * nout * E * H);
-      if (mfma) {
-#define FNSSL_SN_OUT(BF, TP)                                                                                        \
-  do {                                                                                                              \
-    const size_t lds = (size_t)w_lds_floats<E, H, BF>() * sizeof(float);                                            \
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sn_mamba_out_mfma_kernel<BF, TP>),                  \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                          \
-    hipLaunchKernelGGL((sn_mamba_out_mfma_kernel<BF, TP>), dim3(mfma_grid(nout, 2)), dim3(512), lds, s, m.y, *x, nt, \
-                       nt2, nf, time_pool, nout, w->woT, residual, out, o_sb, o_st, o_sf);                          \
-  } while (0)
-        if (bf) {
-          if (time_pool == 1) FNSSL_SN_OUT(true, 1); else if (time_pool == 5) FNSSL_SN_OUT(true, 5); else FNSSL_SN_OUT(true, 0);
-        } else {
-          if (time_pool == 1) FNSSL_SN_OUT(false, 1); else if (time_pool == 5) FNSSL_SN_OUT(false, 5); else FNSSL_SN_OUT(false, 0);
-        }
-#undef FNSSL_SN_OUT
-      } else {
-        hipLaunchKernelGGL(sn_mamba_out_kernel, dim3(blocks_of(nout), 2), dim3(256), 0, s, m.y, *x, nt, nt2, nf, time_pool,
-                           nout, w->woT, residual, out, o_sb, o_st, o_sf);
-      }
-      FNSSL_CHECK_LAUNCH("sn_mamba_out_kernel");
-    }
-  }
-  return FNSSL_OK;
+  const int nt2 = nt / time_pool;
+  const long long nout = nseq * nt2;
+  if (nout == 0) return FNSSL_OK;
+  fnssl::TimedLaunch tl("sn_mamba_out", s, 2.0 * nout * E * H);
+  if (!mfma)
+    return enqueue(s, Kernel{sn_mamba_out_kernel, 256, 0, "sn_mamba_out_kernel"}, dim3(blocks_of(nout), 2), y, *x, nt, nt2, nf,
+                   time_pool, nout, w->woT, residual, out, o_sb, o_st, o_sf);
+  return with_bool(bf, [&](auto BF_) {
+    constexpr bool BF = BF_;
+    return with_value<1, 5, 0>(time_pool == 1 || time_pool == 5 ? time_pool : 0, [&](auto TP) {   // 0: any other pool, at run time
+      const size_t lds = (size_t)w_lds_floats<E, H, BF>() * sizeof(float);
+      return enqueue(s, Kernel{sn_mamba_out_mfma_kernel<BF, TP>, 512, lds, "sn_mamba_out_mfma_kernel"}, mfma_grid(nout, 2), y, *x, nt,
+                     nt2, nf, time_pool, nout, w->woT, residual, out, o_sb, o_st, o_sf);
+    });
+  });
 }
 
 int fnssl_sn_head(const fnssl_btf_view* x, int nb, int nt2, int nfc, const float* wfiP, const float* bfiP,
@@ -2101,31 +2047,19 @@ int fnssl_sn_head(const fnssl_btf_view* x, int nb, int nt2, int nfc, const float
   const long long npts = (long long)nb * nt2 * nfc;
   hipStream_t s = fnssl::as_stream(stream);
   fnssl::TimedLaunch tl("sn_head", s, 2.0 * npts * 16 * (DO * H + DO * DO));
-  if (!fnssl::tune(FNSSL_TUNE_SN_SCALAR)) {
-    const size_t lds = (size_t)(16 * 6 * 256 + 256) * sizeof(float);
-    FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sn_head_mfma_kernel),
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(sn_head_mfma_kernel, dim3(mfma_grid(npts, 1)), dim3(512), lds, s, *x, nt2, nfc, npts, wfiP, bfiP, wdT,
-                       bd, out);
-  } else {
-    hipLaunchKernelGGL(sn_head_kernel, dim3(blocks_of(npts)), dim3(256), 0, s, *x, nt2, nfc, npts, wfiP, bfiP, wdT, bd, out);
-  }
-  FNSSL_CHECK_LAUNCH("sn_head_kernel");
-  return FNSSL_OK;
+  if (fnssl::tune(FNSSL_TUNE_SN_SCALAR))
+    return enqueue(s, Kernel{sn_head_kernel, 256, 0, "sn_head_kernel"}, blocks_of(npts), *x, nt2, nfc, npts, wfiP, bfiP, wdT, bd, out);
+  const size_t lds = (size_t)(16 * 6 * 256 + 256) * sizeof(float);
+  return enqueue(s, Kernel{sn_head_mfma_kernel, 512, lds, "sn_head_mfma_kernel"}, mfma_grid(npts, 1), *x, nt2, nfc, npts, wfiP, bfiP, wdT,
+                 bd, out);
 }
 
 // ---- whole network ------------------------------------------------------------------------------------------
 
-static size_t sn_act_floats(int nb, int nf, int nt, int ratio) {
-  const size_t fr = (size_t)nb * nt;
-  const int nfc = nf / 16, nt2 = nt / ratio;
-  return fr * nf * H + fr * (nf / 2) * H + fr * nfc * H + (size_t)nb * (nt2 > 0 ? nt2 : 1) * nfc * H;
-}
-
 size_t fnssl_sn_forward_workspace_bytes(int nb, int nf, int nt) {
   if (nb <= 0 || nf <= 0 || nt <= 0) return 0;
   // sized for ANY time ratio fnssl_sn_forward accepts (1..16): the pooled buffer is largest at ratio 1
-  return (sn_act_floats(nb, nf, nt, 1) + mamba_ws_floats((long long)nb * nt * (nf / 16))) * sizeof(float) + 256;
+  return SnWsLayout(nb, nf, nt, 1).total;
 }
 
 size_t fnssl_sn_state_floats(const fnssl_sn_net* net, int nb, int nf) {
@@ -2147,30 +2081,17 @@ int fnssl_sn_forward(const fnssl_sn_net* net, const float* x, long long x_sb, lo
   FNSSL_REQUIRE(!carry || state, "sn_forward: carry needs the state buffer");
   FNSSL_REQUIRE(!state || nt % net->time_ratio == 0, "sn_forward: streaming chunks must be multiples of %d frames", net->time_ratio);
   const int ratio = net->time_ratio, nfc = nf / 16, nt2 = nt / ratio;
-  const size_t need = (sn_act_floats(nb, nf, nt, ratio) + mamba_ws_floats((long long)nb * nt * nfc)) * sizeof(float) + 256;
-  if (!workspace || workspace_bytes < need) {
-    fnssl::set_error("sn_forward: workspace %zu < %zu bytes", workspace_bytes, need);
-    return FNSSL_E_WORKSPACE;
-  }
-  float* base = reinterpret_cast<float*>((reinterpret_cast<size_t>(workspace) + 255) / 256 * 256);
-  const size_t fr = (size_t)nb * nt;
-  float* a0 = base;                              // [nb, nt, nf, H]
-  float* a1 = a0 + fr * nf * H;                  // [nb, nt, nf/2, H]
-  float* a2 = a1 + fr * (nf / 2) * H;            // [nb, nt, nfc, H]
-  float* a3 = a2 + fr * nfc * H;                 // [nb, nt2, nfc, H]
-  float* mws = a3 + (size_t)nb * (nt2 > 0 ? nt2 : 1) * nfc * H;
-  const size_t mws_bytes = mamba_ws_floats((long long)nb * nt * nfc) * sizeof(float);
+  const SnWsLayout ws(nb, nf, nt, ratio);
+  FNSSL_TRY(check_workspace("sn_forward", workspace, workspace_bytes, ws.total));
+  void* base = reinterpret_cast<void*>((reinterpret_cast<size_t>(workspace) + 255) / 256 * 256);
+  float *const a0 = ws.a0.floats(base), *const a1 = ws.a1.floats(base), *const a2 = ws.a2.floats(base), *const a3 = ws.a3.floats(base);
+  float* const mws = ws.mamba.floats(base);
+  const size_t mws_bytes = ws.mamba.bytes;
   const size_t nseq = (size_t)nb * nfc;
   float* st_enc = state;
   float* st_m = state ? state + (size_t)nb * net->dim_input * nf * (KE - 1) : nullptr;
   auto conv_st = [&](int l, int j) { return st_m ? st_m + ((size_t)l * 2 + j) * nseq * (3 * E + E * NST) : nullptr; };
   auto ssm_st = [&](int l, int j) { return st_m ? conv_st(l, j) + nseq * 3 * E : nullptr; };
-  int rc;
-#define FNSSL_SN_TRY(call) \
-  do {                     \
-    rc = (call);           \
-    if (rc != FNSSL_OK) return rc; \
-  } while (0)
   auto strides = [&](int f, long long& sb, long long& st, long long& sf, int t) {
     sf = H;
     st = (long long)f * H;
@@ -2178,34 +2099,33 @@ int fnssl_sn_forward(const fnssl_sn_net* net, const float* x, long long x_sb, lo
   };
   long long sb, st, sf, sb2, st2, sf2;
   strides(nf, sb, st, sf, nt);
-  FNSSL_SN_TRY(fnssl_sn_encoder(x, x_sb, x_sc, x_sf, x_st, nb, net->dim_input, nf, nt, net->enc_wT, net->enc_b,
+  FNSSL_TRY(fnssl_sn_encoder(x, x_sb, x_sc, x_sf, x_st, nb, net->dim_input, nf, nt, net->enc_wT, net->enc_b,
                                 carry ? st_enc : nullptr, st_enc, a0, sb, st, sf, prec, stream));
   const fnssl_sn_layer* L = &net->layers[0];
   fnssl_btf_view v0 = {a0, sb, st, sf};
   strides(nf / 2, sb2, st2, sf2, nt);
-  FNSSL_SN_TRY(fnssl_sn_fconv(&v0, nb, nt, nf, &L->fconv1, 1, 2, a1, sb2, st2, sf2, prec, stream));
+  FNSSL_TRY(fnssl_sn_fconv(&v0, nb, nt, nf, &L->fconv1, 1, 2, a1, sb2, st2, sf2, prec, stream));
   fnssl_btf_view v1 = {a1, sb2, st2, sf2};
-  FNSSL_SN_TRY(fnssl_sn_full(&v1, nb, nt, nf / 2, &L->full, 1, a1, sb2, st2, sf2, prec, stream));
+  FNSSL_TRY(fnssl_sn_full(&v1, nb, nt, nf / 2, &L->full, 1, a1, sb2, st2, sf2, prec, stream));
   strides(nfc, sb, st, sf, nt);
-  FNSSL_SN_TRY(fnssl_sn_fconv(&v1, nb, nt, nf / 2, &L->fconv2, 1, 8, a2, sb, st, sf, prec, stream));
+  FNSSL_TRY(fnssl_sn_fconv(&v1, nb, nt, nf / 2, &L->fconv2, 1, 8, a2, sb, st, sf, prec, stream));
   fnssl_btf_view v2 = {a2, sb, st, sf};
-  FNSSL_SN_TRY(fnssl_sn_mamba(&v2, nb, nt, nfc, &L->mamba[0], 1, 1, conv_st(0, 0), ssm_st(0, 0), carry, a2, sb, st, sf,
+  FNSSL_TRY(fnssl_sn_mamba(&v2, nb, nt, nfc, &L->mamba[0], 1, 1, conv_st(0, 0), ssm_st(0, 0), carry, a2, sb, st, sf,
                               mws, mws_bytes, prec, stream));
   if (nt2 == 0) return FNSSL_OK;                 // fewer frames than one pooled step: empty output (AvgPool floor)
   strides(nfc, sb2, st2, sf2, nt2);
-  FNSSL_SN_TRY(fnssl_sn_mamba(&v2, nb, nt, nfc, &L->mamba[1], 1, ratio, conv_st(0, 1), ssm_st(0, 1), carry, a3, sb2, st2,
+  FNSSL_TRY(fnssl_sn_mamba(&v2, nb, nt, nfc, &L->mamba[1], 1, ratio, conv_st(0, 1), ssm_st(0, 1), carry, a3, sb2, st2,
                               sf2, mws, mws_bytes, prec, stream));
   fnssl_btf_view v3 = {a3, sb2, st2, sf2};
   for (int l = 1; l < net->num_layers; ++l) {
     L = &net->layers[l];
-    FNSSL_SN_TRY(fnssl_sn_fconv(&v3, nb, nt2, nfc, &L->fconv1, 1, 1, a3, sb2, st2, sf2, prec, stream));
-    FNSSL_SN_TRY(fnssl_sn_full(&v3, nb, nt2, nfc, &L->full, 1, a3, sb2, st2, sf2, prec, stream));
-    FNSSL_SN_TRY(fnssl_sn_fconv(&v3, nb, nt2, nfc, &L->fconv2, 1, 1, a3, sb2, st2, sf2, prec, stream));
+    FNSSL_TRY(fnssl_sn_fconv(&v3, nb, nt2, nfc, &L->fconv1, 1, 1, a3, sb2, st2, sf2, prec, stream));
+    FNSSL_TRY(fnssl_sn_full(&v3, nb, nt2, nfc, &L->full, 1, a3, sb2, st2, sf2, prec, stream));
+    FNSSL_TRY(fnssl_sn_fconv(&v3, nb, nt2, nfc, &L->fconv2, 1, 1, a3, sb2, st2, sf2, prec, stream));
     for (int j = 0; j < 2; ++j)
-      FNSSL_SN_TRY(fnssl_sn_mamba(&v3, nb, nt2, nfc, &L->mamba[j], 1, 1, conv_st(l, j), ssm_st(l, j), carry, a3, sb2, st2,
+      FNSSL_TRY(fnssl_sn_mamba(&v3, nb, nt2, nfc, &L->mamba[j], 1, 1, conv_st(l, j), ssm_st(l, j), carry, a3, sb2, st2,
                                   sf2, mws, mws_bytes, prec, stream));
   }
-#undef FNSSL_SN_TRY
   return fnssl_sn_head(&v3, nb, nt2, nfc, net->wfiP, net->bfiP, net->wdT, net->bd, out, stream);
 }
 

@@ -11,7 +11,10 @@
 //   head_bwd           tanh' + Linear(256, 2)^T + AvgPool(12)^T, and the per-block partial dW / db
 //   mse_kernel         loss and d loss / d pred of the re-batched prediction
 //   adam_kernel        torch.optim.Adam (no amsgrad / weight decay) on the flat parameter vector
-#include "common.h"
+#include "host.h"
+
+using fnssl::enqueue;
+using fnssl::Kernel;
 
 namespace {
 
@@ -244,17 +247,13 @@ int fnssl_train_combine(float* out, long long o_sb, long long o_st, long long o_
   const long long total = (long long)nb * nt * nf * p.c4;
   FNSSL_REQUIRE((total + 255) / 256 < (1ll << 31), "train_combine: too large");
   fnssl::TimedLaunch tl("train_combine", fnssl::as_stream(stream));
-  hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, fnssl::as_stream(stream), p);
-  FNSSL_CHECK_LAUNCH("combine_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{combine_kernel, 256, 0, "combine_kernel"}, (unsigned)((total + 255) / 256), p);
 }
 
 int fnssl_dropout_scale(float* out, long long n, unsigned seed32, long long offset, void* stream) {
   FNSSL_REQUIRE(out && n > 0 && offset >= 0, "dropout_scale: bad arguments");
-  hipLaunchKernelGGL(dropout_scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, fnssl::as_stream(stream),
-                     out, n, seed32, offset);
-  FNSSL_CHECK_LAUNCH("dropout_scale_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{dropout_scale_kernel, 256, 0, "dropout_scale_kernel"},
+                 (unsigned)((n + 255) / 256), out, n, seed32, offset);
 }
 
 size_t fnssl_head_backward_workspace_bytes(void) { return (size_t)kHeadBlocks * 520 * sizeof(float); }
@@ -272,21 +271,20 @@ int fnssl_head_backward(const float* x, const float* w, const float* pred, const
   const long long items = (long long)nb * nf * nt2;
   const int nblk = (int)(items < kHeadBlocks ? (items > 0 ? items : 1) : kHeadBlocks);
   if (items > 0) {
-    hipLaunchKernelGGL(head_bwd_kernel, dim3(nblk), dim3(256), 0, st, x, w, pred, dpred, nb, nf, nt, nt2, dx, part);
-    FNSSL_CHECK_LAUNCH("head_bwd_kernel");
+    FNSSL_TRY(enqueue(st, Kernel{head_bwd_kernel, 256, 0, "head_bwd_kernel"}, nblk, x, w, pred, dpred, nb, nf, nt, nt2, dx,
+                      part));
   } else {
     FNSSL_HIP(hipMemsetAsync(part, 0, 520 * sizeof(float), st));
   }
   if (nt > nt2 * kSeg) {
     const long long n = (long long)nb * nf * (nt - nt2 * kSeg) * 64;
-    hipLaunchKernelGGL(head_tail_zero_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dx,
-                       (long long)nb * nf, nt, nt2);
-    FNSSL_CHECK_LAUNCH("head_tail_zero_kernel");
+    FNSSL_TRY(enqueue(st, Kernel{head_tail_zero_kernel, 256, 0, "head_tail_zero_kernel"}, (unsigned)((n + 255) / 256), dx,
+                      (long long)nb * nf, nt, nt2));
   }
-  hipLaunchKernelGGL(reduce_parts_kernel, dim3(2), dim3(256), 0, st, part, nblk, 520, 512, dw, accumulate, 1.0f);
-  hipLaunchKernelGGL(reduce_parts_kernel, dim3(1), dim3(256), 0, st, part + 512, nblk, 520, 2, db, accumulate, 1.0f);
-  FNSSL_CHECK_LAUNCH("reduce_parts_kernel");
-  return FNSSL_OK;
+  FNSSL_TRY(enqueue(st, Kernel{reduce_parts_kernel, 256, 0, "reduce_parts_kernel"}, 2, part, nblk, 520, 512, dw, accumulate,
+                    1.0f));
+  return enqueue(st, Kernel{reduce_parts_kernel, 256, 0, "reduce_parts_kernel"}, 1, part + 512, nblk, 520, 2, db, accumulate,
+                 1.0f);
 }
 
 int fnssl_mse_loss(const float* pred, const float* gt, int nb, int np, int nt2, int nf2, long long n_total,
@@ -299,12 +297,10 @@ int fnssl_mse_loss(const float* pred, const float* gt, int nb, int np, int nt2, 
   float* part = static_cast<float*>(workspace);
   const long long total = (long long)nb * np * nt2 * nf2;
   const int nblk = (int)((total + 255) / 256 < kMseBlocks ? (total + 255) / 256 : kMseBlocks);
-  hipLaunchKernelGGL(mse_kernel, dim3(nblk), dim3(256), 0, st, pred, gt, nb, np, nt2, nf2, 2.0f / (float)n_total, dpred,
-                     part);
-  hipLaunchKernelGGL(reduce_parts_kernel, dim3(1), dim3(256), 0, st, part, nblk, 1, 1, loss, accumulate,
-                     1.0f / (float)n_total);
-  FNSSL_CHECK_LAUNCH("mse_kernel");
-  return FNSSL_OK;
+  FNSSL_TRY(enqueue(st, Kernel{mse_kernel, 256, 0, "mse_kernel"}, nblk, pred, gt, nb, np, nt2, nf2, 2.0f / (float)n_total, dpred,
+                    part));
+  return enqueue(st, Kernel{reduce_parts_kernel, 256, 0, "reduce_parts_kernel"}, 1, part, nblk, 1, 1, loss, accumulate,
+                 1.0f / (float)n_total);
 }
 
 int fnssl_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float lr,
@@ -312,11 +308,8 @@ int fnssl_adam_step(float* param, const float* grad, float* exp_avg, float* exp_
   FNSSL_REQUIRE(param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1, "adam_step: bad arguments");
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
   fnssl::TimedLaunch tl("adam", fnssl::as_stream(stream));
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, fnssl::as_stream(stream), param, grad,
-                     exp_avg, exp_avg_sq, n, grad_scale, beta1, beta2, (float)((double)lr / bc1),
-                     (float)(1.0 / sqrt(bc2)), eps);
-  FNSSL_CHECK_LAUNCH("adam_kernel");
-  return FNSSL_OK;
+  return enqueue(fnssl::as_stream(stream), Kernel{adam_kernel, 256, 0, "adam_kernel"}, (unsigned)((n + 255) / 256), param, grad,
+                 exp_avg, exp_avg_sq, n, grad_scale, beta1, beta2, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)), eps);
 }
 
 }  // extern "C"

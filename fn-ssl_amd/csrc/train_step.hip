@@ -15,7 +15,10 @@
 #include <cstring>
 #include <vector>
 
-#include "common.h"
+#include "host.h"
+
+using fnssl::enqueue;
+using fnssl::Kernel;
 
 namespace {
 
@@ -73,12 +76,6 @@ struct Ctx {
   void* bwd_ws;
   size_t bwd_ws_bytes;
 };
-
-#define TRY(call)                  \
-  do {                             \
-    const int rc__ = (call);       \
-    if (rc__ != FNSSL_OK) return rc__; \
-  } while (0)
 
 int combine(const Ctx& c, const T4& out, std::initializer_list<T4> masked, std::initializer_list<T4> plain, bool use_mask,
             unsigned seed, long long b0) {
@@ -364,10 +361,7 @@ int fnssl_train_backward(fnssl_train* t, const float* theta, float* grad, const 
   FNSSL_REQUIRE(nb > 0 && np > 0 && nf > 0 && nt >= 12, "train_backward: empty problem");
   const int nbp = nb * np, nt2 = nt / 12;
   const Plan pl = make_plan(t, nbp, nf, nt);
-  if (!workspace || workspace_bytes < pl.total) {
-    fnssl::set_error("train_backward: workspace %zu < %zu bytes", workspace_bytes, pl.total);
-    return FNSSL_E_WORKSPACE;
-  }
+  FNSSL_TRY(fnssl::check_workspace("train_backward", workspace, workspace_bytes, pl.total));
   hipStream_t st = fnssl::as_stream(stream);
   char* base = reinterpret_cast<char*>((reinterpret_cast<size_t>(workspace) + 255) / 256 * 256);
   auto F = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
@@ -381,19 +375,18 @@ int fnssl_train_backward(fnssl_train* t, const float* theta, float* grad, const 
   for (int l = 0; l < 6; ++l)
     for (int d = 0; d < t->L[l].ndir; ++d) {
       const Layer& L = t->L[l];
-      hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((L.fw_floats + 255) / 256)), dim3(256), 0, st, theta,
-                         t->dmaps + L.map_fw_a[d], t->dmaps + L.map_fw_b[d], (long long)L.fw_floats, F(pl.fw[l][d]));
-      hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((L.bw_floats + 255) / 256)), dim3(256), 0, st, theta,
-                         t->dmaps + L.map_bw[d], (const int*)nullptr, (long long)L.bw_floats, F(pl.bw[l][d]));
-      FNSSL_CHECK_LAUNCH("gather_kernel");
+      FNSSL_TRY(enqueue(st, Kernel{gather_kernel, 256, 0, "gather_kernel"}, (unsigned)((L.fw_floats + 255) / 256), theta,
+                        t->dmaps + L.map_fw_a[d], t->dmaps + L.map_fw_b[d], (long long)L.fw_floats, F(pl.fw[l][d])));
+      FNSSL_TRY(enqueue(st, Kernel{gather_kernel, 256, 0, "gather_kernel"}, (unsigned)((L.bw_floats + 255) / 256), theta,
+                        t->dmaps + L.map_bw[d], (const int*)nullptr, (long long)L.bw_floats, F(pl.bw[l][d])));
       fw[l][d] = F(pl.fw[l][d]);
       bw[l][d] = F(pl.bw[l][d]);
     }
 
   const int nho = t->L[1].ndir * t->L[1].hidden, ndn = t->L[1].ndir;
   const T4 XF = make_F(F(pl.xf), nt, nf, 4), XN = make_N(F(pl.xn), nt, nf, 4);
-  TRY(fnssl_nchw_to_seq(x, nbp, 4, nf, nt, XF.p, st));
-  TRY(combine(c, XN, {}, {XF}, false, 0, 0));   // the same numbers stored [b, f, t, 4]
+  FNSSL_TRY(fnssl_nchw_to_seq(x, nbp, 4, nf, nt, XF.p, st));
+  FNSSL_TRY(combine(c, XN, {}, {XF}, false, 0, 0));   // the same numbers stored [b, f, t, 4]
   T4 Fk[3], Uk[3], Vk[3], Nk[3];
   const T4 X = make_N(F(pl.x), nt, nf, kCh);
   // ---------------- forward (train mode) ----------------
@@ -403,26 +396,26 @@ int fnssl_train_backward(fnssl_train* t, const float* theta, float* grad, const 
     Vk[k] = make_N(F(pl.v[k]), nt, nf, kCh);
     Nk[k] = make_N(F(pl.n[k]), nt, nf, nho);
     if (k == 0) {
-      TRY(lstm_fwd(c, lf, XF, nullptr, fw[0], Fk[0], F(pl.res[0]), pl.res_bytes[0]));
-      TRY(combine(c, Vk[0], {Fk[0]}, {}, true, seeds[0], pair0));                        // dropout_full (:40)
+      FNSSL_TRY(lstm_fwd(c, lf, XF, nullptr, fw[0], Fk[0], F(pl.res[0]), pl.res_bytes[0]));
+      FNSSL_TRY(combine(c, Vk[0], {Fk[0]}, {}, true, seeds[0], pair0));                        // dropout_full (:40)
     } else {
       Uk[k] = make_F(F(pl.u[k]), nt, nf, kCh);
-      TRY(combine(c, Uk[k], {}, {X, Fk[k - 1]}, false, 0, 0));                            // x + fb_skip (:36-37)
-      TRY(lstm_fwd(c, lf, Uk[k], nullptr, fw[2 * k], Fk[k], F(pl.res[2 * k]), pl.res_bytes[2 * k]));
-      TRY(combine(c, Vk[k], {Fk[k]}, {X}, true, seeds[2 * k], pair0));                    // + nb_skip (:44-45)
+      FNSSL_TRY(combine(c, Uk[k], {}, {X, Fk[k - 1]}, false, 0, 0));                            // x + fb_skip (:36-37)
+      FNSSL_TRY(lstm_fwd(c, lf, Uk[k], nullptr, fw[2 * k], Fk[k], F(pl.res[2 * k]), pl.res_bytes[2 * k]));
+      FNSSL_TRY(combine(c, Vk[k], {Fk[k]}, {X}, true, seeds[2 * k], pair0));                    // + nb_skip (:44-45)
     }
-    TRY(lstm_fwd(c, ln, Vk[k], k == 0 ? &XN : nullptr, fw[2 * k + 1], Nk[k], F(pl.res[2 * k + 1]), pl.res_bytes[2 * k + 1]));
-    TRY(combine(c, X, {Nk[k]}, {}, true, seeds[2 * k + 1], pair0));                       // dropout_narr (:48)
+    FNSSL_TRY(lstm_fwd(c, ln, Vk[k], k == 0 ? &XN : nullptr, fw[2 * k + 1], Nk[k], F(pl.res[2 * k + 1]), pl.res_bytes[2 * k + 1]));
+    FNSSL_TRY(combine(c, X, {Nk[k]}, {}, true, seeds[2 * k + 1], pair0));                       // dropout_narr (:48)
   }
   const float* emb_w = theta + t->off_emb_w;
   const float* emb_b = theta + t->off_emb_b;
   float* pred = F(pl.pred);
   float* dpred = F(pl.dpred);
-  TRY(fnssl_head(X.p, nbp, nf, nt, emb_w, emb_b, pred, st));
-  TRY(fnssl_mse_loss(pred, gt, nb, np, nt2, 2 * nf, n_total, dpred, loss, 1, F(pl.small), 4096, st));
+  FNSSL_TRY(fnssl_head(X.p, nbp, nf, nt, emb_w, emb_b, pred, st));
+  FNSSL_TRY(fnssl_mse_loss(pred, gt, nb, np, nt2, 2 * nf, n_total, dpred, loss, 1, F(pl.small), 4096, st));
   // ---------------- backward ----------------
   const T4 G = make_N(F(pl.g), nt, nf, kCh);
-  TRY(fnssl_head_backward(X.p, emb_w, pred, dpred, nbp, nf, nt, G.p, grad + t->off_emb_w, grad + t->off_emb_b, 1, F(pl.small),
+  FNSSL_TRY(fnssl_head_backward(X.p, emb_w, pred, dpred, nbp, nf, nt, G.p, grad + t->off_emb_w, grad + t->off_emb_b, 1, F(pl.small),
                           fnssl_head_backward_workspace_bytes(), st));
   T4 gx[3] = {G};
   int ngx = 1;
@@ -434,29 +427,29 @@ int fnssl_train_backward(fnssl_train* t, const float* theta, float* grad, const 
     {   // dropout_narr backward: DN = mask * sum(gx)
       fnssl_btf_view mv[3];
       for (int i = 0; i < ngx; ++i) mv[i] = btf(gx[i]);
-      TRY(fnssl_train_combine(DN.p, DN.sb, DN.st, DN.sf, nbp, nt, nf, nho, mv, ngx, nullptr, 0, 1, seeds[2 * k + 1], pair0, st));
+      FNSSL_TRY(fnssl_train_combine(DN.p, DN.sb, DN.st, DN.sf, nbp, nt, nf, nho, mv, ngx, nullptr, 0, 1, seeds[2 * k + 1], pair0, st));
     }
     const T4 dA_n = make_N(F(pl.da), nt, nf, ndn * 4 * ln.hidden);
     const T4 DV = make_N(F(pl.dv[k & 1]), nt, nf, ndn * kCh);
-    TRY(lstm_bwd(c, ln, F(pl.res[2 * k + 1]), DN, dA_n, &DV, bw[2 * k + 1]));
-    TRY(weight_grads(c, ln, grad, dA_n.p, Vk[k].p, k == 0 ? XN.p : nullptr, Nk[k].p));
+    FNSSL_TRY(lstm_bwd(c, ln, F(pl.res[2 * k + 1]), DN, dA_n, &DV, bw[2 * k + 1]));
+    FNSSL_TRY(weight_grads(c, ln, grad, dA_n.p, Vk[k].p, k == 0 ? XN.p : nullptr, Nk[k].p));
     const T4 DF = make_F(F(pl.df), nt, nf, 2 * kHFull);
     {   // dropout_full backward + fb_skip: DF = mask * sum(dv slabs) + sum(dfb)
       fnssl_btf_view mv[2], pv[2];
       for (int d = 0; d < ndn; ++d) mv[d] = btf(chan(DV, d * kCh, kCh));
       for (int i = 0; i < ndfb; ++i) pv[i] = btf(dfb[i]);
-      TRY(fnssl_train_combine(DF.p, DF.sb, DF.st, DF.sf, nbp, nt, nf, 2 * kHFull, mv, ndn, pv, ndfb, 1, seeds[2 * k], pair0, st));
+      FNSSL_TRY(fnssl_train_combine(DF.p, DF.sb, DF.st, DF.sf, nbp, nt, nf, 2 * kHFull, mv, ndn, pv, ndfb, 1, seeds[2 * k], pair0, st));
     }
     const T4 dA_f = make_F(F(pl.da), nt, nf, 2 * 4 * kHFull);
     if (k > 0) {
       const T4 DU = make_F(F(pl.du[k & 1]), nt, nf, 2 * kCh);
-      TRY(lstm_bwd(c, lf, F(pl.res[2 * k]), DF, dA_f, &DU, bw[2 * k]));
-      TRY(weight_grads(c, lf, grad, dA_f.p, Uk[k].p, nullptr, Fk[k].p));
+      FNSSL_TRY(lstm_bwd(c, lf, F(pl.res[2 * k]), DF, dA_f, &DU, bw[2 * k]));
+      FNSSL_TRY(weight_grads(c, lf, grad, dA_f.p, Uk[k].p, nullptr, Fk[k].p));
       T4 du[2] = {chan(DU, 0, kCh), chan(DU, kCh, kCh)};
       int ndu = 2;
       if (ndn + 2 > 3) {   // offline narrow-band: 2 + 2 operands -> fold the full-band pair first
         const T4 S = make_F(F(pl.s), nt, nf, kCh);
-        TRY(combine(c, S, {}, {du[0], du[1]}, false, 0, 0));
+        FNSSL_TRY(combine(c, S, {}, {du[0], du[1]}, false, 0, 0));
         du[0] = S;
         ndu = 1;
       }
@@ -466,8 +459,8 @@ int fnssl_train_backward(fnssl_train* t, const float* theta, float* grad, const 
       ndfb = ndu;   // dL/dF_{k-1} through fb_skip
       for (int i = 0; i < ndu; ++i) dfb[i] = du[i];
     } else {
-      TRY(lstm_bwd(c, lf, F(pl.res[0]), DF, dA_f, nullptr, bw[0]));
-      TRY(weight_grads(c, lf, grad, dA_f.p, XF.p, nullptr, Fk[0].p));
+      FNSSL_TRY(lstm_bwd(c, lf, F(pl.res[0]), DF, dA_f, nullptr, bw[0]));
+      FNSSL_TRY(weight_grads(c, lf, grad, dA_f.p, XF.p, nullptr, Fk[0].p));
     }
   }
   return FNSSL_OK;
@@ -482,8 +475,8 @@ int fnssl_train_step(fnssl_train* t, float* theta, float* grad, float* exp_avg, 
   FNSSL_HIP(hipMemsetAsync(grad, 0, n * sizeof(float), fnssl::as_stream(stream)));
   FNSSL_HIP(hipMemsetAsync(loss, 0, sizeof(float), fnssl::as_stream(stream)));
   const long long n_total = (long long)nb * np * (nt / 12) * 2 * nf;
-  TRY(fnssl_train_backward(t, theta, grad, x, gt, nb, np, nf, nt, seed_base, 0, n_total, loss, workspace, workspace_bytes, stream));
-  TRY(fnssl_adam_step(theta, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, 1.f, stream));
+  FNSSL_TRY(fnssl_train_backward(t, theta, grad, x, gt, nb, np, nf, nt, seed_base, 0, n_total, loss, workspace, workspace_bytes, stream));
+  FNSSL_TRY(fnssl_adam_step(theta, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, 1.f, stream));
   FNSSL_HIP(hipMemsetAsync(theta, 0, sizeof(float), fnssl::as_stream(stream)));   // element 0 stays the constant 0
   return FNSSL_OK;
 }

@@ -20,7 +20,10 @@
 //   * partial tiles go to a workspace [slab][M][N]; a second kernel adds them up in slab order (deterministic, no
 //     float atomics) into the caller's gradient (+=: chunks accumulate).
 // Roof: fp32 MFMA (157.3 TFLOP/s); algorithmic work 2 * R * M * N flop per layer, compulsory traffic R * (M + N) * 4 B.
-#include "common.h"
+#include "host.h"
+
+using fnssl::enqueue;
+using fnssl::Kernel;
 
 namespace {
 
@@ -424,10 +427,7 @@ int fnssl_lstm_weight_grads(const fnssl_wgrad_desc* d, void* stream) {
   p.timed = false;
 #endif
   const size_t need = fnssl_lstm_weight_grads_workspace_bytes(p.rows, H, nd, d->c0, d->c2);
-  if (!d->workspace || d->workspace_bytes < need) {
-    fnssl::set_error("lstm_weight_grads: workspace %zu < %zu bytes", d->workspace_bytes, need);
-    return FNSSL_E_WORKSPACE;
-  }
+  FNSSL_TRY(fnssl::check_workspace("lstm_weight_grads", d->workspace, d->workspace_bytes, need));
   p.part = reinterpret_cast<float*>(d->workspace);
   p.part_db = p.part + (size_t)p.slabs * p.M * p.ncat;
   hipStream_t st = fnssl::as_stream(stream);
@@ -435,15 +435,8 @@ int fnssl_lstm_weight_grads(const fnssl_wgrad_desc* d, void* stream) {
   const int per_xcd = (nitems + 7) / 8;
   {
     fnssl::TimedLaunch tl(H >= 256 ? "wgrad_h256" : "wgrad_h128", st, 2.0 * (double)p.rows * p.M * p.ncat);
-    if (kWgradLds > 48 * 1024) {
-      FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgradLds));
-      FNSSL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWgradLds));
-    }
-    if (p.xs)
-      hipLaunchKernelGGL(wgrad_small_kernel, dim3(per_xcd * 8), dim3(kThreads), kWgradLds, st, p);
-    else
-      hipLaunchKernelGGL(wgrad_kernel, dim3(per_xcd * 8), dim3(kThreads), kWgradLds, st, p);
-    FNSSL_CHECK_LAUNCH("wgrad_kernel");
+    FNSSL_TRY(p.xs ? enqueue(st, Kernel{wgrad_small_kernel, kThreads, kWgradLds, "wgrad_small_kernel"}, per_xcd * 8, p)
+                   : enqueue(st, Kernel{wgrad_kernel, kThreads, kWgradLds, "wgrad_kernel"}, per_xcd * 8, p));
   }
   ReduceParams r{};
   r.part = p.part;
@@ -463,8 +456,7 @@ int fnssl_lstm_weight_grads(const fnssl_wgrad_desc* d, void* stream) {
   const long long total = (long long)p.M * p.ncat + p.M;
   {
     fnssl::TimedLaunch tl("wgrad_reduce", st);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, r);
-    FNSSL_CHECK_LAUNCH("wgrad_reduce_kernel");
+    FNSSL_TRY(enqueue(st, Kernel{wgrad_reduce_kernel, 256, 0, "wgrad_reduce_kernel"}, (unsigned)((total + 255) / 256), r));
   }
   return FNSSL_OK;
 }

@@ -312,7 +312,7 @@ int fnssl_lstm_plan_rounds(int hidden, int nseq, int ndir, int ncu, int* waves_p
 int fnssl_lstm_forward(const fnssl_lstm_desc* d, void* stream);
 
 /* Which kernel family fnssl_lstm_forward(d) takes on the current device with the current environment (host-only,
- * launches nothing: the forward's own router runs with a launch context that enqueues nothing — csrc/lstm_host.h —
+ * launches nothing: the forward's own router runs with a launch context that enqueues nothing — csrc/host.h —
  * so the answer cannot drift from what the call does).  Tests assert it, so that "cluster kernel == rounds" comparisons cannot silently compare the
  * rounds with the rounds.  *rounds (optional) = number of launches of the family (planner rounds; 1 otherwise). */
 #define FNSSL_LSTM_FAMILY_GENERIC 1         /* lstm_rec_kernel rounds (any shape)                               */

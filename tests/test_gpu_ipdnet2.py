@@ -87,6 +87,19 @@ def test_causal_conv1d_vs_reference_and_streaming(dev):
     assert_close(torch.cat(parts, -1).cpu().numpy(), g["cc_out"], RTOL, ATOL, "CausalConv1d chunked")
 
 
+def test_encoder_wider_than_the_matrix_pipe_kernels(dev):
+    """cin * 5 > 160: no matrix-pipe instantiation holds the weights, so the fp32 call takes the scalar-operand kernel and
+    the bf16 call is refused."""
+    from fnssl import spatialnet as sn
+    from oracle import ipdnet2_oracle as O2
+    w, b, x = rs_randn(2601, (96, 40, 5), 0.1), rs_randn(2602, (96,), 0.1), rs_randn(2603, (1, 40, 16, 6))
+    xd, wT, bd = to_dev(x, dev), to_dev(w, dev).permute(1, 2, 0).contiguous(), to_dev(b, dev)
+    want = np.stack([O2.causal_conv1d(x[:, :, f, :], w, b)[0] for f in range(16)], 1).transpose(0, 1, 3, 2)
+    assert_close(sn.encoder(xd, wT, bd).cpu().numpy(), want, RTOL, ATOL, "encoder cin 40")
+    with pytest.raises(RuntimeError, match=r"cin \* 5 <= 160"):
+        sn.encoder(xd, wT, bd, precision=sn.BF16)
+
+
 def test_fconv_full_pool_freqinverse_vs_reference(dev):
     g = load_golden("g14_ipdnet2")
     from oracle import ipdnet2_oracle as O2

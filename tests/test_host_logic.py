@@ -160,6 +160,27 @@ def test_spatialnet_entry_points_validate_before_touching_the_device():
     assert b"precision" in lib.fnssl_last_error()
 
 
+def test_spatialnet_workspace_sizes_are_pinned_and_a_short_workspace_is_refused():
+    """One workspace layout per entry point (spatialnet.hip: SnWsLayout, MambaWsLayout) behind the size, the check and the
+    carve-up: the sizes are pinned, and a workspace one byte short is refused with both byte counts, before any launch."""
+    lib = _lib.load()
+    assert lib.fnssl_sn_forward_workspace_bytes(2, 256, 10) == 3983616
+    assert lib.fnssl_sn_forward_workspace_bytes(1, 128, 7) == 697344
+    assert lib.fnssl_sn_mamba_workspace_bytes(3, 7, 8) == 413952
+    buf = np.zeros(64, np.float32)
+    p = buf.ctypes.data // 16 * 16 + 16
+    net = _lib.SnNet()
+    net.dim_input, net.num_layers, net.time_ratio, net.precision = 10, 1, 1, 0
+    assert lib.fnssl_sn_forward(C.byref(net), p, 0, 0, 0, 1, 1, 128, 7, None, 0, p, p, 697344 - 1, None) == -3
+    assert lib.fnssl_last_error() == b"sn_forward: workspace 697343 < 697344 bytes"
+    w = _lib.SnMambaW()
+    for name, _ in w._fields_:
+        setattr(w, name, p)
+    v = _lib.BtfView(p, 96, 96, 96)
+    assert lib.fnssl_sn_mamba(C.byref(v), 3, 7, 8, C.byref(w), 1, 1, None, None, 0, p, 96, 96, 96, p, 413952 - 1, 0, None) == -3
+    assert lib.fnssl_last_error() == b"sn_mamba: workspace 413951 < 413952 bytes"
+
+
 def test_ipdnet2_dropin_keeps_reference_names_and_rejects_cpu():
     import importlib.util
     import torch
