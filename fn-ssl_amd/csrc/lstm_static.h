@@ -13,22 +13,11 @@
 // concatenated tensor (NS2 = 1) and the optional fused residual output.
 #pragma once
 
-#include "lstm_kernel.h"
+#include "lstm_wave.h"
 
 #pragma clang fp contract(off)
 
 namespace fnssl_lstm {
-
-template <int I>
-using ic = std::integral_constant<int, I>;
-
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(ic<I>{});
-    static_for<N, I + 1>(f);
-  }
-}
 
 // ABL = true: timing-ablation twin driven by FNSSL_ABLATE (bits as in lstm_rec_kernel); wrong results.
 template <int H, int NW, int M, int NV0, int NS0, int NS2, int CHQ, int PAD, int MODE, bool ABL = false, int XD = 4,
@@ -48,35 +37,15 @@ __global__ void __launch_bounds__(NW * 64) lstm_static_kernel(const LstmParams p
   static_assert(!(NS0 && NV0), "remainder-only or block-only summed input");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
-  const int lane = threadIdx.x & 63;
-  const int n = lane & 15, g = lane >> 4;
-  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int dir = blockIdx.x / p.wgs_per_dir;
-  const int wg = blockIdx.x - dir * p.wgs_per_dir;
-  const int task = p.task0 + wg * NW + w;
-  int q = task * 16 + n;
-  const bool valid = q < p.nseq && task < p.task1;
-  if (q >= p.nseq) q = p.nseq - 1;
-  const long long qo = q / p.q_inner, qi = q - qo * p.q_inner;
-
-  unsigned vo0 = 0, vo2 = 0, voo = 0, vok = 0, voo2 = 0;
-  const rsrc_t rx0 = split_addr(p.src0.p, qo * p.src0.so + qi * p.src0.si, 4 * g, vo0);
-  const rsrc_t rx2 = HAS2 ? split_addr(p.src2.p, qo * p.src2.so + qi * p.src2.si, g, vo2) : rx0;
-  const unsigned vo2v = vo2 + 12 * g;   // 16-channel blocks of the concatenated input: lane (n, g) reads 4g..4g+3
-  const rsrc_t rsk = SUM ? split_addr(p.skip.p, qo * p.skip.so + qi * p.skip.si, dir * H + 4 * g, vok) : rx0;
-  const rsrc_t ro = split_addr(p.out, qo * p.out_so + qi * p.out_si, dir * H + 4 * g, voo);
-  const rsrc_t ro2 = SUM ? split_addr(p.out_sum, qo * p.out_so + qi * p.out_si, dir * H + 4 * g, voo2) : ro;
-  const rsrc_t rc = make_rsrc(cell_record<NS>(p.cscratch, p.ntasks, dir, task < p.task1 ? task : p.ntasks + w));
-  const unsigned cy = (unsigned)p.carry;   // streaming (see lstm_rec_kernel)
-  const rsrc_t rw = make_rsrc(p.wpack[dir]);
-  const unsigned st0 = (unsigned)(p.src0.st * 4), st2 = HAS2 ? (unsigned)(p.src2.st * 4) : 0u;
-  const unsigned sto = (unsigned)(p.out_st * 4), stk = SUM ? (unsigned)(p.skip.st * 4) : 0u;
-  const unsigned vlane = lane * 16;
-  const bool rev = dir == 1;
+  const WaveSeq<H, NW, 1, HAS2, SUM> pl(p);
+  const int lane = pl.lane, w = pl.w;
+  const unsigned vo0 = pl.vo0 - (NS0 ? 12 * pl.g : 0);   // remainder-only input: lane (n, g) reads channel g, not 4g..4g+3
+  const unsigned vo2v = pl.vo2 + 12 * pl.g;   // 16-channel blocks of the concatenated input: lane (n, g) reads 4g..4g+3
+  const unsigned cy = (unsigned)p.carry;      // streaming (see lstm_rec_kernel)
   const int abl = ABL ? p.ablate : 0;
-  if (NS0) vo0 -= 12 * g;   // remainder-only input: lane (n, g) reads channel g, not 4g..4g+3
 
-  // ---- weight ring ---------------------------------------------------------------
+  // ---- weight ring (this kernel's own, not lstm_wave.h's RegRing / quad_step: through those its registers move and
+  // the compiler peels the slice loop of other instantiations — tools/isa_compare.py, profiles/r12/) ---------------
   char* const lds_rd = smem + lane * 16;
   char* const lds_wr = smem + w * 1024 + lane * 16;
   constexpr int NSLOT = 2;
@@ -89,7 +58,7 @@ __global__ void __launch_bounds__(NW * 64) lstm_static_kernel(const LstmParams p
 #pragma unroll
     for (int m = 0; m < M; ++m) {
       const int r = w + m * NW;
-      if (r < CH && src_vq * 4 + r < QPS * 4) stg[m] = bld4(rw, vlane, (unsigned)(src_rec + r) * 1024u);
+      if (r < CH && src_vq * 4 + r < QPS * 4) stg[m] = bld4(pl.rw, pl.vlane, (unsigned)(src_rec + r) * 1024u);
     }
     src_vq += CHQ;
     src_rec += CH;
@@ -177,28 +146,28 @@ __global__ void __launch_bounds__(NW * 64) lstm_static_kernel(const LstmParams p
 #pragma unroll
   for (int i = 0; i < XD; ++i) xr[i] = zero4;
   {
-    const unsigned tt0 = rev ? p.nsteps - 1 : 0;
-    static_for<(NV0 < XD ? NV0 : XD)>([&](auto v) { xr[v.value] = bld4(rx0, vo0, tt0 * st0 + 64 * v.value); });
+    const unsigned tt0 = pl.rev ? p.nsteps - 1 : 0;
+    static_for<(NV0 < XD ? NV0 : XD)>([&](auto v) { xr[v.value] = bld4(pl.rx0, vo0, tt0 * pl.st0 + 64 * v.value); });
   }
 
   for (int step = 0; step < p.nsteps; ++step) {
-    const unsigned tt = rev ? p.nsteps - 1 - step : step;
-    const unsigned ttn = step + 1 < p.nsteps ? (rev ? tt - 1 : tt + 1) : tt;
-    const unsigned o0 = tt * st0, o2 = tt * st2, oo = (tt + cy) * sto, ok = tt * stk;
+    const unsigned tt = pl.rev ? p.nsteps - 1 - step : step;
+    const unsigned ttn = step + 1 < p.nsteps ? (pl.rev ? tt - 1 : tt + 1) : tt;
+    const unsigned o0 = tt * pl.st0, o2 = tt * pl.st2, oo = (tt + cy) * pl.sto, ok = tt * pl.stk;
     float xs0[NS0 > 0 ? NS0 : 1], xs2[NS2 > 0 ? NS2 : 1];   // 4-channel remainder blocks: lane (n, g) holds channel 4u + g
-    static_for<NS0>([&](auto u) { xs0[u.value] = bld1(rx0, vo0, o0 + 64 * NV0 + 16 * u.value); });
-    static_for<NS2>([&](auto u) { xs2[u.value] = bld1(rx2, vo2, o2 + 64 * NV2 + 16 * u.value); });
+    static_for<NS0>([&](auto u) { xs0[u.value] = bld1(pl.rx0, vo0, o0 + 64 * NV0 + 16 * u.value); });
+    static_for<NS2>([&](auto u) { xs2[u.value] = bld1(pl.rx2, pl.vo2, o2 + 64 * NV2 + 16 * u.value); });
     v4f xv2[NV2 > 0 ? NV2 : 1];   // the concatenated input is the same for every slice: held for the whole step
-    static_for<NV2>([&](auto v) { xv2[v.value] = bld4(rx2, vo2v, o2 + 64 * v.value); });
+    static_for<NV2>([&](auto v) { xv2[v.value] = bld4(pl.rx2, vo2v, o2 + 64 * v.value); });
     if ((step > 0 || cy) && !(abl & 32)) {
-      const unsigned op = (rev ? tt + 1 : tt - 1 + cy) * sto;
+      const unsigned op = (pl.rev ? tt + 1 : tt - 1 + cy) * pl.sto;
 #pragma unroll
-      for (int s = 0; s < NS; ++s) hold[s] = bld4(ro, voo, op + 64 * s);
+      for (int s = 0; s < NS; ++s) hold[s] = bld4(pl.ro, pl.voo, op + 64 * s);
     }
 
     for (int s = 0; s < NS; ++s) {
       v4f cprev = zero4, skipv = zero4;
-      const unsigned nx = (s + 1 < NS ? tt : ttn) * st0;   // x of the next slice / next step
+      const unsigned nx = (s + 1 < NS ? tt : ttn) * pl.st0;   // x of the next slice / next step
 
       // quad 0: bias -> accumulators
       acc[0] = a0;
@@ -214,15 +183,15 @@ __global__ void __launch_bounds__(NW * 64) lstm_static_kernel(const LstmParams p
         SQUAD(1 + V, xb.x, xb.y, xb.z, xb.w);
         if (!(abl & 1)) {
           if constexpr (V + XD < NV0)
-            xr[V % XD] = bld4(rx0, vo0, o0 + 64 * (V + XD));
+            xr[V % XD] = bld4(pl.rx0, vo0, o0 + 64 * (V + XD));
           else
-            xr[V % XD] = bld4(rx0, vo0, nx + 64 * (V + XD - NV0));   // wraps into the next slice
+            xr[V % XD] = bld4(pl.rx0, vo0, nx + 64 * (V + XD - NV0));   // wraps into the next slice
         }
       });
       // cell state and residual operand of this slice: requested after the x part (whose ring
       // registers they reuse), still a whole recurrent part ahead of their use
-      if ((step > 0 || cy) && !(abl & 16)) cprev = bld4(rc, vlane, s * 1024);
-      if (SUM && !(abl & 16)) skipv = bld4(rsk, vok, ok + 64 * s);
+      if ((step > 0 || cy) && !(abl & 16)) cprev = bld4(pl.rc, pl.vlane, s * 1024);
+      if (SUM && !(abl & 16)) skipv = bld4(pl.rsk, pl.vok, ok + 64 * s);
       static_for<NS0>([&](auto u) { SQUAD1(1 + NV0 + decltype(u)::value, xs0[decltype(u)::value]); });
       static_for<NV2>([&](auto v) {
         constexpr int V = decltype(v)::value;
@@ -240,27 +209,25 @@ __global__ void __launch_bounds__(NW * 64) lstm_static_kernel(const LstmParams p
         ring_end(ic<QPS + decltype(u)::value>{});
       });
       // cell update
-      v4f cn, hn;
-      if (ABL && (abl & 2)) {
-        cn = acc[1] + cprev + acc[0];
-        hn = acc[3] + acc[2];
-      } else {
-        const v4f ig = sigmoid4(acc[0]);
-        const v4f fg = sigmoid4(acc[1]);
-        const v4f gg = tanh4(acc[2]);
-        const v4f og = sigmoid4(acc[3]);
-        cn = cell4(fg, cprev, ig, gg);
-        hn = mul_rn4(og, tanh4(cn));
-      }
-      asm("" : "+v"(hn.x), "+v"(hn.y), "+v"(hn.z), "+v"(hn.w));   // h + skip adds the ROUNDED h
-      if (!(abl & 4)) {
-        bst4(cn, rc, vlane, s * 1024);
-        if (valid) {
-          bst4(hn, ro, voo, oo + 64 * s);
-          if (SUM) bst4(add_rn4(hn, skipv), ro2, voo2, oo + 64 * s);
+      if (ABL && (abl & 6)) {   // timing-ablation twin (wrong results): bit 2 = no gate math, bit 4 = no stores
+        Cell c;
+        if (abl & 2) {
+          c.cn = acc[1] + cprev + acc[0];
+          c.hn = acc[3] + acc[2];
+        } else {
+          c = cell_math(acc, cprev);
+        }
+        if (!(abl & 4)) {
+          bst4(c.cn, pl.rc, pl.vlane, s * 1024);
+          if (pl.valid) {
+            bst4(c.hn, pl.ro, pl.voo, oo + 64 * s);
+            if (SUM) bst4(add_rn4(c.hn, skipv), pl.ro2, pl.voo2, oo + 64 * s);
+          }
+        } else {
+          asm volatile("" ::"v"(c.cn), "v"(c.hn));
         }
       } else {
-        asm volatile("" ::"v"(cn), "v"(hn));
+        cell_step(pl, acc, cprev, skipv, s * 1024, oo + 64 * s);
       }
     }
   }

@@ -13,7 +13,7 @@
 // compile time per chunk; anything else it issued in between only makes the wait stricter; vector memory operations
 // complete in order).
 //
-// Weight stream: QUAD-interleaved [slice quad][quad][slice in quad][4 records] (quad_stream_kernel, lstm.hip: one tiny
+// Weight stream: QUAD-interleaved [slice quad][quad][slice in quad][4 records] (interleave_stream_kernel<4>, lstm.hip: one tiny
 // launch per call into the workspace, like the pair-interleaved copy of lstm_static3_kernel).  Same k order per sequence
 // and slice, same gate code: bit-identical to every other fp32 family.
 #pragma once
@@ -51,36 +51,16 @@ __global__ void __launch_bounds__(NW * 64) lstm_static4_kernel(const LstmParams 
   static_assert(VQ % CHQ == 0, "chunks must tile the (padded) slice quad");
   constexpr int CH = 16 * CHQ;                          // records per chunk: CHQ quads x 4 slices x 4 records
   constexpr int M = (CH + NW - 1) / NW;                 // DMA instructions per wave and chunk
-  static_assert(NB % XD == 0 && XD <= NV0, "the operand ring depth must divide the block count");
   static_assert(PAD < CHQ, "a chunk of padding only would have no operand load to count the DMA by");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
-  const int lane = threadIdx.x & 63;
-  const int n = lane & 15, g = lane >> 4;
-  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int dir = blockIdx.x / p.wgs_per_dir;
-  const int wg = blockIdx.x - dir * p.wgs_per_dir;
-  const int task = p.task0 + wg * NW + w;
-  int q = task * 16 + n;
-  const bool valid = q < p.nseq && task < p.task1;
-  if (q >= p.nseq) q = p.nseq - 1;
-  const long long qo = q / p.q_inner, qi = q - qo * p.q_inner;
-
-  unsigned vo0 = 0, vo2 = 0, voo = 0, vok = 0, voo2 = 0;
-  const rsrc_t rx0 = split_addr(p.src0.p, qo * p.src0.so + qi * p.src0.si, 4 * g, vo0);
-  const rsrc_t rx2 = HAS2 ? split_addr(p.src2.p, qo * p.src2.so + qi * p.src2.si, g, vo2) : rx0;
-  const rsrc_t rsk = SUM ? split_addr(p.skip.p, qo * p.skip.so + qi * p.skip.si, dir * H + 4 * g, vok) : rx0;
-  const rsrc_t ro = split_addr(p.out, qo * p.out_so + qi * p.out_si, dir * H + 4 * g, voo);
-  const rsrc_t ro2 = SUM ? split_addr(p.out_sum, qo * p.out_so + qi * p.out_si, dir * H + 4 * g, voo2) : ro;
+  const WaveSeq<H, NW, 1, HAS2, SUM> pl(p);
+  const int lane = pl.lane, w = pl.w;
   // h_{-1} = 0: the same base with ZERO records — every lane is out of range and the load returns 0
   const rsrc_t rzero = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.out), 0, 0, 0x00020000);
-  const rsrc_t rc = make_rsrc(cell_record<NS>(p.cscratch, p.ntasks, dir, task < p.task1 ? task : p.ntasks + w));
-  const rsrc_t rw = make_rsrc(p.wpack[dir]);
-  const unsigned st0 = (unsigned)(p.src0.st * 4), st2 = HAS2 ? (unsigned)(p.src2.st * 4) : 0u;
-  const unsigned sto = (unsigned)(p.out_st * 4), stk = SUM ? (unsigned)(p.skip.st * 4) : 0u;
-  const unsigned vlane = lane * 16;
-  const bool rev = dir == 1;
 
+  // (ring and SQUAD4 macros are this kernel's own: on lstm_wave.h's reader and quad_step<4> the same instructions came out in
+  // another order and the plain layer measured 0.1 - 0.4 % slower, profiles/r12/)
   // ---- weight ring: 2 slots of CHQ quads = 16 CHQ records, filled by LDS-DMA (1 KiB per wave-instruction: lane l's 16
   // bytes land at the slot address + 16 l; not counted by the compiler — see the vmcnt in ring_end) ---------------------
   const unsigned lds0 = (unsigned)(uintptr_t)smem;
@@ -95,7 +75,7 @@ __global__ void __launch_bounds__(NW * 64) lstm_static4_kernel(const LstmParams 
       if (r < CH && src_vq * 16 + r < QPS * 16) {
         const unsigned soff = (unsigned)(src_rec + r) * 1024u;
         const unsigned ld = lds0 + (unsigned)(dslot * CH + r) * 1024u;
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(vlane), "s"(rw),
+        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(pl.vlane), "s"(pl.rw),
                      "s"(__builtin_amdgcn_readfirstlane(ld)), "s"(__builtin_amdgcn_readfirstlane(soff))
                      : "memory");
       }
@@ -199,22 +179,17 @@ __global__ void __launch_bounds__(NW * 64) lstm_static4_kernel(const LstmParams 
     ring_end(ic<(QI)>{});                                                                         \
   } while (0)
 
-  // ---- operand ring: block b of a pass (b < NV0: channels 16 b.. of x_t; else hidden units 16 (b - NV0).. of h_{t-1})
-  // lives in br[b % XD] and is requested right after block b - XD has been consumed
-  v4f br[XD];
-  {
-    const unsigned tt0 = rev ? p.nsteps - 1 : 0;
-    static_for<XD>([&](auto v) { br[v.value] = bld4(rx0, vo0, tt0 * st0 + 64 * v.value); });
-  }
+  OperandRing<XD, NV0, NS> ops;   // [x_t | h_{t-1}]: block b of a pass lives in ops.br[b % XD]
+  ops.prime(pl.rx0, pl.vo0, (pl.rev ? p.nsteps - 1 : 0) * pl.st0);
 
   for (int step = 0; step < p.nsteps; ++step) {
-    const unsigned tt = rev ? p.nsteps - 1 - step : step;
-    const unsigned ttn = step + 1 < p.nsteps ? (rev ? tt - 1 : tt + 1) : tt;
-    const unsigned o0 = tt * st0, o2 = tt * st2, oo = tt * sto, ok = tt * stk;
-    const unsigned op = (rev ? tt + 1 : tt - 1) * sto;     // row of h_{step - 1} (not addressed at step 0: zero records)
-    const rsrc_t rh = step > 0 ? ro : rzero;
+    const unsigned tt = pl.rev ? p.nsteps - 1 - step : step;
+    const unsigned ttn = step + 1 < p.nsteps ? (pl.rev ? tt - 1 : tt + 1) : tt;
+    const unsigned o0 = tt * pl.st0, o2 = tt * pl.st2, oo = tt * pl.sto, ok = tt * pl.stk;
+    const unsigned op = (pl.rev ? tt + 1 : tt - 1) * pl.sto;     // row of h_{step - 1} (not addressed at step 0: zero records)
+    const rsrc_t rh = step > 0 ? pl.ro : rzero;
     float xs2 = 0.f;
-    if (NS2) xs2 = bld1(rx2, vo2, o2);
+    if (NS2) xs2 = bld1(pl.rx2, pl.vo2, o2);
 
     for (int pr = 0; pr < NP; ++pr) {
       const int s0 = 4 * pr;
@@ -228,7 +203,7 @@ __global__ void __launch_bounds__(NW * 64) lstm_static4_kernel(const LstmParams 
       if constexpr (PF4) static_for<4>([&](auto s_) { cpf[s_.value] = zero4; skf[s_.value] = zero4; });
       const bool last = pr + 1 == NP;
       // the input blocks requested across the end of the pass: the same row, or (last quad) the next step's
-      const unsigned nx = (last ? ttn : tt) * st0;
+      const unsigned nx = (last ? ttn : tt) * pl.st0;
       // quad 0: the four slices' bias records -> accumulators
       acc[0][0] = a0;
       acc[0][1] = a1;
@@ -242,30 +217,19 @@ __global__ void __launch_bounds__(NW * 64) lstm_static4_kernel(const LstmParams 
         constexpr int B = decltype(bc)::value;
         constexpr int QI = B < NV0 ? 1 + B : 1 + NS2 + B;          // the 4-channel quad of block 1 sits between x and h
         if constexpr (NS2 > 0 && B == NV0) SQUAD4_1(1 + NV0, xs2);
-        const v4f ob = br[B % XD];
+        const v4f ob = ops.get(bc);
         // request block B + XD (of this pass, or — wrapping — of the next one) BEFORE this block's chunk can end: the
         // count in ring_end relies on one operand-block load per block quad having been issued ahead of its barrier
-        constexpr int BN = (B + XD) % NB;
-        if (!skip_ring) {
-          if constexpr (B + XD < NB) {
-            if constexpr (BN < NV0)
-              br[B % XD] = bld4(rx0, vo0, o0 + 64 * BN);
-            else
-              br[B % XD] = bld4(rh, voo, op + 64 * (BN - NV0));
-          } else {
-            static_assert(BN < NV0, "the wrapped requests are input blocks");
-            br[B % XD] = bld4(rx0, vo0, nx + 64 * BN);
-          }
-        }
+        if (!skip_ring) ops.request(bc, pl.rx0, pl.vo0, o0, nx, rh, pl.voo, op);
         if constexpr (!PF4 && B == NB - 4) {   // cell state / residual operand of the first slice: four quads ahead of their use
-          if (step > 0) cprev = bld4(rc, vlane, s0 * 1024);
-          if (SUM) skipv = bld4(rsk, vok, ok + 64 * s0);
+          if (step > 0) cprev = bld4(pl.rc, pl.vlane, s0 * 1024);
+          if (SUM) skipv = bld4(pl.rsk, pl.vok, ok + 64 * s0);
         }
         if constexpr (PF4 && B == NB - 3) {    // ... of all four slices, at the start of the pass's last chunk
           static_for<4>([&](auto s_) {
             constexpr int S = decltype(s_)::value;
-            if (step > 0) cpf[S] = bld4(rc, vlane, (s0 + S) * 1024);
-            if (SUM) skf[S] = bld4(rsk, vok, ok + 64 * (s0 + S));
+            if (step > 0) cpf[S] = bld4(pl.rc, pl.vlane, (s0 + S) * 1024);
+            if (SUM) skf[S] = bld4(pl.rsk, pl.vok, ok + 64 * (s0 + S));
           });
         }
         SQUAD4(QI, ob.x, ob.y, ob.z, ob.w);
@@ -274,25 +238,19 @@ __global__ void __launch_bounds__(NW * 64) lstm_static4_kernel(const LstmParams 
         ring_step(ic<QPS + decltype(u)::value>{});
         ring_end(ic<QPS + decltype(u)::value>{});
       });
-      // cell updates of the four slices; the next slice's cell state / residual operand in flight under this one's gate math
+      // cell updates of the four slices; without PF4 the next slice's cell state / residual operand in flight under this
+      // one's gate math
       static_for<4>([&](auto sc) {
         constexpr int S = decltype(sc)::value;
-        const v4f ig = sigmoid4(acc[S][0]), fg = sigmoid4(acc[S][1]), gg = tanh4(acc[S][2]), og = sigmoid4(acc[S][3]);
-        v4f cp_cur = cprev, sk_cur = skipv;
         if constexpr (PF4) {
-          cp_cur = cpf[S];
-          sk_cur = skf[S];
-        } else if constexpr (S < 3) {
-          if (step > 0) cprev = bld4(rc, vlane, (s0 + S + 1) * 1024);
-          if (SUM) skipv = bld4(rsk, vok, ok + 64 * (s0 + S + 1));
-        }
-        const v4f cn = cell4(fg, cp_cur, ig, gg);
-        v4f hn = mul_rn4(og, tanh4(cn));
-        asm("" : "+v"(hn.x), "+v"(hn.y), "+v"(hn.z), "+v"(hn.w));   // h + skip adds the ROUNDED h
-        bst4(cn, rc, vlane, (s0 + S) * 1024);
-        if (valid) {
-          bst4(hn, ro, voo, oo + 64 * (s0 + S));
-          if (SUM) bst4(add_rn4(hn, sk_cur), ro2, voo2, oo + 64 * (s0 + S));
+          cell_step(pl, acc[S], cpf[S], skf[S], (s0 + S) * 1024, oo + 64 * (s0 + S));
+        } else {
+          cell_step(pl, acc[S], cprev, skipv, (s0 + S) * 1024, oo + 64 * (s0 + S), [&] {
+            if constexpr (S < 3) {
+              if (step > 0) cprev = bld4(pl.rc, pl.vlane, (s0 + S + 1) * 1024);
+              if (SUM) skipv = bld4(pl.rsk, pl.vok, ok + 64 * (s0 + S + 1));
+            }
+          });
         }
       });
     }

@@ -92,7 +92,7 @@ const char* fnssl_last_error(void);
 #define FNSSL_TUNE_CLUSTER_SPIN_LIMIT 34      /* bounded-wait length of the cluster kernels' hand-offs (default 2^20 spins, about 1.5 s) */
 #define FNSSL_TUNE_CLUSTER_TEST_STALL 35      /* FAULT INJECTION: m + 1 = member m of cluster 0 never shows up (the give-up / guarded-fallback tests) */
 #define FNSSL_TUNE_RESERVED_CUS 36            /* compute units the caller keeps busy with other work (RCCL's all-reduce kernels under an overlapped backward): the cluster-resident kernels size their co-resident grids for device CUs minus this */
-#define FNSSL_TUNE_NO_F32_SMALL 37            /* few-sequence fp32 launches (one utterance, a streaming chunk) on the split kernels instead of the slice-resident cluster kernel (lstm_f32s.h) */
+#define FNSSL_TUNE_NO_F32_SMALL 37            /* few-sequence fp32 launches (one utterance, a streaming chunk) on the split kernels instead of the slice-resident cluster kernel (lstm_f32c.h) */
 #define FNSSL_TUNE_F32C_MIN_GROUPS 38        /* smallest (groups x directions) count the fp32 cluster kernels take for inference (default: see lstm_f32c.hip) */
 #define FNSSL_TUNE_F32C_GATE_SPLIT 39        /* fp32 cluster kernels: 1 = every wave owns a group, 4 = the four waves of a slot share one (one gate each); default: by groups per cluster */
 #define FNSSL_TUNE_CLUSTER_FULL_TILES 40    /* bf16 cluster kernels, H = 128: full clusters of 24 tiles (rounds 3 - 5) instead of more clusters of 17 - 20 */

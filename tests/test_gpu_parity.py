@@ -1702,6 +1702,55 @@ def test_lstm_operand_ring_kernel_equals_one_slice_kernel(dev, monkeypatch, c2, 
     assert_close(got, want, RTOL, ATOL, "operand-ring kernel vs oracle")
 
 
+@pytest.mark.parametrize("summed", [False, True])
+def test_lstm_operand_ring_kernels_ragged_tail(dev, summed):
+    """The tail handling of the full-chip narrow-band rounds (one prologue for lstm_static.h, lstm_static3.h and
+    lstm_static4.h: clamped sequence index, `valid`, the spare cell slot of an idle wave) at the smallest ragged size that
+    still selects them on 256 CUs: 49125 sequences = 3071 groups, so the last workgroup's last wave has no group and the
+    last group has 5 sequences.  Three steps; the three families bit for bit, plain and with the fused residual; the last
+    sequence against the oracle; the rows behind the last sequence untouched."""
+    ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+    if ncu != 256:
+        pytest.skip("49125 sequences select the full-chip rounds on 256 CUs, this device has %d" % ncu)
+    from fnssl import _lib, ops
+    from oracle import fnssl_oracle as O
+    H, c0, nt, nf, spare = 256, 256, 3, 49125, 27
+    sd = lstm_state(c0, H, False, 5830)
+    w = [ops.pack_lstm(sd["L.weight_ih_l0"], sd["L.weight_hh_l0"], sd["L.bias_ih_l0"], sd["L.bias_hh_l0"], c0, 0, dev)]
+    g = torch.Generator(device="cpu").manual_seed(5831)
+    x0 = (torch.randn((1, nt, nf, c0), generator=g) * 0.5).to(dev)
+    skip = (torch.randn((1, nt, nf, H), generator=g) * 0.5).to(dev) if summed else None
+
+    def run(plan=False, **knobs):
+        # the row's knobs and no others, whatever the environment says; without the small-shape cluster kernel, which
+        # would take 3071 groups
+        tuning = _lib.make_tuning(base=_lib.Tuning(), no_f32_small=1, **knobs)
+        buf = torch.full((1, nf + spare, nt, H), float("nan"), device=dev)
+        bsum = torch.full((1, nf + spare, nt, H), float("nan"), device=dev) if summed else None
+        out = buf[:, :nf].permute(0, 2, 1, 3)
+        osum = bsum[:, :nf].permute(0, 2, 1, 3) if summed else None
+        r = ops.lstm_layer("narrow", x0, None, None, w, H, out, skip=skip, out_sum=osum, plan_only=plan, tuning=tuning)
+        return r if plan else (buf, bsum)
+
+    assert run(plan=True) == ("static4", 1), run(plan=True)
+    assert run(plan=True, no_static4=1) == ("static3", 1), run(plan=True, no_static4=1)
+    assert run(plan=True, no_static3=1)[0] == "static", run(plan=True, no_static3=1)
+    a, asum = run()
+    b, bsum = run(no_static4=1)
+    c, csum = run(no_static3=1)
+    assert torch.isfinite(a[:, :nf]).all()
+    for name, o, osum in (("static4", a, asum), ("static3", b, bsum), ("static", c, csum)):
+        assert torch.isnan(o[:, nf:]).all(), "%s wrote behind the last sequence" % name
+        assert not summed or torch.isnan(osum[:, nf:]).all(), "%s wrote the residual output behind the last sequence" % name
+    assert torch.equal(a[:, :nf], b[:, :nf]), "four slices per pass differ from two at the ragged tail"
+    assert torch.equal(a[:, :nf], c[:, :nf]), "four slices per pass differ from the one-slice kernel at the ragged tail"
+    if summed:
+        assert torch.equal(asum[:, :nf], bsum[:, :nf]) and torch.equal(asum[:, :nf], csum[:, :nf])
+        assert torch.equal(asum[:, :nf], a[:, :nf] + skip.permute(0, 2, 1, 3))
+    want = O.lstm(x0[0, :, nf - 1].cpu().numpy()[None], sd, "L.", False)            # [1, nt, H]
+    assert_close(a[0, nf - 1].cpu().numpy()[None], want, RTOL, ATOL, "last valid sequence vs oracle")
+
+
 def test_lstm_forward_rejects_an_input_that_aliases_an_output(dev):
     """The recurrence re-reads h_{t-1} from `out`, and the guarded fallback kernels behind a cluster kernel that gave up
     recompute the layer from the inputs: an in-place call would corrupt either (round-4 advisor note) — it is an error."""
