@@ -13,7 +13,10 @@ running the HIP kernels of libfnssl_hip.so (``fnssl_sn_*``) on an MI355X.
 Built for the configuration the reference ships (run_IPDnet2.py:103-119): dim_hidden 96, dim_squeeze 8,
 kernel_size (5, .), conv_groups (8, .), all-LN norms, attention 'mamba(16,4)', dim_output 16,
 fre_compression_ratio 16, time_compression_layer 0; other values raise.  Forward only (``eval()``), fp32, ROCm
-tensors only — there is no CPU path.  ``inference=True`` (the reference's frame-by-frame Mamba stepping, :170-177)
+tensors only — there is no CPU path.  One branch trains: on a layer in ``train()`` mode with gradients enabled,
+``SpatialNetLayer._mamba(x, mamba, norm, dropout)`` (LN + Mamba along T, without the residual) returns a tensor with a
+``grad_fn`` whose backward is ``fnssl_sn_mamba_backward`` (fp32 only; ``inference=True`` raises there).  The other
+branches have no backward yet, so ``SpatialNetLayer.forward`` and ``OnlineSpatialNet.forward`` still raise in ``train()``.  ``inference=True`` (the reference's frame-by-frame Mamba stepping, :170-177)
 is honoured: the Mamba blocks are driven one frame per ``fnssl_sn_mamba`` call with carried conv / SSM state (the
 role of ``InferenceParams``); it computes the same function as the parallel mode with T x the launches.  The Mamba block follows the
 published algorithm ("parity unpinned": no mamba_ssm to compare with, see oracle/ipdnet2_oracle.py).
@@ -32,6 +35,7 @@ if _PKG not in sys.path:
 
 from fnssl import ops                                               # noqa: E402
 from fnssl import spatialnet as sn                                  # noqa: E402
+from fnssl import spatialnet_train as sn_train                      # noqa: E402
 from Model import _is_bf16, _param_key, _require_eval               # noqa: E402
 
 
@@ -225,6 +229,15 @@ class SpatialNetLayer(nn.Module):
     def _mamba(self, x: torch.Tensor, mamba: Mamba, norm: nn.Module, dropout: nn.Module, inference: bool = False):
         """LN + Mamba along T WITHOUT the residual (:166-181).  ``inference``: frame-by-frame stepping from zero state,
         the carried conv taps / SSM state playing ``InferenceParams`` (:170-177)."""
+        if self.training and torch.is_grad_enabled():
+            # the one trainable branch so far: autograd around the same forward kernels (fnssl/spatialnet_train.py)
+            if inference:
+                raise RuntimeError("SpatialNetLayer._mamba: training runs whole sequences; inference=True (frame-by-frame "
+                                   "stepping with carried state) is forward-only")
+            if _is_bf16(self) or x.dtype != torch.float32:
+                raise RuntimeError("SpatialNetLayer._mamba: the Mamba block trains in fp32; call .float() on the module "
+                                   "and its input")
+            return sn_train.mamba_train(x, norm, mamba, residual=False)
         w = self._packed(x.device)
         mw = w[3] if mamba is self.mhsa else w[4]
         xf = x.float()

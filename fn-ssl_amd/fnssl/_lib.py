@@ -66,6 +66,7 @@ SYMBOLS = [
     "fnssl_ipd2doa_tracks", "fnssl_doa_metrics",
     "fnssl_doa_metrics_ex", "fnssl_ipd2doa_mse_tracks", "fnssl_ipdnet2_targets",
     "fnssl_stream_frontend_state_bytes", "fnssl_stream_frontend",
+    "fnssl_sn_mamba_backward_workspace_bytes", "fnssl_sn_mamba_backward_chunk", "fnssl_sn_mamba_backward",
 ]
 
 
@@ -153,6 +154,11 @@ class SnFullW(C.Structure):
 class SnMambaW(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ln_w", "ln_b", "winT", "conv_w", "conv_b", "wxT", "wdt", "bdt", "a", "d",
                                           "woT")]
+
+
+class SnMambaGrads(C.Structure):
+    """fnssl_sn_mamba_grads: one pointer per field of SnMambaW, the gradient in the same packed layout."""
+    _fields_ = SnMambaW._fields_
 
 
 class SnLayer(C.Structure):
@@ -323,6 +329,11 @@ def load():
     lib.fnssl_sn_mamba_workspace_bytes.argtypes = [i, i, i]
     lib.fnssl_sn_mamba_workspace_bytes.restype = sz
     lib.fnssl_sn_mamba.argtypes = [PV, i, i, i, C.POINTER(SnMambaW), i, i, vp, vp, i, vp, ll, ll, ll, vp, sz, i, vp]
+    lib.fnssl_sn_mamba_backward_workspace_bytes.argtypes = [i, i, i]
+    lib.fnssl_sn_mamba_backward_workspace_bytes.restype = sz
+    lib.fnssl_sn_mamba_backward_chunk.argtypes = []
+    lib.fnssl_sn_mamba_backward.argtypes = [PV, i, i, i, C.POINTER(SnMambaW), i, i, vp, sz, vp, ll, ll, ll, vp, ll, ll, ll,
+                                            C.POINTER(SnMambaGrads), vp, sz, vp]
     lib.fnssl_sn_head.argtypes = [PV, i, i, i, vp, vp, vp, vp, vp, vp]
     lib.fnssl_sn_forward_workspace_bytes.argtypes = [i, i, i]
     lib.fnssl_sn_forward_workspace_bytes.restype = sz

@@ -1028,6 +1028,31 @@ int fnssl_sn_mamba(const fnssl_btf_view* x, int nb, int nt, int nf, const fnssl_
                    float* out, long long o_sb, long long o_st, long long o_sf,
                    void* workspace, size_t workspace_bytes, int precision, void* stream);
 
+/* ---- Mamba block, backward (additive: FNSSL_ABI_VERSION stays 19) --------------------------------------------------------
+ * The gradients of one fnssl_sn_mamba call in FNSSL_PRECISION_FP32 on whole sequences from zero state (conv_state,
+ * ssm_state NULL, carry 0).  The forward's workspace is the saved state: xz | dbl | y exactly as that call left them, of
+ * exactly fnssl_sn_mamba_workspace_bytes(nb, nt, nf) bytes; x, w, residual and time_pool are the forward's arguments.
+ *   dout view [nb, nt / time_pool, nf, 96], dx view [nb, nt, nf, 96] (strides in floats, multiples of 4, 16-byte bases);
+ *   dx is written — frames past the last whole pooling window get exactly 0.
+ *   g: one pointer per weight of fnssl_sn_mamba_w, in the packed layout the kernels read (winT [96][384], wxT [192][40]
+ *   with the two pad columns zero, woT [192][96], a = the gradient with respect to A = -exp(A_log)); written, not
+ *   accumulated.  Bitwise reproducible: every sum runs in a fixed order, no float atomics.
+ * fnssl_sn_mamba_backward_chunk() is the number of steps between two checkpoints of the scan's state (the reverse scan
+ * rebuilds h_t chunk by chunk), so that tests can place nt around it. */
+typedef struct {
+  float *ln_w, *ln_b, *winT, *conv_w, *conv_b, *wxT, *wdt, *bdt, *a, *d, *woT;
+} fnssl_sn_mamba_grads;
+
+size_t fnssl_sn_mamba_backward_workspace_bytes(int nb, int nt, int nf);
+int fnssl_sn_mamba_backward_chunk(void);
+int fnssl_sn_mamba_backward(const fnssl_btf_view* x, int nb, int nt, int nf, const fnssl_sn_mamba_w* w,
+                            int residual, int time_pool,
+                            const void* fwd_workspace, size_t fwd_workspace_bytes,
+                            const float* dout, long long d_sb, long long d_st, long long d_sf,
+                            float* dx, long long x_sb, long long x_st, long long x_sf,
+                            const fnssl_sn_mamba_grads* g,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /*
  * Replaces FreqInverse + tanh + decoder + the output re-ordering (IPDnet2.py:23-43, 355-364).
  *   x     [nb, nt2, nfc, 96] (nfc compressed bins; nf = 16 * nfc)
