@@ -13,10 +13,12 @@ running the HIP kernels of libfnssl_hip.so (``fnssl_sn_*``) on an MI355X.
 Built for the configuration the reference ships (run_IPDnet2.py:103-119): dim_hidden 96, dim_squeeze 8,
 kernel_size (5, .), conv_groups (8, .), all-LN norms, attention 'mamba(16,4)', dim_output 16,
 fre_compression_ratio 16, time_compression_layer 0; other values raise.  Forward only (``eval()``), fp32, ROCm
-tensors only — there is no CPU path.  One branch trains: on a layer in ``train()`` mode with gradients enabled,
-``SpatialNetLayer._mamba(x, mamba, norm, dropout)`` (LN + Mamba along T, without the residual) returns a tensor with a
-``grad_fn`` whose backward is ``fnssl_sn_mamba_backward`` (fp32 only; ``inference=True`` raises there).  The other
-branches have no backward yet, so ``SpatialNetLayer.forward`` and ``OnlineSpatialNet.forward`` still raise in ``train()``.  ``inference=True`` (the reference's frame-by-frame Mamba stepping, :170-177)
+tensors only — there is no CPU path.  A layer trains: on a ``SpatialNetLayer`` in ``train()`` mode with gradients
+enabled, ``_mamba(x, mamba, norm, dropout)``, ``_fconv(ml, x)`` and ``_full(x)`` (each branch without the residual) return
+tensors with a ``grad_fn`` whose backward is ``fnssl_sn_mamba_backward`` / ``fnssl_sn_fconv_backward`` /
+``fnssl_sn_full_backward`` (fp32 only; ``inference=True`` raises there), and ``forward_train(x, time_pool=1)`` runs the
+whole layer that way (fnssl.spatialnet_train.layer_train: x + 40 parameter gradients).  The encoder and the head have no
+backward yet, so ``SpatialNetLayer.forward`` and ``OnlineSpatialNet.forward`` still raise in ``train()``.  ``inference=True`` (the reference's frame-by-frame Mamba stepping, :170-177)
 is honoured: the Mamba blocks are driven one frame per ``fnssl_sn_mamba`` call with carried conv / SSM state (the
 role of ``InferenceParams``); it computes the same function as the parallel mode with T x the launches.  The Mamba block follows the
 published algorithm ("parity unpinned": no mamba_ssm to compare with, see oracle/ipdnet2_oracle.py).
@@ -219,18 +221,31 @@ class SpatialNetLayer(nn.Module):
         return self._w
 
     # the three branches on their own (WITHOUT the residual), as the reference's private helpers return them
+    def _train_path(self, who: str, x: torch.Tensor) -> bool:
+        """The rule of every branch: autograd around the forward kernels on a module in ``train()`` with gradients on."""
+        if not (self.training and torch.is_grad_enabled()):
+            return False
+        if _is_bf16(self) or x.dtype != torch.float32:
+            raise RuntimeError("SpatialNetLayer.%s: the branch trains in fp32; call .float() on the module and its input"
+                               % who)
+        return True
+
     def _fconv(self, ml: nn.ModuleList, x: torch.Tensor) -> torch.Tensor:
+        if self._train_path("_fconv", x):
+            return sn_train.fconv_train(x, ml, residual=False)
         w = self._packed(x.device)
         return sn.fconv(x.float(), w[0] if ml is self.fconv1 else w[2], residual=False, precision=_prec(self)).to(x.dtype)
 
     def _full(self, x: torch.Tensor) -> torch.Tensor:
+        if self._train_path("_full", x):
+            return sn_train.full_train(x, self, residual=False)
         return sn.full(x.float(), self._packed(x.device)[1], residual=False, precision=_prec(self)).to(x.dtype)
 
     def _mamba(self, x: torch.Tensor, mamba: Mamba, norm: nn.Module, dropout: nn.Module, inference: bool = False):
         """LN + Mamba along T WITHOUT the residual (:166-181).  ``inference``: frame-by-frame stepping from zero state,
         the carried conv taps / SSM state playing ``InferenceParams`` (:170-177)."""
         if self.training and torch.is_grad_enabled():
-            # the one trainable branch so far: autograd around the same forward kernels (fnssl/spatialnet_train.py)
+            # autograd around the same forward kernels (fnssl/spatialnet_train.py)
             if inference:
                 raise RuntimeError("SpatialNetLayer._mamba: training runs whole sequences; inference=True (frame-by-frame "
                                    "stepping with carried state) is forward-only")
@@ -271,6 +286,19 @@ class SpatialNetLayer(nn.Module):
             y = sn.mamba(y, m0, out=y, precision=pr)
             y = sn.mamba(y, m1, out=y, precision=pr)
         return y.to(x.dtype), None
+
+    @ops.on_device
+    def forward_train(self, x: torch.Tensor, time_pool: int = 1) -> torch.Tensor:
+        """The layer in ``train()`` mode: x [B, F, T, H] -> [B, F', T // time_pool, H] with a ``grad_fn`` that reaches x and
+        the layer's 40 parameters (fnssl.spatialnet_train.layer_train).  At time_pool 1 the forward's bits are
+        ``eval()``'s.  ``forward`` itself stays forward-only until the encoder and the head have a backward."""
+        if not self.training:
+            raise RuntimeError("SpatialNetLayer.forward_train: the module is in eval() mode; call .train() first, or use "
+                               "forward for inference")
+        if _is_bf16(self) or x.dtype != torch.float32:
+            raise RuntimeError("SpatialNetLayer.forward_train: the layer trains in fp32; call .float() on the module and "
+                               "its input")
+        return sn_train.layer_train(self, x, time_pool)
 
     def extra_repr(self) -> str:
         return f"full_share={self.full_share}"

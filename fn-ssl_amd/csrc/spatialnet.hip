@@ -31,48 +31,11 @@
 
 namespace {
 
-constexpr int HS = 8;      // dim_squeeze
-constexpr int NG = 8;      // f-conv groups
-constexpr int CG = 12;     // channels per group
-constexpr int KF = 5;      // f-conv taps
 constexpr int KE = 5;      // encoder taps
 constexpr int DO = 16;     // dim_output
 
 constexpr int kFconvTile = 4992;   // floats per buffer: max over nf in [8, 256] of (256/nf) * (nf + 4) * 13
 constexpr int kFullTile = 2304;    // max over nf of (256/nf) * (nf * 8 + 4)
-
-__device__ __forceinline__ void load_row(float (&x)[H], const float* __restrict__ p) {
-  const float4* p4 = reinterpret_cast<const float4*>(p);
-#pragma unroll
-  for (int i = 0; i < H / 4; ++i) {
-    const float4 v = p4[i];
-    x[4 * i] = v.x;
-    x[4 * i + 1] = v.y;
-    x[4 * i + 2] = v.z;
-    x[4 * i + 3] = v.w;
-  }
-}
-
-__device__ __forceinline__ void store_row(float* __restrict__ p, const float (&x)[H]) {
-  float4* p4 = reinterpret_cast<float4*>(p);
-#pragma unroll
-  for (int i = 0; i < H / 4; ++i) p4[i] = make_float4(x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3]);
-}
-
-// nn.LayerNorm statistics over the thread's own 96 channels (biased variance, eps inside the root).
-__device__ __forceinline__ void ln_stats(const float (&x)[H], float& mean, float& rstd) {
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < H; ++c) s += x[c];
-  mean = s * (1.f / H);
-  float v = 0.f;
-#pragma unroll
-  for (int c = 0; c < H; ++c) {
-    const float d = x[c] - mean;
-    v = fmaf(d, d, v);
-  }
-  rstd = 1.f / sqrtf(v * (1.f / H) + kEps);
-}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -1,6 +1,7 @@
-// What the IPDnet2 forward kernels (spatialnet.hip) and the Mamba block's backward (spatialnet_train.hip) share: the shape
-// constants of the Mamba block, the matrix-pipe helpers (LDS weight image, MFMA tile product), the index split, and the
-// host-side view checks and the forward workspace layout.
+// What the IPDnet2 forward kernels (spatialnet.hip), the Mamba block's backward (spatialnet_train.hip) and the f-conv /
+// full-band backward (spatialnet_layer_train.hip) share: the shape constants, a point's row load / store and LayerNorm
+// statistics, the matrix-pipe helpers (LDS weight image, MFMA tile product), the index split, the host-side view checks,
+// the forward workspace layout and the ordered reduction of partial sums.
 #pragma once
 
 #include <cstdlib>
@@ -16,7 +17,45 @@ constexpr int NST = 16;    // Mamba d_state
 constexpr int RK = 6;      // Mamba dt_rank
 constexpr int KC = 4;      // Mamba d_conv
 constexpr int XP = 40;     // x_proj outputs (6 + 16 + 16) padded to a float4 multiple
+constexpr int HS = 8;      // dim_squeeze
+constexpr int NG = 8;      // f-conv groups
+constexpr int CG = 12;     // channels per group
+constexpr int KF = 5;      // f-conv taps
 constexpr float kEps = 1e-5f;
+
+// one point's 96 channels, to and from the thread's registers
+__device__ __forceinline__ void load_row(float (&x)[H], const float* __restrict__ p) {
+  const float4* p4 = reinterpret_cast<const float4*>(p);
+#pragma unroll
+  for (int i = 0; i < H / 4; ++i) {
+    const float4 v = p4[i];
+    x[4 * i] = v.x;
+    x[4 * i + 1] = v.y;
+    x[4 * i + 2] = v.z;
+    x[4 * i + 3] = v.w;
+  }
+}
+
+__device__ __forceinline__ void store_row(float* __restrict__ p, const float (&x)[H]) {
+  float4* p4 = reinterpret_cast<float4*>(p);
+#pragma unroll
+  for (int i = 0; i < H / 4; ++i) p4[i] = make_float4(x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3]);
+}
+
+// nn.LayerNorm statistics over the thread's own 96 channels (biased variance, eps inside the root).
+__device__ __forceinline__ void ln_stats(const float (&x)[H], float& mean, float& rstd) {
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < H; ++c) s += x[c];
+  mean = s * (1.f / H);
+  float v = 0.f;
+#pragma unroll
+  for (int c = 0; c < H; ++c) {
+    const float d = x[c] - mean;
+    v = fmaf(d, d, v);
+  }
+  rstd = 1.f / sqrtf(v * (1.f / H) + kEps);
+}
 
 // x * sigmoid(x) with the reciprocal instruction (1 ulp) instead of the IEEE division sequence (10 operations): the
 // unsqueeze of the full-band branch alone applies it 96 times per point
@@ -209,6 +248,35 @@ inline unsigned mfma_grid(long long npts, int per_cu, int waves = 8) {
   const long long wgs = ((npts + 15) / 16 + waves - 1) / waves;
   const long long cap = (long long)fnssl::device_cus() * per_cu;
   return (unsigned)(wgs < cap ? wgs : cap);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// ordered reduction of per-workgroup (or per-slab, per-sequence) partial sums: the last step of every backward
+// ---------------------------------------------------------------------------------------------------------
+// One row of partials may feed several gradients: column i of the row belongs to segment k with end[k-1] <= i < end[k].
+struct RowSegs {
+  int end[4];
+  float* out[4];
+};
+
+// out[i] = part[0][i] + part[1][i] + ...   (rows `stride` floats apart), in row order
+__global__ void __launch_bounds__(256)
+sn_reduce_rows_kernel(const float* __restrict__ part, int rows, long long stride, RowSegs segs) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= segs.end[3]) return;
+  float v = 0.f;
+#pragma unroll 16
+  for (int r = 0; r < rows; ++r) v += part[r * stride + i];        // the loads of 16 rows in flight, the adds in row order
+  const int k = (i >= segs.end[0]) + (i >= segs.end[1]) + (i >= segs.end[2]);
+  segs.out[k][i - (k ? segs.end[k - 1] : 0)] = v;
+}
+
+// the row's columns go to o0 (n0 of them), then o1 (n1), ...; unused segments: n = 0
+inline int reduce_rows(hipStream_t s, const float* part, long long rows, long long stride, int n0, float* o0, int n1 = 0,
+                       float* o1 = nullptr, int n2 = 0, float* o2 = nullptr, int n3 = 0, float* o3 = nullptr) {
+  const RowSegs segs = {{n0, n0 + n1, n0 + n1 + n2, n0 + n1 + n2 + n3}, {o0, o1, o2, o3}};
+  return enqueue(s, Kernel{sn_reduce_rows_kernel, 256, 0, "sn_reduce_rows_kernel"}, blocks_of(segs.end[3]), part, (int)rows, stride,
+                 segs);
 }
 
 }  // namespace

@@ -614,24 +614,6 @@ sn_wgrad_pts_kernel(const float* __restrict__ A, int lda, int M, const float* __
   }
 }
 
-// One row of partials may feed several gradients: column i of the row belongs to segment k with end[k-1] <= i < end[k].
-struct RowSegs {
-  int end[4];
-  float* out[4];
-};
-
-// out[i] = part[0][i] + part[1][i] + ...   (rows `stride` floats apart), in row order
-__global__ void __launch_bounds__(256)
-sn_reduce_rows_kernel(const float* __restrict__ part, int rows, long long stride, RowSegs segs) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= segs.end[3]) return;
-  float v = 0.f;
-#pragma unroll 16
-  for (int r = 0; r < rows; ++r) v += part[r * stride + i];        // the loads of 16 rows in flight, the adds in row order
-  const int k = (i >= segs.end[0]) + (i >= segs.end[1]) + (i >= segs.end[2]);
-  segs.out[k][i - (k ? segs.end[k - 1] : 0)] = v;
-}
-
 // The regions of the backward workspace, front to back: the one description behind its size, its check and its carve-up.
 struct MambaBwdWsLayout {         // fnssl_sn_mamba_backward, npts = nb * nt * nf points, nseq = nb * nf sequences
   WsRegion dyu, dxz, ddbl, u, ln, dO;   // [npts, E] (dy, then du), [npts, 2E], [npts, XP], [npts, E], [npts, H], [npts, H]
@@ -654,14 +636,6 @@ struct MambaBwdWsLayout {         // fnssl_sn_mamba_backward, npts = nb * nt * n
     total = pw.end();
   }
 };
-
-// the row's columns go to o0 (n0 of them), then o1 (n1), ...; unused segments: n = 0
-int reduce_rows(hipStream_t s, const float* part, long long rows, long long stride, int n0, float* o0, int n1 = 0,
-                float* o1 = nullptr, int n2 = 0, float* o2 = nullptr, int n3 = 0, float* o3 = nullptr) {
-  const RowSegs segs = {{n0, n0 + n1, n0 + n1 + n2, n0 + n1 + n2 + n3}, {o0, o1, o2, o3}};
-  return enqueue(s, Kernel{sn_reduce_rows_kernel, 256, 0, "sn_reduce_rows_kernel"}, blocks_of(segs.end[3]), part, (int)rows, stride,
-                 segs);
-}
 
 // out[M][N] = A^T B over the points: split-K partial tiles, then the slabs in order
 template <int NT>

@@ -67,6 +67,8 @@ SYMBOLS = [
     "fnssl_doa_metrics_ex", "fnssl_ipd2doa_mse_tracks", "fnssl_ipdnet2_targets",
     "fnssl_stream_frontend_state_bytes", "fnssl_stream_frontend",
     "fnssl_sn_mamba_backward_workspace_bytes", "fnssl_sn_mamba_backward_chunk", "fnssl_sn_mamba_backward",
+    "fnssl_sn_fconv_backward_workspace_bytes", "fnssl_sn_fconv_backward",
+    "fnssl_sn_full_backward_workspace_bytes", "fnssl_sn_full_backward",
 ]
 
 
@@ -159,6 +161,16 @@ class SnMambaW(C.Structure):
 class SnMambaGrads(C.Structure):
     """fnssl_sn_mamba_grads: one pointer per field of SnMambaW, the gradient in the same packed layout."""
     _fields_ = SnMambaW._fields_
+
+
+class SnFconvGrads(C.Structure):
+    """fnssl_sn_fconv_grads: one pointer per field of SnFconvW, the gradient in the same packed layout."""
+    _fields_ = SnFconvW._fields_
+
+
+class SnFullGrads(C.Structure):
+    """fnssl_sn_full_grads: one pointer per field of SnFullW, the gradient in the same packed layout."""
+    _fields_ = SnFullW._fields_
 
 
 class SnLayer(C.Structure):
@@ -334,6 +346,13 @@ def load():
     lib.fnssl_sn_mamba_backward_chunk.argtypes = []
     lib.fnssl_sn_mamba_backward.argtypes = [PV, i, i, i, C.POINTER(SnMambaW), i, i, vp, sz, vp, ll, ll, ll, vp, ll, ll, ll,
                                             C.POINTER(SnMambaGrads), vp, sz, vp]
+    for name in ("fnssl_sn_fconv_backward_workspace_bytes", "fnssl_sn_full_backward_workspace_bytes"):
+        getattr(lib, name).argtypes = [i, i, i]
+        getattr(lib, name).restype = sz
+    lib.fnssl_sn_fconv_backward.argtypes = [PV, i, i, i, C.POINTER(SnFconvW), i, i, vp, ll, ll, ll, vp, ll, ll, ll,
+                                            C.POINTER(SnFconvGrads), vp, sz, vp]
+    lib.fnssl_sn_full_backward.argtypes = [PV, i, i, i, C.POINTER(SnFullW), i, vp, ll, ll, ll, vp, ll, ll, ll,
+                                           C.POINTER(SnFullGrads), vp, sz, vp]
     lib.fnssl_sn_head.argtypes = [PV, i, i, i, vp, vp, vp, vp, vp, vp]
     lib.fnssl_sn_forward_workspace_bytes.argtypes = [i, i, i]
     lib.fnssl_sn_forward_workspace_bytes.restype = sz

@@ -1,12 +1,16 @@
-"""Training front of one IPDnet2 Mamba block: ``torch.autograd`` around ``fnssl_sn_mamba`` (forward) and
-``fnssl_sn_mamba_backward`` (include/fnssl.h).  fp32, whole sequences from zero state, ROCm tensors only.
+"""Training front of one IPDnet2 layer: ``torch.autograd`` around the forward entry points ``fnssl_sn_mamba`` /
+``fnssl_sn_fconv`` / ``fnssl_sn_full`` and their backwards ``fnssl_sn_mamba_backward`` / ``fnssl_sn_fconv_backward`` /
+``fnssl_sn_full_backward`` (include/fnssl.h).  fp32, whole sequences from zero state, ROCm tensors only.
 
     y = mamba_train(x, norm, mamba, residual=True, time_pool=1)      # x logical [B, F, T, 96]
     y.backward(...)   # fills x.grad and the .grad of the LayerNorm's 2 and the Mamba's 9 parameters
+    y = fconv_train(x, ml, residual=True, pool=1)                    # ml = ModuleList(LN, Conv1d, PReLU): 5 parameters
+    y = full_train(x, layer, residual=True)                          # norm_full, squeeze, full, unsqueeze: 8 parameters
+    y = layer_train(layer, x, time_pool=1)                           # the five branches of a SpatialNetLayer: 40
 
-The forward is the inference call itself (same kernels, same bits) into a workspace tensor of its own, which is what the
-backward recomputes from: xz | dbl | y as the forward left them, plus x.  The rest of the network (f-conv, full-band
-branch, encoder, head) has no backward yet, so ``OnlineSpatialNet`` stays forward-only.
+Every forward is the inference call itself (same kernels, same bits).  The Mamba block saves the forward's workspace
+(xz | dbl | y) plus x; the f-conv and full-band branches are local to a frame and save x alone.  The encoder and the head
+have no backward yet, so ``OnlineSpatialNet`` stays forward-only.
 """
 from __future__ import annotations
 
@@ -15,9 +19,9 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import SnMambaGrads, SnMambaW, check
+from ._lib import SnFconvGrads, SnFconvW, SnFullGrads, SnFullW, SnMambaGrads, SnMambaW, check
 from .ops import _need_dev, _ptr, _stream
-from .spatialnet import E, FP32, H, KC, NST, RK, _conform, _new_bfth, _view, pack_mamba
+from .spatialnet import E, FP32, H, HS, KC, NST, RK, _conform, _new_bfth, _view, pack_fconv, pack_full, pack_mamba
 
 PARAMS = ("in_proj.weight", "conv1d.weight", "conv1d.bias", "x_proj.weight", "dt_proj.weight", "dt_proj.bias", "A_log", "D",
           "out_proj.weight")
@@ -84,3 +88,131 @@ def mamba_train(x, norm, mamba, residual: bool = True, time_pool: int = 1):
         raise RuntimeError("fnssl.spatialnet_train: expected [B, F, T, %d], got %s" % (H, tuple(x.shape)))
     sd = dict(mamba.named_parameters())
     return MambaFunction.apply(x, bool(residual), int(time_pool), norm.weight, norm.bias, *[sd[n] for n in PARAMS])
+
+
+def _need_fp32(what, x, params):
+    if x.dtype != torch.float32 or any(p.dtype != torch.float32 for p in params):
+        raise RuntimeError("fnssl.spatialnet_train: %s trains in fp32 (got %s)"
+                           % (what, sorted({str(t.dtype) for t in (x,) + tuple(params)})))
+
+
+class FconvFunction(torch.autograd.Function):
+    """pool_F(residual * x + PReLU(Conv1d_g(LN(x)))) along F for x logical [B, F, T, 96]; arguments after ``pool``:
+    LayerNorm weight and bias, Conv1d weight [96, 12, 5] and bias, PReLU weight."""
+
+    @staticmethod
+    def forward(ctx, x, residual, pool, *params):
+        _need_fp32("the f-conv branch", x, params)                 # before _need_dev, whose own message does not say fp32
+        _need_dev(x, *params)
+        with torch.cuda.device(x.device):
+            xc = _conform(x.detach())
+            nb, nf, nt, _ = xc.shape
+            sd = dict(zip(("p.0.weight", "p.0.bias", "p.1.weight", "p.1.bias", "p.2.weight"), params))
+            w, keep = pack_fconv(sd, "p", x.device)
+            out = _new_bfth(nb, nf // pool, nt, x.device)              # fresh: never aliases x, which the backward reads
+            xv, ov = _view(xc), _view(out)
+            check(_lib.load().fnssl_sn_fconv(C.byref(xv), nb, nt, nf, C.byref(w), int(residual), int(pool), ov.p, ov.sb,
+                                             ov.st, ov.sf, FP32, _stream()), "sn_fconv")
+        ctx.save_for_backward(xc, *keep.tensors)                       # the 5 packed tensors, in fnssl_sn_fconv_w's order
+        ctx.residual, ctx.pool = int(residual), int(pool)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        xc, *packed = ctx.saved_tensors
+        with torch.cuda.device(xc.device):
+            nb, nf, nt, _ = xc.shape
+            lib = _lib.load()
+            w = SnFconvW(*[t.data_ptr() for t in packed])
+            grads = [torch.empty_like(t) for t in packed]
+            g = SnFconvGrads(*[t.data_ptr() for t in grads])
+            dx = _new_bfth(nb, nf, nt, xc.device)
+            ws = torch.empty(lib.fnssl_sn_fconv_backward_workspace_bytes(nb, nt, nf), dtype=torch.uint8, device=xc.device)
+            dout = _conform(dout.float())
+            xv, dv, gv = _view(xc), _view(dout), _view(dx)
+            check(lib.fnssl_sn_fconv_backward(C.byref(xv), nb, nt, nf, C.byref(w), ctx.residual, ctx.pool, dv.p, dv.sb, dv.st,
+                                              dv.sf, gv.p, gv.sb, gv.st, gv.sf, C.byref(g), _ptr(ws), ws.numel(), _stream()),
+                  "sn_fconv_backward")
+        gln_w, gln_b, gwT, gbias, gprelu = grads
+        # wT is [g][tap][ci][o]: back to Conv1d's [g * 12 + o, ci, tap], the inverse of pack_fconv's permute
+        gw = gwT.view(8, 5, 12, 12).permute(0, 3, 2, 1).reshape(H, 12, 5)
+        return dx, None, None, gln_w, gln_b, gw, gbias, gprelu
+
+
+class FullFunction(torch.autograd.Function):
+    """residual * x + SiLU(unsqueeze(Linear_F(SiLU(squeeze(LN(x)))))) for x logical [B, F, T, 96]; arguments after
+    ``residual``: norm_full weight, bias; squeeze.0 weight [8, 96, 1], bias; full weight [F, F], bias; unsqueeze.0 weight
+    [96, 8, 1], bias."""
+
+    @staticmethod
+    def forward(ctx, x, residual, *params):
+        _need_fp32("the full-band branch", x, params)                 # before _need_dev, whose own message does not say fp32
+        _need_dev(x, *params)
+        with torch.cuda.device(x.device):
+            xc = _conform(x.detach())
+            nb, nf, nt, _ = xc.shape
+            sd = dict(zip(("norm_full.weight", "norm_full.bias", "squeeze.0.weight", "squeeze.0.bias", "full.weight",
+                           "full.bias", "unsqueeze.0.weight", "unsqueeze.0.bias"), params))
+            w, keep, nfull = pack_full(sd, "", x.device)
+            if nfull != nf:
+                raise RuntimeError("fnssl.spatialnet_train: full.weight is %d x %d, x has %d bins" % (nfull, nfull, nf))
+            out = _new_bfth(nb, nf, nt, x.device)                      # fresh: never aliases x, which the backward reads
+            xv, ov = _view(xc), _view(out)
+            check(_lib.load().fnssl_sn_full(C.byref(xv), nb, nt, nf, C.byref(w), int(residual), ov.p, ov.sb, ov.st, ov.sf,
+                                            FP32, _stream()), "sn_full")
+        ctx.save_for_backward(xc, *keep.tensors)                       # the 8 packed tensors, in fnssl_sn_full_w's order
+        ctx.residual = int(residual)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        xc, *packed = ctx.saved_tensors
+        with torch.cuda.device(xc.device):
+            nb, nf, nt, _ = xc.shape
+            lib = _lib.load()
+            w = SnFullW(*[t.data_ptr() for t in packed])
+            grads = [torch.empty_like(t) for t in packed]
+            g = SnFullGrads(*[t.data_ptr() for t in grads])
+            dx = _new_bfth(nb, nf, nt, xc.device)
+            ws = torch.empty(lib.fnssl_sn_full_backward_workspace_bytes(nb, nt, nf), dtype=torch.uint8, device=xc.device)
+            dout = _conform(dout.float())
+            xv, dv, gv = _view(xc), _view(dout), _view(dx)
+            check(lib.fnssl_sn_full_backward(C.byref(xv), nb, nt, nf, C.byref(w), ctx.residual, dv.p, dv.sb, dv.st, dv.sf,
+                                             gv.p, gv.sb, gv.st, gv.sf, C.byref(g), _ptr(ws), ws.numel(), _stream()),
+                  "sn_full_backward")
+        gln_w, gln_b, gwsT, gbs, gwfT, gbf, gwuT, gbu = grads
+        return (dx, None, gln_w, gln_b, gwsT.t().reshape(HS, H, 1), gbs, gwfT.t(), gbf, gwuT.t().reshape(H, HS, 1), gbu)
+
+
+def _need_bfth(x):
+    if x.dim() != 4 or x.shape[3] != H:
+        raise RuntimeError("fnssl.spatialnet_train: expected [B, F, T, %d], got %s" % (H, tuple(x.shape)))
+
+
+def fconv_train(x, ml, residual: bool = True, pool: int = 1):
+    """pool_F(residual * x + PReLU(conv(LN(x)))) along F with a ``grad_fn``.  ``ml``: the branch's ModuleList (LayerNorm,
+    Conv1d(96, 96, 5, groups 8), PReLU(96)).  The forward's bits are ``fnssl.spatialnet.fconv``'s in fp32."""
+    _need_bfth(x)
+    return FconvFunction.apply(x, bool(residual), int(pool), ml[0].weight, ml[0].bias, ml[1].weight, ml[1].bias, ml[2].weight)
+
+
+def full_train(x, layer, residual: bool = True):
+    """residual * x + the full-band branch of ``layer`` (norm_full, squeeze, full, unsqueeze) with a ``grad_fn``.  The
+    forward's bits are ``fnssl.spatialnet.full``'s in fp32."""
+    _need_bfth(x)
+    return FullFunction.apply(x, bool(residual), layer.norm_full.weight, layer.norm_full.bias, layer.squeeze[0].weight,
+                              layer.squeeze[0].bias, layer.full.weight, layer.full.bias, layer.unsqueeze[0].weight,
+                              layer.unsqueeze[0].bias)
+
+
+def layer_train(layer, x, time_pool: int = 1):
+    """One ``SpatialNetLayer`` with a ``grad_fn``: the five branches composed as ``SpatialNetLayer.forward`` composes the
+    five forward calls (residual inside each call, F pooled by 2 and by 8 in the first layer), ``time_pool`` handed to the
+    second Mamba block.  x logical [B, F, T, 96] -> [B, F', T // time_pool, 96]; at time_pool 1 the bits of
+    ``layer.eval()(x)[0]``."""
+    first = bool(layer.is_first)
+    y = fconv_train(x, layer.fconv1, True, 2 if first else 1)
+    y = full_train(y, layer, True)
+    y = fconv_train(y, layer.fconv2, True, 8 if first else 1)
+    y = mamba_train(y, layer.norm_mhsa, layer.mhsa, True, 1)
+    return mamba_train(y, layer.norm_tconvffn, layer.tconvffn, True, int(time_pool))

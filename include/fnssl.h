@@ -1053,6 +1053,35 @@ int fnssl_sn_mamba_backward(const fnssl_btf_view* x, int nb, int nt, int nf, con
                             const fnssl_sn_mamba_grads* g,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- f-conv and full-band branch, backward (additive: FNSSL_ABI_VERSION stays 19) ----------------------------------------
+ * The gradients of one fnssl_sn_fconv / fnssl_sn_full call in FNSSL_PRECISION_FP32.  x, w, residual and pool are the
+ * forward's arguments, and x is the only saved state: both branches are local to one (b, t) frame, so LayerNorm statistics,
+ * the conv pre-activation and the squeeze / Linear / unsqueeze intermediates are recomputed frame by frame.
+ *   nf a power of two in [8, 256], pool 1, 2 or 8 (the forward's domain);
+ *   dout view [nb, nt, nf / pool, 96] (full: [nb, nt, nf, 96]), dx view [nb, nt, nf, 96]: strides in floats, multiples of
+ *   4, 16-byte bases; dx must not alias x or dout.  dx is written, not accumulated.
+ *   g: one pointer per weight of fnssl_sn_fconv_w / fnssl_sn_full_w, the gradient in the same packed layout (wT
+ *   [8][5][12][12]; wsT [96][8], wfT [nf][nf], wuT [8][96]); written, not accumulated.
+ *   workspace: one row of partial parameter sums per workgroup (at most one workgroup per compute unit) — nothing per point.
+ * Bitwise reproducible on a given device: every sum runs in a fixed order (points of a block, blocks of a workgroup,
+ * workgroups), no float atomics.  PReLU is differentiated as the forward branches: slope where the pre-activation is < 0,
+ * 1 elsewhere. */
+typedef struct { float *ln_w, *ln_b, *wT, *bias, *prelu; } fnssl_sn_fconv_grads;
+typedef struct { float *ln_w, *ln_b, *wsT, *bs, *wfT, *bf, *wuT, *bu; } fnssl_sn_full_grads;
+
+size_t fnssl_sn_fconv_backward_workspace_bytes(int nb, int nt, int nf);
+int fnssl_sn_fconv_backward(const fnssl_btf_view* x, int nb, int nt, int nf, const fnssl_sn_fconv_w* w,
+                            int residual, int pool,
+                            const float* dout, long long d_sb, long long d_st, long long d_sf,
+                            float* dx, long long x_sb, long long x_st, long long x_sf,
+                            const fnssl_sn_fconv_grads* g, void* workspace, size_t workspace_bytes, void* stream);
+
+size_t fnssl_sn_full_backward_workspace_bytes(int nb, int nt, int nf);
+int fnssl_sn_full_backward(const fnssl_btf_view* x, int nb, int nt, int nf, const fnssl_sn_full_w* w, int residual,
+                           const float* dout, long long d_sb, long long d_st, long long d_sf,
+                           float* dx, long long x_sb, long long x_st, long long x_sf,
+                           const fnssl_sn_full_grads* g, void* workspace, size_t workspace_bytes, void* stream);
+
 /*
  * Replaces FreqInverse + tanh + decoder + the output re-ordering (IPDnet2.py:23-43, 355-364).
  *   x     [nb, nt2, nfc, 96] (nfc compressed bins; nf = 16 * nfc)
