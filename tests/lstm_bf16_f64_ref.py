@@ -21,25 +21,32 @@ def _sig(v):
     return 1.0 / (1.0 + np.exp(-v))
 
 
-def step_consistent(x, w_ih, w_hh, b_ih, b_hh, h_dev, reverse=False):
+def step_consistent(x, w_ih, w_hh, b_ih, b_hh, h_dev, reverse=False, rnd=O.bf16_round, bias=None, info=None):
     """x [N, T, I] fp32, h_dev [N, T, H] (what the kernel stored, fp32 or bf16 values) -> float64 [N, T, H].
     The matrix products of all steps are one float64 product (no step depends on the reference's previous h); only
-    c_t = f c + i g and h_t = o tanh(c_t) run sequentially."""
+    c_t = f c + i g and h_t = o tanh(c_t) run sequentially.
+    rnd: what the kernel does to x, the weights and the stored h where they enter the product (the bf16 kernels: nearest-even
+    bf16; the fp32 kernels of tests/lstm_f32_f64_ref.py: nothing).  bias: the [4H] bias as the kernel adds it, when that is not
+    the exact b_ih + b_hh.  info: a dict that receives "pre", the largest |gate pre-activation|."""
     x = np.asarray(x, dtype=F32)
     h_dev = np.asarray(h_dev, dtype=F32)
     N, T, I = x.shape
     H = w_hh.shape[1]
     assert h_dev.shape == (N, T, H), (h_dev.shape, (N, T, H))
-    xb = O.bf16_round(x).astype(F64)
-    wih, whh = O.bf16_round(w_ih).astype(F64), O.bf16_round(w_hh).astype(F64)
-    bias = np.asarray(b_ih, dtype=F64) + np.asarray(b_hh, dtype=F64)
+    xb = rnd(x).astype(F64)
+    wih, whh = rnd(w_ih).astype(F64), rnd(w_hh).astype(F64)
+    if bias is None:
+        bias = np.asarray(b_ih, dtype=F64) + np.asarray(b_hh, dtype=F64)
+    bias = np.asarray(bias, dtype=F64)
     hp = np.zeros((N, T, H), dtype=F64)                       # the operand h_{t-1}: zero at the first step
-    hb = O.bf16_round(h_dev).astype(F64)
+    hb = rnd(h_dev).astype(F64)
     if reverse:
         hp[:, :-1] = hb[:, 1:]
     else:
         hp[:, 1:] = hb[:, :-1]
     g = (xb.reshape(N * T, I) @ wih.T + hp.reshape(N * T, H) @ whh.T + bias).reshape(N, T, 4 * H)
+    if info is not None:
+        info["pre"] = max(float(np.abs(g).max()), info.get("pre", 0.0))
     ig, fg = _sig(g[..., 0:H]), _sig(g[..., H:2 * H])
     gg, og = np.tanh(g[..., 2 * H:3 * H]), _sig(g[..., 3 * H:4 * H])
     c = np.zeros((N, H), dtype=F64)
