@@ -17,8 +17,12 @@ tensors only — there is no CPU path.  A layer trains: on a ``SpatialNetLayer``
 enabled, ``_mamba(x, mamba, norm, dropout)``, ``_fconv(ml, x)`` and ``_full(x)`` (each branch without the residual) return
 tensors with a ``grad_fn`` whose backward is ``fnssl_sn_mamba_backward`` / ``fnssl_sn_fconv_backward`` /
 ``fnssl_sn_full_backward`` (fp32 only; ``inference=True`` raises there), and ``forward_train(x, time_pool=1)`` runs the
-whole layer that way (fnssl.spatialnet_train.layer_train: x + 40 parameter gradients).  The encoder and the head have no
-backward yet, so ``SpatialNetLayer.forward`` and ``OnlineSpatialNet.forward`` still raise in ``train()``.  ``inference=True`` (the reference's frame-by-frame Mamba stepping, :170-177)
+whole layer that way (fnssl.spatialnet_train.layer_train: x + 40 parameter gradients).  The network trains too:
+``OnlineSpatialNet.forward_train(x)`` chains the encoder, the layers and the head, each an autograd function around its
+inference kernel with a HIP backward (``fnssl_sn_encoder_backward``, the three above, ``fnssl_sn_head_backward``), so the
+prediction has ``eval()``'s bits and a ``grad_fn`` that reaches all 2 + 40 L + 4 parameters.  ``SpatialNetLayer.forward``
+and ``OnlineSpatialNet.forward`` themselves stay forward-only and still raise in ``train()``; ``run_step.MyModel`` routes to
+``forward_train`` when built with ``train_on_device=True``.  ``inference=True`` (the reference's frame-by-frame Mamba stepping, :170-177)
 is honoured: the Mamba blocks are driven one frame per ``fnssl_sn_mamba`` call with carried conv / SSM state (the
 role of ``InferenceParams``); it computes the same function as the parallel mode with T x the launches.  The Mamba block follows the
 published algorithm ("parity unpinned": no mamba_ssm to compare with, see oracle/ipdnet2_oracle.py).
@@ -291,7 +295,8 @@ class SpatialNetLayer(nn.Module):
     def forward_train(self, x: torch.Tensor, time_pool: int = 1) -> torch.Tensor:
         """The layer in ``train()`` mode: x [B, F, T, H] -> [B, F', T // time_pool, H] with a ``grad_fn`` that reaches x and
         the layer's 40 parameters (fnssl.spatialnet_train.layer_train).  At time_pool 1 the forward's bits are
-        ``eval()``'s.  ``forward`` itself stays forward-only until the encoder and the head have a backward."""
+        ``eval()``'s.  ``forward`` itself stays forward-only; a whole network trains through
+        ``OnlineSpatialNet.forward_train``."""
         if not self.training:
             raise RuntimeError("SpatialNetLayer.forward_train: the module is in eval() mode; call .train() first, or use "
                                "forward for inference")
@@ -360,6 +365,23 @@ class OnlineSpatialNet(nn.Module):
         if inference:       # the reference's frame-by-frame Mamba stepping (:170-177), see DeviceSpatialNet.forward_stepwise
             return dn.forward_stepwise(x.float()).to(x.dtype)
         return dn.forward(x.float()).to(x.dtype)
+
+    @ops.on_device
+    def forward_train(self, x: torch.Tensor) -> torch.Tensor:
+        """The network in ``train()`` mode: x [B, dim_input, F, T] -> [B, T // 5, 2F, 4, 2] with a ``grad_fn`` that reaches
+        the encoder's 2, every layer's 40 and the head's 4 parameters (fnssl.spatialnet_train.net_train).  Every forward
+        is the inference call itself, so the prediction's bits are ``eval()``'s ``forward``'s.  fp32, whole sequences from
+        zero state; under ``torch.no_grad()`` the result carries no ``grad_fn``."""
+        if not self.training:
+            raise RuntimeError("OnlineSpatialNet.forward_train: the module is in eval() mode; call .train() first, or use "
+                               "forward for inference")
+        if _is_bf16(self) or x.dtype != torch.float32:
+            raise RuntimeError("OnlineSpatialNet.forward_train: the network trains in fp32; call .float() on the module and "
+                               "its input")
+        if x.dim() != 4 or x.shape[1] != self.encoder.in_channels or x.shape[2] != self.num_freqs:
+            raise RuntimeError("OnlineSpatialNet.forward_train: expected [B, %d, %d, T], got %s"
+                               % (self.encoder.in_channels, self.num_freqs, tuple(x.shape)))
+        return sn_train.net_train(self, x)
 
     @ops.on_device
     def forward_stream(self, x: torch.Tensor, state=None):

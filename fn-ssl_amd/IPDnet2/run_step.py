@@ -22,9 +22,14 @@ utterance's targets, azimuths, distances and VAD are cut to the prediction's fra
 methods are called directly.  The constructor is the reference's plus a trailing ``arch``: ``None`` builds the shipped
 ``OnlineSpatialNet(...)`` of :103-119.  ``compile`` is accepted and ignored (there is nothing to compile).
 
-Out of scope: datasets and the CLI, the ``np.save`` dumps of ``test_step``'s evaluation, ``ch_mode='MM'``, and TRAINING:
-``OnlineSpatialNet`` is forward-only, so ``training_step`` raises its forward-only error unless the module is in
-``eval()`` mode, and the loss carries no ``grad_fn``.
+Training (:159-171) is opt-in: ``MyModel(..., train_on_device=True)`` routes ``forward`` to
+``OnlineSpatialNet.forward_train`` while the module is in ``train()`` with gradients enabled, and ``training_step`` then
+aligns the frame counts as the evaluation steps do and returns ``{"loss": loss}`` with the PIT-MSE loss of
+``fnssl.ipdnet_step.PitMSE``, whose ``backward()`` fills the ``.grad`` of every parameter of ``arch`` on the device (fp32).
+With the default ``train_on_device=False`` everything is as before: ``OnlineSpatialNet.forward`` is forward-only, so
+``training_step`` raises its forward-only error unless the module is in ``eval()`` mode, and the loss carries no ``grad_fn``.
+
+Out of scope: datasets and the CLI, the ``np.save`` dumps of ``test_step``'s evaluation, ``ch_mode='MM'``, bf16 training.
 """
 import itertools
 import os
@@ -51,8 +56,9 @@ class MyModel(_Base):
     def __init__(self, tar_useVAD: bool = True, ch_mode: str = 'M', res_the: int = 1, res_phi: int = 180, fs: int = 16000,
                  win_len: int = 512, nfft: int = 512, win_shift_ratio: float = 0.625, method_mode: str = 'IDL',
                  cuda_activated: bool = True, return_metric: bool = True, compile: bool = False, exp_name: str = 'exp',
-                 device: str = 'cuda', arch=None):
+                 device: str = 'cuda', arch=None, train_on_device: bool = False):
         super().__init__()
+        self.train_on_device = bool(train_on_device)
         if (win_len, nfft, win_shift_ratio, fs) != (512, 512, 0.625, 16000):
             raise ValueError("the MI355X path is built for fs 16000, win_len = nfft = 512, hop 320 (run_IPDnet2.py:90-93)")
         if ch_mode != 'M':
@@ -75,6 +81,8 @@ class MyModel(_Base):
         self.last_metrics = None
 
     def forward(self, x):
+        if self.train_on_device and self.arch.training and torch.is_grad_enabled():
+            return self.arch.forward_train(x)
         return self.arch(x)
 
     def _log(self, name, value, **kw):
@@ -114,7 +122,13 @@ class MyModel(_Base):
         return loss
 
     def training_step(self, batch, batch_idx: int = 0):
-        """:159-171.  The network is forward-only: in ``train()`` mode ``self(in_batch)`` raises its forward-only error."""
+        """:159-171.  ``train_on_device``: the aligned prediction of ``forward_train`` and the differentiable PIT-MSE loss.
+        Otherwise the network is forward-only: in ``train()`` mode ``self(in_batch)`` raises its forward-only error."""
+        if self.train_on_device:
+            pred_batch, gt_batch = self._forward_aligned(batch)        # cutting the prediction is a view
+            loss = self.cal_loss(pred_batch=pred_batch, gt_batch=gt_batch)
+            self._log("train/loss", loss, prog_bar=True)
+            return {"loss": loss}
         data_batch = self.data_preprocess(batch[0], batch[1], batch[3], batch[2], batch[4])
         pred_batch = self(data_batch[0])
         loss = self.cal_loss(pred_batch=pred_batch, gt_batch=data_batch[1:])
@@ -138,7 +152,10 @@ class MyModel(_Base):
     def cal_loss(self, pred_batch=None, gt_batch=None, mode='train'):
         """Frame-level PIT-MSE (:237-251) in one HIP kernel.  ``mode='train'``: the loss, a 0-d device tensor; otherwise
         (loss, ipd_gt [nb * nt, nsrc, D], the prediction [nb * nt, nsrc, D] with its tracks in the best permutation),
-        D = 512 * (nmic - 1)."""
+        D = 512 * (nmic - 1).  A ``pred_batch`` that requires a gradient gives, in ``mode='train'``, the same loss with a
+        ``grad_fn`` (``ipdnet_step.PitMSE``)."""
+        if mode == 'train' and pred_batch.requires_grad and torch.is_grad_enabled():
+            return ipdnet_step.PitMSE.apply(pred_batch.to(self.dev).float(), gt_batch[1])
         pred = pred_batch.detach().to(self.dev).float()
         ipd_gt = gt_batch[1]
         want = mode != 'train'

@@ -1509,11 +1509,8 @@ sn_head_kernel(fnssl_btf_view xv, int nt2, int nfc, long long npts, const float*
 // D fragment (lane (point, q): outputs 4 q .. + 3) after bias + tanh is exactly the B operand of the decoder's
 // 16 -> 16 product (K = 16: lane q holds k = 4 q .. + 3), so the decoder is one more group of 4 MFMAs per fine bin.
 // Output order of IPDnet2.py:355-364: element gg*8 + m*2 + a <- dec[a*8 + gg*4 + m]: lane q holds (a, gg) = (q >> 1,
-// q & 1), m = 0..3; it trades registers with lane q ^ 2 (the other a) and stores one float4.
-__device__ __forceinline__ float tanh_fast(float x) {       // 1 - 2 / (e^2x + 1): the LSTM kernels' formulation
-  return __fmaf_rn(-2.0f, __builtin_amdgcn_rcpf(__fadd_rn(__expf(2.0f * x), 1.0f)), 1.0f);
-}
-
+// q & 1), m = 0..3; it trades registers with lane q ^ 2 (the other a) and stores one float4.  tanh_fast:
+// spatialnet_common.h (the head's backward recomputes v with it).
 __global__ void __launch_bounds__(512)
 sn_head_mfma_kernel(fnssl_btf_view xv, int nt2, int nfc, long long npts, const float* __restrict__ wfiP,
                     const float* __restrict__ bfiP, const float* __restrict__ wdT, const float* __restrict__ bd,

@@ -1,7 +1,8 @@
-// What the IPDnet2 forward kernels (spatialnet.hip), the Mamba block's backward (spatialnet_train.hip) and the f-conv /
-// full-band backward (spatialnet_layer_train.hip) share: the shape constants, a point's row load / store and LayerNorm
-// statistics, the matrix-pipe helpers (LDS weight image, MFMA tile product), the index split, the host-side view checks,
-// the forward workspace layout and the ordered reduction of partial sums.
+// What the IPDnet2 forward kernels (spatialnet.hip), the Mamba block's backward (spatialnet_train.hip), the f-conv /
+// full-band backward (spatialnet_layer_train.hip) and the encoder / head backward (spatialnet_net_train.hip) share: the
+// shape constants, a point's row load / store and LayerNorm statistics, the head's tanh, the matrix-pipe helpers (LDS
+// weight image, MFMA tile product), the index split, the host-side view checks, the forward workspace layout and the
+// ordered reduction of partial sums.
 #pragma once
 
 #include <cstdlib>
@@ -60,6 +61,12 @@ __device__ __forceinline__ void ln_stats(const float (&x)[H], float& mean, float
 // x * sigmoid(x) with the reciprocal instruction (1 ulp) instead of the IEEE division sequence (10 operations): the
 // unsqueeze of the full-band branch alone applies it 96 times per point
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
+
+// the head's tanh, forward and backward: 1 - 2 / (e^2x + 1), the LSTM kernels' formulation (+-1 exactly where e^2x
+// overflows or vanishes)
+__device__ __forceinline__ float tanh_fast(float x) {
+  return __fmaf_rn(-2.0f, __builtin_amdgcn_rcpf(__fadd_rn(__expf(2.0f * x), 1.0f)), 1.0f);
+}
 
 // q = p / d, r = p % d (p >= 0, d > 0) in 32-bit arithmetic whenever p fits: a 64-bit division by a run-time value is
 // ~150 VALU instructions, and the three per point of the index split were most of the instruction stream of the

@@ -69,6 +69,8 @@ SYMBOLS = [
     "fnssl_sn_mamba_backward_workspace_bytes", "fnssl_sn_mamba_backward_chunk", "fnssl_sn_mamba_backward",
     "fnssl_sn_fconv_backward_workspace_bytes", "fnssl_sn_fconv_backward",
     "fnssl_sn_full_backward_workspace_bytes", "fnssl_sn_full_backward",
+    "fnssl_sn_encoder_backward_workspace_bytes", "fnssl_sn_encoder_backward",
+    "fnssl_sn_head_backward_workspace_bytes", "fnssl_sn_head_backward",
 ]
 
 
@@ -171,6 +173,11 @@ class SnFconvGrads(C.Structure):
 class SnFullGrads(C.Structure):
     """fnssl_sn_full_grads: one pointer per field of SnFullW, the gradient in the same packed layout."""
     _fields_ = SnFullW._fields_
+
+
+class SnHeadGrads(C.Structure):
+    """fnssl_sn_head_grads: the head's gradients in the packed layouts of its weights (wfiP, bfiP, wdT, bd)."""
+    _fields_ = [(n, C.c_void_p) for n in ("wfiP", "bfiP", "wdT", "bd")]
 
 
 class SnLayer(C.Structure):
@@ -354,6 +361,13 @@ def load():
     lib.fnssl_sn_full_backward.argtypes = [PV, i, i, i, C.POINTER(SnFullW), i, vp, ll, ll, ll, vp, ll, ll, ll,
                                            C.POINTER(SnFullGrads), vp, sz, vp]
     lib.fnssl_sn_head.argtypes = [PV, i, i, i, vp, vp, vp, vp, vp, vp]
+    lib.fnssl_sn_encoder_backward_workspace_bytes.argtypes = [i, i, i, i]
+    lib.fnssl_sn_encoder_backward_workspace_bytes.restype = sz
+    lib.fnssl_sn_encoder_backward.argtypes = [vp, ll, ll, ll, ll, i, i, i, i, vp, vp, ll, ll, ll, vp, vp, vp, ll, ll, ll, ll,
+                                              vp, sz, vp]
+    lib.fnssl_sn_head_backward_workspace_bytes.argtypes = [i, i, i]
+    lib.fnssl_sn_head_backward_workspace_bytes.restype = sz
+    lib.fnssl_sn_head_backward.argtypes = [PV, i, i, i, vp, vp, vp, vp, vp, ll, ll, ll, C.POINTER(SnHeadGrads), vp, sz, vp]
     lib.fnssl_sn_forward_workspace_bytes.argtypes = [i, i, i]
     lib.fnssl_sn_forward_workspace_bytes.restype = sz
     lib.fnssl_sn_state_floats.argtypes = [C.POINTER(SnNet), i, i]

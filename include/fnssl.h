@@ -1092,6 +1092,42 @@ int fnssl_sn_full_backward(const fnssl_btf_view* x, int nb, int nt, int nf, cons
 int fnssl_sn_head(const fnssl_btf_view* x, int nb, int nt2, int nfc, const float* wfiP, const float* bfiP,
                   const float* wdT, const float* bd, float* out, void* stream);
 
+/* ---- encoder and head, backward (additive: FNSSL_ABI_VERSION stays 19) ---------------------------------------------------
+ * With them the network trains end to end: encoder -> layers (the backwards above) -> head.  FNSSL_PRECISION_FP32, whole
+ * sequences from zero state; x is the only saved state of either call.
+ *
+ * fnssl_sn_encoder_backward: the gradients of one fnssl_sn_encoder call with state_in == NULL.
+ *   x, its four strides, nb, cin, nf, nt: the forward's arguments;  dout view [nb, nt, nf, 96] (strides in floats,
+ *   multiples of 4, 16-byte base).
+ *   dwT [cin][5][96] (the packed layout the forward reads), dbias [96]: written, not accumulated.
+ *   dx: NULL = not wanted (the network's features carry no gradient); otherwise x's logical shape under its own four
+ *   strides, written (its own launch; needs wT, the forward's weights).
+ *   cin * 5 + 1 <= 160: dW and dbias are one points-as-K product on the fp32 matrix pipe, dout read once for both (the
+ *   first padded im2col row is the constant 1); wider inputs take a plain kernel.
+ *   workspace: one row of partial sums per workgroup — nothing per point.
+ * fnssl_sn_head_backward: the gradients of one fnssl_sn_head call.
+ *   dout [nb, nt2, 2*nf, 4, 2] contiguous, 16-byte aligned;  dx view [nb, nt2, nfc, 96], written.
+ *   g: the gradients in the packed layouts of the forward's weights (wfiP [16][16][96], bfiP [16][16], wdT [16][16],
+ *   bd [16]); written, not accumulated.  tanh is recomputed with the forward's own formulation (+-1 exactly where e^2u
+ *   overflows or vanishes: dx is exactly 0 there).
+ * Both are bitwise reproducible on a given device: every sum runs in a fixed order (the points of a tile, the tiles of a
+ * workgroup, the workgroups), no float atomics. */
+typedef struct { float *wfiP, *bfiP, *wdT, *bd; } fnssl_sn_head_grads;
+
+size_t fnssl_sn_encoder_backward_workspace_bytes(int nb, int cin, int nf, int nt);
+int fnssl_sn_encoder_backward(const float* x, long long x_sb, long long x_sc, long long x_sf, long long x_st,
+                              int nb, int cin, int nf, int nt, const float* wT,
+                              const float* dout, long long d_sb, long long d_st, long long d_sf,
+                              float* dwT, float* dbias,
+                              float* dx, long long dx_sb, long long dx_sc, long long dx_sf, long long dx_st,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
+size_t fnssl_sn_head_backward_workspace_bytes(int nb, int nt2, int nfc);
+int fnssl_sn_head_backward(const fnssl_btf_view* x, int nb, int nt2, int nfc, const float* wfiP, const float* bfiP,
+                           const float* wdT, const float* dout,
+                           float* dx, long long x_sb, long long x_st, long long x_sf,
+                           const fnssl_sn_head_grads* g, void* workspace, size_t workspace_bytes, void* stream);
+
 #define FNSSL_SN_MAX_LAYERS 16
 typedef struct {
   fnssl_sn_fconv_w fconv1, fconv2;
