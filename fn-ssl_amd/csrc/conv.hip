@@ -371,13 +371,6 @@ int fnssl_conv3x3_pack(const float* w, int cout, int ca, int cb, float* packed) 
   return FNSSL_OK;
 }
 
-static unsigned short conv_to_bf16(float f) {   // round to nearest even
-  unsigned u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-  return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 static int bf16_quads_per_pass(int cout, int ca, int cb) {
   const int npairs = ((ca >> 4) + (cb >> 4) + 1) / 2;
   return 9 * npairs * (conv_nt_tiles(cout) / 4);
@@ -406,7 +399,7 @@ int fnssl_conv3x3_pack_bf16(const float* w, int cout, int ca, int cb, float* pac
               for (int jj = 0; jj < 4; ++jj) {
                 const int blk = 2 * pi + half, oc = 16 * j + (l & 15), ci = 16 * blk + 4 * (l >> 4) + jj;
                 const float v = (blk < nv && oc < cout) ? w[(((size_t)oc * cin + ci) * 3 + df) * 3 + dt] : 0.f;
-                rec[l * 8 + half * 4 + jj] = conv_to_bf16(v);
+                rec[l * 8 + half * 4 + jj] = fnssl::bf16_rne(v);
               }
         }
   if ((size_t)(recf - packed) != total) {

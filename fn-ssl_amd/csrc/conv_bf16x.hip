@@ -395,13 +395,6 @@ pool_t_bf16_kernel(const float4* __restrict__ in, int rows, int nt, int c4, int 
   out[idx] = __builtin_bit_cast(uint2, __builtin_convertvector(m, v4bfx));
 }
 
-unsigned short to_bf16_host(float f) {   // round to nearest even
-  unsigned u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-  return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 int groups_of(int ca, int cb) { return ca / 32 + cb / 16; }
 
 }  // namespace
@@ -438,7 +431,7 @@ int fnssl_conv3x3_pack_bf16x(const float* w, int cout, int ca, int cb, void* pac
             for (int l = 0; l < 64; ++l)
               for (int i = 0; i < 8; ++i) {
                 const int oc = 32 * ct + (l & 31), ci = c0 + 8 * (l >> 5) + i;
-                rec[l * 8 + i] = oc < cout ? to_bf16_host(w[(((size_t)oc * cin + ci) * 3 + df) * 3 + dt]) : 0;
+                rec[l * 8 + i] = oc < cout ? fnssl::bf16_rne(w[(((size_t)oc * cin + ci) * 3 + df) * 3 + dt]) : 0;
               }
           }
   if ((size_t)(reinterpret_cast<char*>(rec) - static_cast<char*>(packed)) != total) {

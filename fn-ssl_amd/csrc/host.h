@@ -3,6 +3,7 @@
 #pragma once
 
 #include <cstdint>
+#include <cstring>
 #include <type_traits>
 
 #include "common.h"
@@ -49,6 +50,21 @@ int with_value(int v, F&& f) {
 template <class F>
 int with_bool(bool b, F&& f) {
   return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// float -> bf16 bits, round to nearest even, and back: what every weight packer uses (lstm_bf16.hip, lstm_bf16w.hip,
+// conv.hip, conv_bf16x.hip).  A NaN keeps its sign and upper payload and becomes quiet (0x40), so it cannot round to an infinity.
+inline unsigned short bf16_rne(float f) {
+  unsigned u;
+  std::memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);   // NaN
+  return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+inline float bf16_to_float(unsigned short h) {
+  const unsigned u = (unsigned)h << 16;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
 }
 
 // one region of a workspace layout, in bytes from the workspace's start

@@ -33,13 +33,6 @@ int launch_bf16(const LstmParams& p, int H, int NW, int nwg, const LaunchCtx& lc
   return kNoStatic;
 }
 
-static unsigned short to_bf16(float f) {   // round to nearest even
-  unsigned u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);   // NaN
-  return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 // Launch plan of the bf16 path: 4 or 8 waves per workgroup, rounds of 8 waves per CU.
 int forward_bf16(LstmParams p, int H, const LaunchCtx& lc) {
   const int ncu = fnssl::device_cus();
@@ -107,7 +100,7 @@ int fnssl_lstm_pack_bf16(const float* w_ih, const float* w_hh, const float* b_ih
                 const int blk = 2 * pi + half;
                 const float v = blk < nblk ? mat[(size_t)(qg * H + 16 * s + (l & 15)) * ld + col0 + 16 * blk + 4 * (l >> 4) + j]
                                            : 0.f;
-                rec[l * 8 + half * 4 + j] = to_bf16(v);
+                rec[l * 8 + half * 4 + j] = fnssl::bf16_rne(v);
               }
         }
     };

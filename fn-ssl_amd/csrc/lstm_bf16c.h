@@ -34,16 +34,17 @@
 //     (kNoCluster: the caller takes the pair-split kernels unguarded).
 //
 // Arithmetic: per 32-row tile the MFMA chain is the one of lstm_bf16p_kernel — ones block (bias), input blocks, recurrent
-// blocks, in that order, into one fp32 accumulator — and the gate math is the same code, so the results are
-// bit-identical to the pair-split kernels'.  The weight stream is fnssl_lstm_pack_bf16w's, unchanged: tile-major, so
-// a member's slice is one contiguous chunk.
+// blocks, in that order, into one fp32 accumulator — and the gate math is the same function (wide_cell, lstm_bf16w.h),
+// so the results are bit-identical to the pair-split kernels'.  The weight stream is fnssl_lstm_pack_bf16w's, unchanged:
+// tile-major, so a member's slice is one contiguous chunk.
 #pragma once
 
 #include "lstm_bf16w.h"
 
 namespace fnssl_lstm {
 
-// Geometry per hidden size (cluster_geom in lstm_kernel.h has the host-side copy used for the workspace):
+// Geometry per hidden size (cluster_members / cluster_parts / cluster_parity_bytes in lstm_kernel.h, one definition for
+// the kernel and for the host's workspace layout):
 //   H = 256 (narrow-band): 8 members x 4 tiles, 2 parts  -> 512 sequences per cluster
 //   H = 128 (full-band):   4 members x 4 tiles, 3 parts  -> 768 sequences per cluster (config 3: 19200 sequences per
 //                          direction = exactly 25 clusters, 50 clusters x 4 CUs in ONE launch; with 2 parts it would be
@@ -118,7 +119,9 @@ __global__ void __launch_bounds__(512) lstm_bf16c_kernel(const LstmParams p, con
   }
   __syncthreads();
 
-  // ---- per-part addressing (buffer descriptors are opaque scalars: named variables, picked by the part index)
+  // ---- per-part addressing (buffer descriptors are opaque scalars: named variables, picked by the part index).  Not a
+  // WideSeq (lstm_bf16w.h) per part: a part has its own presence rule, and a lane's output offset is the one AFTER the
+  // lane-pair swap of the store below (16 hb: 32 contiguous bytes per lane), not its units' (4 hb)
   unsigned vo0[3], vo2[3], voo[3];
   bool valid[3];
   long long off0[3], off2[3], offo[3];
@@ -156,11 +159,7 @@ __global__ void __launch_bounds__(512) lstm_bf16c_kernel(const LstmParams p, con
   auto hx_off = [&](int par, int pt, int s) { return (unsigned)par * cp.parity_stride + (unsigned)(((pt * 8 + w) * NKH + s) * 1024); };
 
   // ---- state
-  v8bfw ones;
-  {
-    const __bf16 o1 = (__bf16)(hb == 0 ? 1.0f : 0.0f);
-    ones = v8bfw{o1, o1, o1, 0, 0, 0, 0, 0};
-  }
+  const v8bfw ones = wide_ones(hb);
   v4f c[NP][TPM];
 #pragma unroll
   for (int pt = 0; pt < NP; ++pt)
@@ -171,7 +170,7 @@ __global__ void __launch_bounds__(512) lstm_bf16c_kernel(const LstmParams p, con
   unsigned tagv = 0;              // tag of member (lane % CL) for the coming part
 
   const char* const lds_a = smem + lane * 16;
-  auto arec = [&](int r, int k) { return __builtin_bit_cast(v8bfw, *reinterpret_cast<const v4f*>(lds_a + (r * KT + k) * 1024)); };
+  auto arec = [&](int r, int k) { return wide_arec(lds_a, r * KT + k); };
 
   // window group T of part pt (T < GX: input blocks 4 T ..; else recurrent blocks 4 (T - GX) ..) into its slots
   auto load_group = [&](auto tc, int pt, unsigned tt, int par) {
@@ -324,19 +323,13 @@ __global__ void __launch_bounds__(512) lstm_bf16c_kernel(const LstmParams p, con
     static_for<TPM>([&](auto r) {
       constexpr int R = decltype(r)::value;
       const v16f& ac = acc[R];
-      v4f cn, hn;
+      v4f hn;
       if constexpr (ABL & 2) {
-        cn = c[PT][R] * 0.5f + v4f{ac[0], ac[5], ac[10], ac[15]};
-        hn = cn * 0.5f + v4f{ac[1], ac[6], ac[11], ac[12]};
+        c[PT][R] = c[PT][R] * 0.5f + v4f{ac[0], ac[5], ac[10], ac[15]};
+        hn = c[PT][R] * 0.5f + v4f{ac[1], ac[6], ac[11], ac[12]};
       } else {
-        const v4f ig = sigmoid4(v4f{ac[0], ac[1], ac[2], ac[3]});
-        const v4f fg = sigmoid4(v4f{ac[4], ac[5], ac[6], ac[7]});
-        const v4f gg = tanh4(v4f{ac[8], ac[9], ac[10], ac[11]});
-        const v4f og = sigmoid4(v4f{ac[12], ac[13], ac[14], ac[15]});
-        cn = cell4(fg, c[PT][R], ig, gg);
-        hn = mul_rn4(og, tanh4(cn));
+        hn = wide_cell(ac, c[PT][R]);
       }
-      c[PT][R] = cn;
       hq[R] = __builtin_convertvector(hn, v4bfw);
     });
     // Output row piece of this member: units 32 m .. 32 m + 31 (64 bytes per sequence).  Lane (n, hb) holds units

@@ -20,8 +20,9 @@
 // transcendentals 6.5 ms, without both 4.45 ms: the floor is the weight stream — every CU pulls the whole 1.06 MB
 // matrix from L2 once per step (84 GB per launch, 97.6 % L2 hits, 2.4 ms at the L2 peak), and with 64 sequences per
 // CU (batch 64) there is nobody to share a pass with.  SQ counters: waves issue-active 62 %, MFMA pipes busy 36 %.
-// Stream layout, operand permutation, bias-as-three-bf16-terms and element types: exactly those of lstm_bf16w.h
+// Stream layout, operand permutation, bias-as-three-bf16-terms and element types: those of lstm_bf16w.h
 // (fnssl_lstm_pack_bf16w); only the ORDER in which tiles are fetched differs, and that is address arithmetic here.
+// The cell update, the MFMA order, the operand loads and the h staging ARE lstm_bf16w.h's (its shared pieces).
 #pragma once
 
 #include "lstm_bf16w.h"
@@ -67,6 +68,8 @@ __global__ void __launch_bounds__(NG * 128) lstm_bf16p_kernel(const LstmParams p
   static_assert(NG * (KPW - 1) - 1 < KQ1 || KPW == 1, "only the last request of a piece may need clamping");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
+  // lane / sequence prologue: WideSeq's text (lstm_bf16w.h) with a role's unit offset, kept as locals — constructed as
+  // a WideSeq, the H = 256 instantiations move one s_waitcnt lgkmcnt between neighbouring counts (profiles/r16/README.md)
   const int lane = threadIdx.x & 63;
   const int n = lane & 31, hb = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -125,11 +128,7 @@ __global__ void __launch_bounds__(NG * 128) lstm_bf16p_kernel(const LstmParams p
 
   // ---- state ---------------------------------------------------------------------------------------------------
   const v4bfw zb4 = v4bfw{0, 0, 0, 0};
-  v8bfw ones;
-  {
-    const __bf16 o1 = (__bf16)(hb == 0 ? 1.0f : 0.0f);
-    ones = v8bfw{o1, o1, o1, 0, 0, 0, 0, 0};
-  }
+  const v8bfw ones = wide_ones(hb);
   v8bfw xb[NKX > 0 ? NKX : 1], xn[NKX > 0 ? NKX : 1];
   v8bfw hop[NKH];
   v4f creg[NTW];
@@ -140,24 +139,12 @@ __global__ void __launch_bounds__(NG * 128) lstm_bf16p_kernel(const LstmParams p
   // the group's h_t staging area [block s][lane][16 B]: global tile 2 s -> bytes 0-7, 2 s + 1 -> 8-15
   char* const hbuf = smem + RING + grp * HBUF + lane * 16;
 
-  auto load_x = [&](auto bc, unsigned tt) -> v8bfw {
+  auto load_x = [&](auto bc, unsigned tt) -> v8bfw {     // input block B (src0's blocks, then src2's) of time tt
     constexpr int B = decltype(bc)::value;
-    if constexpr (B < NB0) {
-      if constexpr (F0) {
-        const v4f a = bld4(rx0, vo0, tt * st0 + 64 * B), c = bld4(rx0, vo0, tt * st0 + 64 * B + 16);
-        return join8(__builtin_convertvector(a, v4bfw), __builtin_convertvector(c, v4bfw));
-      } else {
-        return __builtin_bit_cast(v8bfw, bld4(rx0, vo0, tt * st0 + 32 * B));
-      }
-    } else {
-      constexpr int B2 = B - NB0;
-      if constexpr (F2) {
-        const v4f a = bld4(rx2, vo2, tt * st2 + 64 * B2), c = bld4(rx2, vo2, tt * st2 + 64 * B2 + 16);
-        return join8(__builtin_convertvector(a, v4bfw), __builtin_convertvector(c, v4bfw));
-      } else {
-        return __builtin_bit_cast(v8bfw, bld4(rx2, vo2, tt * st2 + 32 * B2));
-      }
-    }
+    if constexpr (B < NB0)
+      return wide_xblock<F0>(rx0, vo0, tt * st0, B);
+    else
+      return wide_xblock<F2>(rx2, vo2, tt * st2, B - NB0);
   };
   static_for<NKX>([&](auto b) { xb[decltype(b)::value] = load_x(b, rev ? p.nsteps - 1 : 0); });
 
@@ -167,12 +154,7 @@ __global__ void __launch_bounds__(NG * 128) lstm_bf16p_kernel(const LstmParams p
   unsigned pend_off = 0;
   bool pend_live = false;
   auto flush_pending = [&]() {
-    if (pend_live && valid) {
-      if constexpr (OUTF)
-        bst4(pend_f, ro, voo, pend_off);
-      else
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, pend_b), ro, voo, pend_off, 0);
-    }
+    if (pend_live && valid) wide_store_h<OUTF>(ro, voo, pend_f, pend_b, pend_off);
     pend_live = false;
   };
   // One barrier per interval: everything I requested so far has landed (my part of the NEXT interval's pieces);
@@ -188,43 +170,26 @@ __global__ void __launch_bounds__(NG * 128) lstm_bf16p_kernel(const LstmParams p
   };
 
   const char* const lds_rd = smem + lane * 16 + role * (KQ0 * 1024);  // my role's half of a slot
-  auto arec = [&](const char* base, int r) { return __builtin_bit_cast(v8bfw, *reinterpret_cast<const v4f*>(base + r * 1024)); };
   v16f accp = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   auto gate = [&](auto ic_, unsigned oo_t) {   // post-process my tile I (global tile role * NTW + I)
     constexpr int I = decltype(ic_)::value;
-    v4f cn, hn;
+    v4f hn;
     if constexpr (ABL & 1) {
-      cn = creg[I] + v4f{accp[0], accp[5], accp[10], accp[15]};
-      hn = cn * 0.5f + v4f{accp[1], accp[6], accp[11], accp[12]};
+      creg[I] += v4f{accp[0], accp[5], accp[10], accp[15]};
+      hn = creg[I] * 0.5f + v4f{accp[1], accp[6], accp[11], accp[12]};
     } else {
-      const v4f ig = sigmoid4(v4f{accp[0], accp[1], accp[2], accp[3]});
-      const v4f fg = sigmoid4(v4f{accp[4], accp[5], accp[6], accp[7]});
-      const v4f gg = tanh4(v4f{accp[8], accp[9], accp[10], accp[11]});
-      const v4f og = sigmoid4(v4f{accp[12], accp[13], accp[14], accp[15]});
-      cn = cell4(fg, creg[I], ig, gg);
-      hn = mul_rn4(og, tanh4(cn));
+      hn = wide_cell(accp, creg[I]);
     }
-    creg[I] = cn;
     const v4bfw hb4 = __builtin_convertvector(hn, v4bfw);
-    pend_f = hn;
-    pend_b = hb4;
-    const int ta = I;                                     // the stream tile of this static index
-    pend_off = oo_t + (OUTF ? 32 : 16) * ta;
-    pend_live = true;
-    // global tile G = role * NTW + ta -> operand block G / 2, elements 4 (G & 1) .. + 3
-    const int gt = role * NTW + ta;
-    *reinterpret_cast<v4bfw*>(hbuf + (gt >> 1) * 1024 + 8 * (gt & 1)) = hb4;
-  };
-  auto reload_h = [&]() {
-#pragma unroll
-    for (int i = 0; i < NKH; ++i) hop[i] = __builtin_bit_cast(v8bfw, *reinterpret_cast<const v4f*>(hbuf + i * 1024));
+    pend_f = hn, pend_b = hb4, pend_off = oo_t + (OUTF ? 32 : 16) * I, pend_live = true;
+    stage_h(hbuf, role * NTW + I, hb4);                   // (the group's staging area holds global tiles)
   };
 
   // the first interval: wait, publish, prime the A pipeline
   piece_barrier(ic<0>{});
   v8bfw apipe[AD];
 #pragma unroll
-  for (int i = 0; i < AD; ++i) apipe[i] = arec(lds_rd, i);
+  for (int i = 0; i < AD; ++i) apipe[i] = wide_arec(lds_rd, i);
 
   unsigned oo_prev = 0;
   for (int step = 0; step < p.nsteps; ++step) {
@@ -242,7 +207,7 @@ __global__ void __launch_bounds__(NG * 128) lstm_bf16p_kernel(const LstmParams p
           piece_barrier(ic<0>{});
       }
       if constexpr (I == 0 && !LATE) {
-        if (step > 0) reload_h();
+        if (step > 0) reload_h<NKH>(hbuf, hop);
       }
       // The next step's input blocks are requested in ONE burst at the start of the step: vector loads return in
       // order, so a load that has to come from HBM holds back the weight requests queued behind it — once per step
@@ -275,7 +240,7 @@ __global__ void __launch_bounds__(NG * 128) lstm_bf16p_kernel(const LstmParams p
             piece_barrier(ic<0>{});
         }
         if constexpr (I == 0 && LATE && K == 1 + NKX) {
-          if (step > 0) reload_h();
+          if (step > 0) reload_h<NKH>(hbuf, hop);
         }
         const v8bfw a = apipe[R];
         // record K + AD: piece index (0..3 this tile, 4..5 next tile) and offset inside the piece
@@ -283,16 +248,11 @@ __global__ void __launch_bounds__(NG * 128) lstm_bf16p_kernel(const LstmParams p
         constexpr int KM = KN % KT;
         constexpr int PC = (KN / KT) * 4 + (KM >= KP ? 2 : 0) + ((KM % KP) >= KQ0 ? 1 : 0);
         constexpr int OFF = (KM % KP) >= KQ0 ? (KM % KP) - KQ0 : (KM % KP);
-        apipe[R] = arec(cbs[PC], OFF);
-        if constexpr (ABL & 4) {
+        apipe[R] = wide_arec(cbs[PC], OFF);
+        if constexpr (ABL & 4)
           acc[K % 16] += (float)a[0];
-        } else if constexpr (K == 0) {
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, ones, acc, 0, 0, 0);          // + bias (exact)
-        } else if constexpr (K <= NKX) {
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, xb[K - 1 < NKX ? K - 1 : 0], acc, 0, 0, 0);
-        } else {
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, hop[K - 1 - NKX], acc, 0, 0, 0);
-        }
+        else
+          acc = wide_mfma<K, NKX>(a, ones, xb, hop, acc);
       });
       accp = acc;
     });

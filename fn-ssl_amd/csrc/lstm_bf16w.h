@@ -44,15 +44,6 @@ constexpr int kW_F0 = 1, kW_F2 = 2, kW_OUTF = 4;   // bit set = that tensor is f
 
 __host__ __device__ inline int bf16w_records_per_tile(int c0, int c2, int H) { return 1 + (c0 >> 4) + (c2 >> 4) + (H >> 4); }
 
-__device__ __forceinline__ void dma16(rsrc_t r, unsigned voff, unsigned soff, unsigned lds) {
-  // one wave-instruction = 1 KiB: lane l's 16 bytes land at lds + 16 l.  M0 is written in the same statement that
-  // reads it (the compiler does not preserve it); hipcc does not count this load: see the vmcnt(N) below.
-  // (readfirstlane: the operands are wave-uniform by construction; this makes the compiler keep them in SGPRs)
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(voff), "s"(r),
-               "s"(__builtin_amdgcn_readfirstlane(lds)), "s"(__builtin_amdgcn_readfirstlane(soff))
-               : "memory");
-}
-
 // split_addr for a tensor of ES-byte elements: wave-uniform base (the wave's minimum) + per-lane byte offset
 template <int ES>
 __device__ __forceinline__ rsrc_t split_addr_e(const void* base, long long off_elems, unsigned& voff) {
@@ -69,8 +60,11 @@ __device__ __forceinline__ rsrc_t split_addr_e(const void* base, long long off_e
   return make_rsrc(reinterpret_cast<const char*>(base) + mnu * ES);
 }
 
-// The same with a compile-time byte offset IMM added to both the stream offset and the LDS destination inside the
-// statement (two SALU adds with a literal instead of four instructions of address arithmetic per record).
+// LDS-DMA, one wave-instruction = 1 KiB: lane l's 16 bytes of the stream at soff + IMM land at lds + IMM + 16 l.  M0 is
+// written in the same statement that reads it (the compiler does not preserve it); hipcc does not count this load: hence
+// the hand-placed vmcnt(N) of the rings.  (readfirstlane: the operands are wave-uniform by construction; this makes the
+// compiler keep them in SGPRs.)  The compile-time byte offset IMM is added to both the stream offset and the LDS
+// destination inside the statement (two SALU adds with a literal instead of four instructions of address arithmetic).
 template <int IMM>
 __device__ __forceinline__ void dma16_imm(rsrc_t r, unsigned voff, unsigned soff, unsigned lds) {
   unsigned tmp;
@@ -81,15 +75,129 @@ __device__ __forceinline__ void dma16_imm(rsrc_t r, unsigned voff, unsigned soff
                : "memory", "scc");   // s_add_u32 writes SCC: without the clobber the compiler keeps a loop condition in it
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vm_barrier() {
-  // all but my N youngest vector-memory operations have completed (in order), then the workgroup barrier: every
-  // wave's share of the tile that is about to be consumed has landed, and everybody is done with the slot that the
-  // next DMA overwrites
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
+__device__ __forceinline__ v8bfw join8(v4bfw lo, v4bfw hi) { return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7); }
+
+// ---- pieces shared by the wide kernels (this file, lstm_bf16p.h, lstm_bf16c.h): what a wave does for its 32 sequences
+//   wide_ones, wide_cell, wide_arec     bias operand; D fragment -> c_t, h_t; one A record from LDS          all three
+//   wide_xblock, wide_store_h           one input block as a B operand; a lane's four units of h_t           bf16w, bf16p
+//   wide_mfma, stage_h, reload_h        the MFMA of K-step K; h_t through the lane-private LDS area           bf16w, bf16p
+//   WideSeq                             lane / sequence prologue with the tail rule                          bf16w
+// lstm_bf16p_kernel keeps its own prologue: through WideSeq its H = 256 instantiations move one s_waitcnt lgkmcnt between
+// neighbouring counts, and no smaller private piece puts it back (profiles/r16/README.md).  lstm_bf16c.h
+// keeps its own: three parts per wave, each with a presence rule, outputs addressed after its lane-pair swap.  The deferred
+// h store stays four variables in each kernel (as a struct, lstm_bf16w_kernel's NL = 0 instantiations move three such
+// waits).  The rings, their barriers and the vmcnt accounting are different protocols and stay where they are.
+// Everything is __forceinline__ and indexed at compile time; the three families are bit-identical to each other
+// (tests/test_gpu_parity.py) because every one of them goes through wide_cell and the same MFMA order.
+
+// input block b (16 channels: a lane's 8 are 16 b + 8 hb + i) of the row at byte offset `row` -> B operand
+template <bool FP32>
+__device__ __forceinline__ v8bfw wide_xblock(rsrc_t rx, unsigned vo, unsigned row, int b) {
+  if constexpr (FP32) {
+    const v4f a = bld4(rx, vo, row + 64 * b), c = bld4(rx, vo, row + 64 * b + 16);
+    return join8(__builtin_convertvector(a, v4bfw), __builtin_convertvector(c, v4bfw));
+  } else {
+    return __builtin_bit_cast(v8bfw, bld4(rx, vo, row + 32 * b));
+  }
+}
+// the lane's four units of one tile, fp32 or bf16, to byte offset `off` of its output row
+template <bool FP32>
+__device__ __forceinline__ void wide_store_h(rsrc_t ro, unsigned voo, const v4f& hn, v4bfw hb4, unsigned off) {
+  if constexpr (FP32)
+    bst4(hn, ro, voo, off);
+  else
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, hb4), ro, voo, off, 0);
 }
 
-__device__ __forceinline__ v8bfw join8(v4bfw lo, v4bfw hi) { return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7); }
+// Lane (n, hb) of a wave works on sequence n of 32-sequence group `task`: channels 8 hb + i of an input block, units
+// 4 hb + j of a gate-row tile.  Tail rule, in ONE place: a lane past the last sequence computes the last sequence again
+// (q clamped), a wave past the last group likewise; only `valid` lanes store h.
+template <int H, int NB0, int NB2, int FLAGS>
+struct WideSeq {
+  static constexpr bool F0 = FLAGS & kW_F0, F2 = FLAGS & kW_F2, OUTF = FLAGS & kW_OUTF;
+  static constexpr int E0 = F0 ? 4 : 2, E2 = F2 ? 4 : 2, EO = OUTF ? 4 : 2;   // element sizes by template flag
+  static constexpr int kTileBytes = 8 * EO;                                  // one tile's 8 units in an output row
+  int n, hb;
+  bool valid, rev;
+  unsigned vo0 = 0, vo2 = 0, voo = 0, vlane;   // per-lane byte offsets into the descriptors below
+  rsrc_t rx0, rx2, ro, rw;                     // input, concatenated input, h, weight stream
+  unsigned st0, st2, sto;                      // their step strides in bytes
+
+  // unit0: the first hidden unit of the wave's tiles
+  __device__ __forceinline__ WideSeq(const LstmParams& p, int lane, int dir, int task, int unit0) {
+    n = lane & 31, hb = lane >> 5;
+    int q = task * 32 + n;
+    valid = q < p.nseq && task < p.task1;
+    if (q >= p.nseq) q = p.nseq - 1;
+    const long long qo = q / p.q_inner, qi = q - qo * p.q_inner;
+    rx0 = make_rsrc(p.out), rx2 = make_rsrc(p.out);
+    if constexpr (NB0 > 0) rx0 = split_addr_e<E0>(p.src0.p, qo * p.src0.so + qi * p.src0.si + 8 * hb, vo0);
+    if constexpr (NB2 > 0) rx2 = split_addr_e<E2>(p.src2.p, qo * p.src2.so + qi * p.src2.si + 8 * hb, vo2);
+    ro = split_addr_e<EO>(p.out, qo * p.out_so + qi * p.out_si + dir * H + unit0 + 4 * hb, voo);
+    st0 = (unsigned)(p.src0.st * E0), st2 = (unsigned)(p.src2.st * E2), sto = (unsigned)(p.out_st * EO);
+    rw = make_rsrc(p.wpack[dir]);
+    vlane = lane * 16;
+    rev = dir == 1;
+  }
+  // input block B (src0's blocks, then src2's) of time tt
+  template <int B>
+  __device__ __forceinline__ v8bfw load_x(ic<B>, unsigned tt) const {
+    if constexpr (B < NB0)
+      return wide_xblock<F0>(rx0, vo0, tt * st0, B);
+    else
+      return wide_xblock<F2>(rx2, vo2, tt * st2, B - NB0);
+  }
+  // h_t of one tile to byte offset `off` of the output row, if there is one (`live`) and the lane has a sequence
+  __device__ __forceinline__ void store_h(const v4f& hn, v4bfw hb4, unsigned off, bool live = true) const {
+    if (live && valid) wide_store_h<OUTF>(ro, voo, hn, hb4, off);
+  }
+};
+
+// B operand of the ones block: k-slots (hb 0, i 0..2) = 1
+__device__ __forceinline__ v8bfw wide_ones(int hb) {
+  const __bf16 o1 = (__bf16)(hb == 0 ? 1.0f : 0.0f);
+  return v8bfw{o1, o1, o1, 0, 0, 0, 0, 0};
+}
+
+// Gates of units 8 T + 4 hb + j (j = 0..3) of the lane's sequence: D register 4 * gate + j of tile T's accumulator.
+// c: the cell state of those units, updated; returns h_t (fp32).  The ABLATE arms stay at the call sites.
+__device__ __forceinline__ v4f wide_cell(const v16f& acc, v4f& c) {
+  const v4f ig = sigmoid4(v4f{acc[0], acc[1], acc[2], acc[3]});
+  const v4f fg = sigmoid4(v4f{acc[4], acc[5], acc[6], acc[7]});
+  const v4f gg = tanh4(v4f{acc[8], acc[9], acc[10], acc[11]});
+  const v4f og = sigmoid4(v4f{acc[12], acc[13], acc[14], acc[15]});
+  const v4f cn = cell4(fg, c, ig, gg);
+  const v4f hn = mul_rn4(og, tanh4(cn));
+  c = cn;
+  return hn;
+}
+
+// record r (1 KiB: 16 bytes per lane) behind `base`, this lane's 16 bytes of a record in LDS
+__device__ __forceinline__ v8bfw wide_arec(const char* base, int r) {
+  return __builtin_bit_cast(v8bfw, *reinterpret_cast<const v4f*>(base + r * 1024));
+}
+
+// the MFMA of K-step K of a tile: K = 0 the ones block (+ bias, exact), K <= NKX input block K - 1, then the recurrent blocks
+template <int K, int NKX>
+__device__ __forceinline__ v16f wide_mfma(v8bfw a, v8bfw ones, const v8bfw* xb, const v8bfw* hop, v16f acc) {
+  if constexpr (K == 0)
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, ones, acc, 0, 0, 0);
+  else if constexpr (K <= NKX)
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, xb[K - 1], acc, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, hop[K - 1 - NKX], acc, 0, 0, 0);
+}
+
+// h_t travels to the next step through a lane-private LDS area, hbuf = [block s][lane][16 B]: the lane's four units of
+// tile G are elements 4 (G & 1) .. + 3 of operand block G / 2; reload_h makes the area the recurrent operands
+__device__ __forceinline__ void stage_h(char* hbuf, int G, v4bfw hb4) {
+  *reinterpret_cast<v4bfw*>(hbuf + (G >> 1) * 1024 + 8 * (G & 1)) = hb4;
+}
+template <int NKH>
+__device__ __forceinline__ void reload_h(const char* hbuf, v8bfw* hop) {
+#pragma unroll
+  for (int i = 0; i < NKH; ++i) hop[i] = wide_arec(hbuf, i);
+}
 
 // NW consumer waves (32 sequences each) + NL loader waves.  NL = 0: the consumers fetch the stream themselves.  NL > 0
 // (launches that leave SIMDs idle anyway — IPDnet's narrow-band layers at batch 64 are 2 groups per CU): the DMA issue
@@ -104,8 +212,7 @@ __global__ void __launch_bounds__((NW + NL) * 64) lstm_bf16w_kernel(const LstmPa
   constexpr int KPW = (KP + NF - 1) / NF;                 // records each fetching wave requests per piece
   constexpr int NPS = 2 * NT;                             // pieces per step
   static_assert(KT % 2 == 0, "tiles are fetched in two pieces");
-  constexpr bool F0 = FLAGS & kW_F0, F2 = FLAGS & kW_F2, OUTF = FLAGS & kW_OUTF;
-  constexpr int AD = 4;                                   // A-operand reads in flight ahead of the MFMA that uses them
+  constexpr int AD = 4;                                  // A-operand reads in flight ahead of the MFMA that uses them
   constexpr int RING = NSLOT * KT * 1024, HBUF = NKH * 1024;   // bytes: weight ring; one wave's h_t staging area
   static_assert(NSLOT == 3, "protocol below: consuming T, T + 1 landed, T + 2 in flight");
   static_assert(RING + NW * HBUF <= 160 * 1024, "ring + h staging do not fit the LDS");
@@ -113,27 +220,10 @@ __global__ void __launch_bounds__((NW + NL) * 64) lstm_bf16w_kernel(const LstmPa
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int lane = threadIdx.x & 63;
-  const int n = lane & 31, hb = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int dir = blockIdx.x / p.wgs_per_dir;
   const int wg = blockIdx.x - dir * p.wgs_per_dir;
-  const int task = p.task0 + wg * NW + w;                 // 32-sequence group
-  int q = task * 32 + n;
-  const bool valid = q < p.nseq && task < p.task1;
-  if (q >= p.nseq) q = p.nseq - 1;
-  const long long qo = q / p.q_inner, qi = q - qo * p.q_inner;
-
-  // activations: element sizes by template flag; a lane reads 8 consecutive channels (k = 8 hb + i) per block
-  constexpr int E0 = F0 ? 4 : 2, E2 = F2 ? 4 : 2, EO = OUTF ? 4 : 2;
-  unsigned vo0 = 0, vo2 = 0, voo = 0;
-  rsrc_t rx0 = make_rsrc(p.out), rx2 = make_rsrc(p.out);
-  if constexpr (NB0 > 0) rx0 = split_addr_e<E0>(p.src0.p, qo * p.src0.so + qi * p.src0.si + 8 * hb, vo0);
-  if constexpr (NB2 > 0) rx2 = split_addr_e<E2>(p.src2.p, qo * p.src2.so + qi * p.src2.si + 8 * hb, vo2);
-  const rsrc_t ro = split_addr_e<EO>(p.out, qo * p.out_so + qi * p.out_si + dir * H + 4 * hb, voo);
-  const unsigned st0 = (unsigned)(p.src0.st * E0), st2 = (unsigned)(p.src2.st * E2), sto = (unsigned)(p.out_st * EO);
-  const rsrc_t rw = make_rsrc(p.wpack[dir]);
-  const unsigned vlane = lane * 16;
-  const bool rev = dir == 1;
+  const WideSeq<H, NB0, NB2, FLAGS> q(p, lane, dir, p.task0 + wg * NW + w, 0);
   const unsigned lds0 = (unsigned)(size_t)smem;            // LDS byte address of the ring
 
   // ---- weight ring: NSLOT tiles = 6 half-tile pieces of KP KiB, one barrier per piece.  At the barrier that opens
@@ -147,9 +237,9 @@ __global__ void __launch_bounds__((NW + NL) * 64) lstm_bf16w_kernel(const LstmPa
   auto fetch_piece = [&](int piece_in_step, int slot) {   // my share: records fw, fw + NF, ... of the piece
     const unsigned sb = (unsigned)(piece_in_step * KP) * 1024u, lb = lds0 + (unsigned)(slot * KP) * 1024u;
     static_for<KPW - 1>([&](auto mc) {
-      dma16_imm<decltype(mc)::value * NF * 1024>(rw, vlane, sb + (unsigned)fw * 1024u, lb + (unsigned)fw * 1024u);
+      dma16_imm<decltype(mc)::value * NF * 1024>(q.rw, q.vlane, sb + (unsigned)fw * 1024u, lb + (unsigned)fw * 1024u);
     });
-    dma16_imm<0>(rw, vlane, sb + (unsigned)rlast * 1024u, lb + (unsigned)rlast * 1024u);
+    dma16_imm<0>(q.rw, q.vlane, sb + (unsigned)rlast * 1024u, lb + (unsigned)rlast * 1024u);
   };
   int ft = 0, fslot = 0;                                   // next piece to request (position inside the step), its slot
   auto fetch_next = [&]() {
@@ -180,11 +270,7 @@ __global__ void __launch_bounds__((NW + NL) * 64) lstm_bf16w_kernel(const LstmPa
 
   // ---- state ---------------------------------------------------------------------------------------------------
   const v4bfw zb4 = v4bfw{0, 0, 0, 0};
-  v8bfw ones;                                              // B operand of the ones block: k-slots (hb 0, i 0..2) = 1
-  {
-    const __bf16 o1 = (__bf16)(hb == 0 ? 1.0f : 0.0f);
-    ones = v8bfw{o1, o1, o1, 0, 0, 0, 0, 0};
-  }
+  const v8bfw ones = wide_ones(q.hb);
   v8bfw xb[NKX > 0 ? NKX : 1], xn[NKX > 0 ? NKX : 1];     // this step's / the next step's input operands
   v8bfw hop[NKH];                                          // h_{t-1} as B operands; h_t is staged in LDS (hbuf)
   v4f creg[NT];
@@ -194,30 +280,9 @@ __global__ void __launch_bounds__((NW + NL) * 64) lstm_bf16w_kernel(const LstmPa
   for (int i = 0; i < NT; ++i) creg[i] = v4f{0.f, 0.f, 0.f, 0.f};
   char* const hbuf = smem + RING + w * HBUF + lane * 16;   // [block s][lane][16 B]: tile 2s -> bytes 0-7, 2s+1 -> 8-15
 
-  // input block b of time tt -> B operand (8 channels 16 b + 8 hb + i of the lane's sequence)
-  auto load_x = [&](auto bc, unsigned tt) -> v8bfw {
-    constexpr int B = decltype(bc)::value;
-    if constexpr (B < NB0) {
-      if constexpr (F0) {
-        const v4f a = bld4(rx0, vo0, tt * st0 + 64 * B), c = bld4(rx0, vo0, tt * st0 + 64 * B + 16);
-        return join8(__builtin_convertvector(a, v4bfw), __builtin_convertvector(c, v4bfw));
-      } else {
-        return __builtin_bit_cast(v8bfw, bld4(rx0, vo0, tt * st0 + 32 * B));
-      }
-    } else {
-      constexpr int B2 = B - NB0;
-      if constexpr (F2) {
-        const v4f a = bld4(rx2, vo2, tt * st2 + 64 * B2), c = bld4(rx2, vo2, tt * st2 + 64 * B2 + 16);
-        return join8(__builtin_convertvector(a, v4bfw), __builtin_convertvector(c, v4bfw));
-      } else {
-        return __builtin_bit_cast(v8bfw, bld4(rx2, vo2, tt * st2 + 32 * B2));
-      }
-    }
-  };
-  static_for<NKX>([&](auto b) { xb[decltype(b)::value] = load_x(b, rev ? p.nsteps - 1 : 0); });
+  static_for<NKX>([&](auto b) { xb[decltype(b)::value] = q.load_x(b, q.rev ? p.nsteps - 1 : 0); });
 
   const char* const lds_rd = smem + lane * 16;
-  auto arec = [&](const char* base, int r) { return __builtin_bit_cast(v8bfw, *reinterpret_cast<const v4f*>(base + r * 1024)); };
   // With loader waves the consumers never wait on vector memory at a tile boundary (their x loads and h stores are
   // waited for where the compiler needs them); without, a wave also certifies its own DMA share.
   auto piece_barrier = [&]() {
@@ -233,7 +298,7 @@ __global__ void __launch_bounds__((NW + NL) * 64) lstm_bf16w_kernel(const LstmPa
   piece_barrier();
   v8bfw apipe[AD];
 #pragma unroll
-  for (int i = 0; i < AD; ++i) apipe[i] = arec(lds_rd, i);
+  for (int i = 0; i < AD; ++i) apipe[i] = wide_arec(lds_rd, i);
 
   // Software pipeline over tiles: the gate math of tile T - 1 (VALU: 20 exp, 20 rcp, ~70 others per lane) is issued
   // in the shadow of tile T's MFMAs — its result is only needed by the NEXT step — so the matrix pipe does not idle
@@ -251,63 +316,37 @@ __global__ void __launch_bounds__((NW + NL) * 64) lstm_bf16w_kernel(const LstmPa
       creg[TP] += v4f{accp[0], accp[5], accp[10], accp[15]};
       return;
     }
-    // gates of units 8 TP + 4 hb + j (j = 0..3) of the lane's sequence: D register 4 * gate + j
-    const v4f ig = sigmoid4(v4f{accp[0], accp[1], accp[2], accp[3]});
-    const v4f fg = sigmoid4(v4f{accp[4], accp[5], accp[6], accp[7]});
-    const v4f gg = tanh4(v4f{accp[8], accp[9], accp[10], accp[11]});
-    const v4f og = sigmoid4(v4f{accp[12], accp[13], accp[14], accp[15]});
-    const v4f cn = cell4(fg, creg[TP], ig, gg);
-    const v4f hn = mul_rn4(og, tanh4(cn));
-    creg[TP] = cn;
+    const v4f hn = wide_cell(accp, creg[TP]);
     const v4bfw hb4 = __builtin_convertvector(hn, v4bfw);
     if constexpr (ABL & 16) {
       creg[TP].x += (float)hb4[0];
       return;
     }
-    if constexpr (NL > 0) {
-      if (valid) {
-        if constexpr (OUTF)
-          bst4(hn, ro, voo, oo_t + 32 * TP);
-        else
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, hb4), ro, voo, oo_t + 16 * TP, 0);
-      }
-    } else {
-      pend_f = hn;
-      pend_b = hb4;
-      pend_off = oo_t + (OUTF ? 32 : 16) * TP;
-      pend_live = true;
-    }
-    // stage h_t for the next step: operand block TP / 2, elements 4 (TP & 1) .. + 3
-    *reinterpret_cast<v4bfw*>(hbuf + (TP / 2) * 1024 + 8 * (TP & 1)) = hb4;
+    if constexpr (NL > 0)
+      q.store_h(hn, hb4, oo_t + q.kTileBytes * TP);
+    else
+      pend_f = hn, pend_b = hb4, pend_off = oo_t + q.kTileBytes * TP, pend_live = true;
+    stage_h(hbuf, TP, hb4);                                 // for the next step
   };
   auto flush_pending = [&]() {
     if constexpr (NL == 0) {
-      if (pend_live && valid) {
-        if constexpr (OUTF)
-          bst4(pend_f, ro, voo, pend_off);
-        else
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, pend_b), ro, voo, pend_off, 0);
-      }
+      q.store_h(pend_f, pend_b, pend_off, pend_live);
       pend_live = false;
     }
-  };
-  auto reload_h = [&]() {   // h_t becomes the recurrent operand (only this wave wrote / reads its staging area)
-#pragma unroll
-    for (int i = 0; i < NKH; ++i) hop[i] = __builtin_bit_cast(v8bfw, *reinterpret_cast<const v4f*>(hbuf + i * 1024));
   };
 
   unsigned oo_prev = 0;
   for (int step = 0; step < p.nsteps; ++step) {
-    const unsigned tt = rev ? p.nsteps - 1 - step : step;
-    const unsigned ttn = step + 1 < p.nsteps ? (rev ? tt - 1 : tt + 1) : tt;
-    const unsigned oo = tt * sto;
+    const unsigned tt = q.rev ? p.nsteps - 1 - step : step;
+    const unsigned ttn = step + 1 < p.nsteps ? (q.rev ? tt - 1 : tt + 1) : tt;
+    const unsigned oo = tt * q.sto;
 
     static_for<NT>([&](auto tc) {
       constexpr int T = decltype(tc)::value;
       if (T > 0 || step > 0) piece_barrier();               // see the protocol above
       flush_pending();
       // the next step's input blocks trickle in, one block per tile
-      if constexpr (T < NKX && !(ABL & 32)) xn[T] = load_x(ic<T>{}, ttn);
+      if constexpr (T < NKX && !(ABL & 32)) xn[T] = q.load_x(ic<T>{}, ttn);
 
       const char* cb = lds_rd + cslot * (KT * 1024);
       cslot = cslot + 1 == NSLOT ? 0 : cslot + 1;
@@ -329,25 +368,20 @@ __global__ void __launch_bounds__((NW + NL) * 64) lstm_bf16w_kernel(const LstmPa
         constexpr int R = (T * KT + K) % AD;
         if constexpr (K == KP) piece_barrier();             // second half of the tile
         if constexpr (T == 0 && K == 1 + NKX) {
-          if (step > 0) reload_h();                         // the last tile's h has just been staged
+          if (step > 0) reload_h<NKH>(hbuf, hop);           // the last tile's h has just been staged (by this wave alone)
         }
         if constexpr (!(ABL & 4)) {
           const v8bfw a = apipe[R];
-          if constexpr (!(ABL & 8)) apipe[R] = (K + AD < KT) ? arec(cb, K + AD) : arec(nb_, K + AD - KT);
-          if constexpr (K == 0)
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, ones, acc, 0, 0, 0);          // + bias (exact)
-          else if constexpr (K <= NKX)
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, xb[K - 1 < NKX ? K - 1 : 0], acc, 0, 0, 0);
-          else
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, hop[K - 1 - NKX], acc, 0, 0, 0);
+          if constexpr (!(ABL & 8)) apipe[R] = (K + AD < KT) ? wide_arec(cb, K + AD) : wide_arec(nb_, K + AD - KT);
+          acc = wide_mfma<K, NKX>(a, ones, xb, hop, acc);
         } else {
           acc[K % 16] += (float)apipe[R][0];
-          apipe[R] = (K + AD < KT) ? arec(cb, K + AD) : arec(nb_, K + AD - KT);
+          apipe[R] = (K + AD < KT) ? wide_arec(cb, K + AD) : wide_arec(nb_, K + AD - KT);
         }
       });
       accp = acc;
     });
-    static_for<(NKX > NT ? NKX - NT : 0)>([&](auto e) { xn[NT + decltype(e)::value] = load_x(ic<NT + decltype(e)::value>{}, ttn); });
+    static_for<(NKX > NT ? NKX - NT : 0)>([&](auto e) { xn[NT + decltype(e)::value] = q.load_x(ic<NT + decltype(e)::value>{}, ttn); });
 #pragma unroll
     for (int i = 0; i < NKX; ++i) xb[i] = xn[i];
     oo_prev = oo;

@@ -100,19 +100,6 @@ int forward_bf16w(LstmParams p, int H, int flags, size_t cluster_bytes, const La
       [&](const unsigned* guard) { return forward_bf16w_plain(p, H, flags, guard, lc, guard ? nullptr : family); });
 }
 
-static unsigned short to_bf16w(float f) {   // round to nearest even
-  unsigned u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);   // NaN
-  return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-static float from_bf16w(unsigned short h) {
-  const unsigned u = (unsigned)h << 16;
-  float f;
-  std::memcpy(&f, &u, 4);
-  return f;
-}
-
 }  // namespace fnssl_lstm
 
 using namespace fnssl_lstm;
@@ -137,10 +124,10 @@ int fnssl_lstm_pack_bf16w(const float* w_ih, const float* w_hh, const float* b_i
     // record 0: bias = hi + mid + lo in k-slots (hb 0, i 0..2)
     for (int l = 0; l < 32; ++l) {
       const float b = b_ih[row_of(l)] + b_hh[row_of(l)];
-      const unsigned short hi = to_bf16w(b);
-      const float r1 = b - from_bf16w(hi);
-      const unsigned short mid = to_bf16w(r1);
-      const unsigned short lo = to_bf16w(r1 - from_bf16w(mid));
+      const unsigned short hi = fnssl::bf16_rne(b);
+      const float r1 = b - fnssl::bf16_to_float(hi);
+      const unsigned short mid = fnssl::bf16_rne(r1);
+      const unsigned short lo = fnssl::bf16_rne(r1 - fnssl::bf16_to_float(mid));
       rec[l * 8 + 0] = hi;
       rec[l * 8 + 1] = mid;
       rec[l * 8 + 2] = lo;
@@ -148,12 +135,12 @@ int fnssl_lstm_pack_bf16w(const float* w_ih, const float* w_hh, const float* b_i
     rec += 512;
     for (int b = 0; b < NKX; ++b, rec += 512)
       for (int l = 0; l < 64; ++l)
-        for (int i = 0; i < 8; ++i) rec[l * 8 + i] = to_bf16w(w_ih[(size_t)row_of(l) * I + 16 * b + 8 * (l >> 5) + i]);
+        for (int i = 0; i < 8; ++i) rec[l * 8 + i] = fnssl::bf16_rne(w_ih[(size_t)row_of(l) * I + 16 * b + 8 * (l >> 5) + i]);
     for (int s = 0; s < NKH; ++s, rec += 512)
       for (int l = 0; l < 64; ++l)
         for (int i = 0; i < 8; ++i) {
           const int unit = 16 * s + 8 * (i >> 2) + 4 * (l >> 5) + (i & 3);
-          rec[l * 8 + i] = to_bf16w(w_hh[(size_t)row_of(l) * H + unit]);
+          rec[l * 8 + i] = fnssl::bf16_rne(w_hh[(size_t)row_of(l) * H + unit]);
         }
   }
   if ((size_t)(reinterpret_cast<float*>(rec) - packed) != total) {
