@@ -14,7 +14,9 @@ Against the reference's dataflow nothing is concatenated or permuted in memory: 
 (:34, :38) are a second operand segment of the consuming LSTM / conv kernel, the permutes are strides.
 ``nn.LSTM`` / ``nn.Conv2d`` sub-modules only hold parameters.  ROCm tensors only.  ``IPDnet.forward`` also trains:
 in ``train()`` mode, at ``hidden_size=256`` in fp32, it returns a tensor with a ``grad_fn`` (fnssl/ipdnet_train.py);
-every other entry, and every other configuration in train mode, is forward-only (``eval()``).  fp32 by default; after ``net.bfloat16()`` (BASELINE config 3: bf16 weights, fp32 accumulate) the LSTM
+``IPDnet.forward_train`` is the same train-mode forward for hidden 256 AND the default hidden 128 (full-band H = 64),
+the opt-in the default model trains through.  Every other entry, and ``forward`` of every other configuration in train
+mode, is forward-only (``eval()``).  fp32 by default; after ``net.bfloat16()`` (BASELINE config 3: bf16 weights, fp32 accumulate) the LSTM
 layers run on bf16 MFMAs — weights and the [x | h] operands rounded to bf16, gates / cell state / every
 tensor in HBM fp32 — and the conv head uses the bf16-rounded weights; inputs of either dtype are accepted and
 the output comes back in the input's dtype.
@@ -356,6 +358,23 @@ class IPDnet(nn.Module):
             c = c.reshape(nb // nseg, nt2 * nseg, 2, nf * 2, -1).permute(0, 1, 3, 4, 2)
             return c[:, :ou_frame, :, :, :].to(in_dtype)
         return c.reshape(nb, nt2, 2, nf * 2, -1).permute(0, 1, 3, 4, 2).to(in_dtype)
+
+    @ops.on_device
+    def forward_train(self, x, offline_inference=False):
+        """The train-mode forward with a ``grad_fn`` (fnssl/ipdnet_train.py) for every trainable module — fp32,
+        ``hidden_size`` 128 (the reference's default: full-band BiLSTM H = 64) or 256.  ``forward`` takes this route by
+        itself only at hidden 256; at the default width it keeps raising the forward-only error in ``train()`` mode, and
+        this entry is the opt-in.  Same dropout bases / counters (``dropout_seed``, ``dropout_calls``,
+        ``force_dropout_base``) and ``utt_offset`` rules; at hidden 256 the same bits as ``forward``.  x
+        [nb, 2*nch, nf, nt >= 12] -> [nb, nt//12, 2*nf, nch-1, max_track]."""
+        if not self.training:
+            raise RuntimeError("IPDnet.forward_train: the module is in eval() mode; call .train() first (forward is the "
+                               "inference entry)")
+        if not ipdnet_train.trainable(self, offline_inference):
+            raise RuntimeError("IPDnet.forward_train: no training kernels for this module or call (fp32, hidden_size 128 "
+                               "or 256, input_size 4..16 in steps of 4, an output width that is a multiple of 4; bf16 "
+                               "and offline_inference are inference-only)")
+        return ipdnet_train.train_forward(self, x)
 
     @ops.on_device
     def forward_stream(self, x, state=None):

@@ -12,14 +12,17 @@ device:
     predict_step      :182-186   and ``predict_stream``, the same from a stream of samples (fnssl/stream.py)
 
 ``pytorch_lightning`` is optional: with it ``MyModel`` is a ``LightningModule``, without it an ``nn.Module`` whose
-methods are called directly.  The constructor is the reference's plus a trailing ``arch``: ``None`` builds ``IPDnet()``
-as the reference does; arrays of more than two microphones pass ``IPDnet(2 * nmic, 256, max_source, True)`` (the
-reference tells its users to edit that line).  ``compile`` is accepted and ignored (there is nothing to compile).
+methods are called directly.  The constructor is the reference's plus two trailing keywords.  ``arch``: ``None`` builds
+``IPDnet()`` as the reference does; arrays of more than two microphones pass ``IPDnet(2 * nmic, 256, max_source, True)``
+(the reference tells its users to edit that line).  ``train_on_device``: with ``True``, ``forward`` in ``train()`` mode
+with gradients enabled calls ``arch.forward_train`` (fnssl/ipdnet_train.py), so ``training_step`` gives a loss whose
+``backward()`` fills every ``.grad`` — for the hidden-128 two-microphone default too (full-band H = 64 training kernels,
+csrc/lstm_train_h64.hip).  With the default ``False`` nothing changes: ``forward`` is ``arch(x)``, which trains by itself
+at hidden 256 and raises the forward-only error in ``train()`` mode at hidden 128.  ``compile`` is accepted and ignored
+(there is nothing to compile).
 
 Out of scope: datasets and the CLI, the ``np.save`` dumps of ``test_step``'s evaluation, runIPDnetOff.py's
-whole-utterance normalisation, and TRAINING the hidden-128 two-microphone default — ``IPDnet()`` keeps raising its
-forward-only error in ``train()`` mode (the full-band H = 64 backward kernels do not exist yet), so with ``arch=None``
-everything here works except the network half of ``loss.backward()``.
+whole-utterance normalisation, bf16 training.
 """
 import os
 import sys
@@ -47,7 +50,7 @@ class MyModel(_Base):
     def __init__(self, tar_useVAD: bool = True, ch_mode: str = 'M', res_the: int = 1, res_phi: int = 180, fs: int = 16000,
                  win_len: int = 512, nfft: int = 512, win_shift_ratio: float = 0.5, max_source: int = 2, device: str = 'cuda',
                  mic_pos=None, compile: bool = False, is_linear_array: bool = True, is_planar_array: bool = True,
-                 exp_name: str = 'exp', arch=None):
+                 exp_name: str = 'exp', arch=None, train_on_device: bool = False):
         super().__init__()
         if (win_len, nfft, win_shift_ratio) != (512, 512, 0.5):
             raise ValueError("the MI355X path is built for win_len = nfft = 512, hop 256 (runIPDnetOn.py:34-35)")
@@ -57,6 +60,7 @@ class MyModel(_Base):
         if not 1 <= int(max_source) <= ipdnet_step.MAX_SOURCES:
             raise ValueError("max_source must be 1..%d, got %r" % (ipdnet_step.MAX_SOURCES, max_source))
         self.arch = IPDnet() if arch is None else arch
+        self.train_on_device = bool(train_on_device)
         self.tar_useVAD = tar_useVAD
         self.ch_mode = ch_mode
         self.nfft = nfft
@@ -80,6 +84,8 @@ class MyModel(_Base):
         self.last_metrics = None
 
     def forward(self, x):
+        if self.train_on_device and self.arch.training and torch.is_grad_enabled():
+            return self.arch.forward_train(x)                        # opt-in: every trainable width (hidden 128 / 256)
         return self.arch(x)
 
     def _log(self, name, value, **kw):

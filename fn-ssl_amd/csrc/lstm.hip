@@ -369,8 +369,8 @@ struct Fp32Call {
 
 // training forward: also save the gate activations (lstm_train.hip)
 int Fp32Call::train() {
-  FNSSL_REQUIRE((H == 128 || H == 256) && !(mode & (kHas1 | kSum)),
-                "lstm_forward: the reserve-saving forward needs hidden 128/256 and no src1 / out_sum");
+  FNSSL_REQUIRE((H == 64 || H == 128 || H == 256) && !(mode & (kHas1 | kSum)),
+                "lstm_forward: the reserve-saving forward needs hidden 64/128/256 and no src1 / out_sum");
   FNSSL_REQUIRE(d->reserve_bytes >= fnssl_lstm_reserve_bytes(d->nseq, H, d->ndir, d->nsteps) && aligned16(d->reserve) &&
                     (long double)d->nsteps * (H / 16) * kReserveRecs * 1024 < 4.0e9L,
                 "lstm_forward: reserve buffer too small or misaligned");

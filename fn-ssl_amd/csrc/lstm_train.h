@@ -282,17 +282,21 @@ int launch_bwd(int nw, int split, const BwdParams& p, int nwg, const LaunchCtx& 
       case 8: return launch_bwd_k<H, 8, 4>(p, nwg, lc);
       case 12: return launch_bwd_k<H, 12, 4>(p, nwg, lc);
     }
-  } else if (split == 4 && !fnssl::tune(FNSSL_TUNE_BWD_RING)) {
-    // 4 waves per group: weights straight from L2 (narrow-band BPTT 31.8 -> 26.0 ms at config 4; with 2 waves
-    // per group the LDS ring is as fast, r01 f_train_layers)
-    if (nw == 4) return launch_bwd_k<H, 4, 1, 4, true>(p, nwg, lc);
-    if (nw == 8) return launch_bwd_k<H, 8, 1, 4, true>(p, nwg, lc);
-  } else if (split == 2 && nw == 4) {
-    return launch_bwd_k<H, 4, 8, 2>(p, nwg, lc);
-  } else if (split == 4 && nw == 4) {
-    return launch_bwd_k<H, 4, 8, 4>(p, nwg, lc);
-  } else if (split == 4 && nw == 8) {
-    return launch_bwd_k<H, 8, 8, 4>(p, nwg, lc);
+  } else if constexpr (H >= 128) {
+    // (H = 64: co_pad / 64 is 1 or 3 output slices, which no 2 or 4 waves divide — backward_rounds() never asks for a
+    //  split there, and the split kernels are not built)
+    if (split == 4 && !fnssl::tune(FNSSL_TUNE_BWD_RING)) {
+      // 4 waves per group: weights straight from L2 (narrow-band BPTT 31.8 -> 26.0 ms at config 4; with 2 waves
+      // per group the LDS ring is as fast, r01 f_train_layers)
+      if (nw == 4) return launch_bwd_k<H, 4, 1, 4, true>(p, nwg, lc);
+      if (nw == 8) return launch_bwd_k<H, 8, 1, 4, true>(p, nwg, lc);
+    } else if (split == 2 && nw == 4) {
+      return launch_bwd_k<H, 4, 8, 2>(p, nwg, lc);
+    } else if (split == 4 && nw == 4) {
+      return launch_bwd_k<H, 4, 8, 4>(p, nwg, lc);
+    } else if (split == 4 && nw == 8) {
+      return launch_bwd_k<H, 8, 8, 4>(p, nwg, lc);
+    }
   }
   fnssl::set_error("lstm_backward: unsupported geometry (%d waves, split %d)", nw, split);
   return FNSSL_E_INVALID;
@@ -325,6 +329,8 @@ int launch_save(int nw, int split, const LstmParams& p, int mode, int nwg, const
                         : launch_save_m<H, kSave>(nw, split, p, nwg, lc);
 }
 
+extern template int launch_bwd<64>(int, int, const BwdParams&, int, const LaunchCtx&);
+extern template int launch_save<64>(int, int, const LstmParams&, int, int, const LaunchCtx&);
 extern template int launch_bwd<128>(int, int, const BwdParams&, int, const LaunchCtx&);
 extern template int launch_bwd<256>(int, int, const BwdParams&, int, const LaunchCtx&);
 extern template int launch_save<128>(int, int, const LstmParams&, int, int, const LaunchCtx&);

@@ -97,8 +97,9 @@ int forward_save(LstmParams p, int H, int mode, const LaunchCtx& lc) {
       if (rc != kNoStatic) return rc;
     }
     choose_chunk(p.quads_per_slice, vr, p.chq, p.pad, gm.split, gm.split > 1 ? lds_chunk_cap(nwg, gm.split) : 0);
-    return H == 128 ? launch_save<128>(gm.nw, gm.split, p, mode | kSave, nwg, lc)
-                    : launch_save<256>(gm.nw, gm.split, p, mode | kSave, nwg, lc);
+    return H == 64    ? launch_save<64>(gm.nw, gm.split, p, mode | kSave, nwg, lc)
+           : H == 128 ? launch_save<128>(gm.nw, gm.split, p, mode | kSave, nwg, lc)
+                      : launch_save<256>(gm.nw, gm.split, p, mode | kSave, nwg, lc);
   });
 }
 
@@ -190,7 +191,7 @@ int fnssl_lstm_backward_status(const void* workspace, size_t workspace_bytes, in
 
 static int check_bwd_desc(const fnssl_lstm_bwd_desc* d, size_t ws_bytes) {
   const int H = d->hidden;
-  FNSSL_REQUIRE(H == 128 || H == 256, "lstm_backward: hidden size %d unsupported (128/256)", H);
+  FNSSL_REQUIRE(H == 64 || H == 128 || H == 256, "lstm_backward: hidden size %d unsupported (64/128/256)", H);
   FNSSL_REQUIRE(d->ndir == 1 || d->ndir == 2, "lstm_backward: ndir must be 1 or 2");
   FNSSL_REQUIRE(d->nseq > 0 && d->nsteps > 0 && d->q_inner > 0, "lstm_backward: empty problem");
   FNSSL_REQUIRE(d->c0g >= 0 && d->c0g % 16 == 0, "lstm_backward: c0g %d must be a multiple of 16", d->c0g);
@@ -241,7 +242,8 @@ static BwdParams bwd_params(const fnssl_lstm_bwd_desc* d) {
 static int backward_rounds(BwdParams p, int H, const LaunchCtx& lc) {
   if (lc.dry) return FNSSL_OK;   // (one family whatever the geometry: nothing more to plan)
   const int nso = p.co_pad / 64;
-  const int max_split = nso % 4 == 0 ? 4 : nso % 2 == 0 ? 2 : 1;   // output slices divide among the waves
+  // output slices divide among the waves (H = 64: co_pad = 64 or 192, one or three slices — always the per-wave rounds)
+  const int max_split = nso % 4 == 0 ? 4 : nso % 2 == 0 ? 2 : 1;
   return plan_rounds(p.ntasks, p.ndir, max_split, H == 256 ? 6 : 2, [&](const Geometry& gm) {
     p.task0 = gm.t0;
     p.task1 = gm.t1;
@@ -256,7 +258,9 @@ static int backward_rounds(BwdParams p, int H, const LaunchCtx& lc) {
     const Variant vr{gm.nw, gm.split > 1 ? 8 : 4, 1};
     const int nwg = p.wgs_per_dir * p.ndir;
     choose_chunk(p.quads_per_slice, vr, p.chq, p.pad, gm.split, gm.split > 1 ? lds_chunk_cap(nwg, gm.split) : 0);
-    return H == 128 ? launch_bwd<128>(gm.nw, gm.split, p, nwg, lc) : launch_bwd<256>(gm.nw, gm.split, p, nwg, lc);
+    return H == 64    ? launch_bwd<64>(gm.nw, gm.split, p, nwg, lc)
+           : H == 128 ? launch_bwd<128>(gm.nw, gm.split, p, nwg, lc)
+                      : launch_bwd<256>(gm.nw, gm.split, p, nwg, lc);
   });
 }
 
@@ -268,7 +272,7 @@ static int lstm_backward_impl(const fnssl_lstm_bwd_desc* d, const LaunchCtx& lc,
   const int H = d->hidden;
   BwdParams p = bwd_params(d);
   const double flops = 2.0 * 4 * H * (double)(d->c0g + H) * d->nseq * (double)d->nsteps * d->ndir;
-  fnssl::TimedLaunch tl(lc.dry ? nullptr : H == 128 ? "lstm_bwd_h128" : "lstm_bwd_h256", lc.st, flops);
+  fnssl::TimedLaunch tl(lc.dry ? nullptr : H == 64 ? "lstm_bwd_h64" : H == 128 ? "lstm_bwd_h128" : "lstm_bwd_h256", lc.st, flops);
   if (family) *family = FNSSL_LSTM_FAMILY_BWD;
   // full-band layers of a large enough shard: the cluster-resident kernel (lstm_bwdc.h), then — in the same call — the
   // per-wave / split kernels as its guarded fallback
@@ -284,7 +288,7 @@ static int lstm_backward_impl(const fnssl_lstm_bwd_desc* d, const LaunchCtx& lc,
 }
 
 // ---- the training kernels (forward with reserve, BPTT) for hidden size 128 (explicit instantiation, see lstm_train.h; hidden
-// size 256: lstm_train_h256.hip)
+// sizes 64 and 256: lstm_train_h64.hip, lstm_train_h256.hip)
 namespace fnssl_lstm {
 template int launch_bwd<128>(int, int, const BwdParams&, int, const LaunchCtx&);
 template int launch_save<128>(int, int, const LstmParams&, int, int, const LaunchCtx&);

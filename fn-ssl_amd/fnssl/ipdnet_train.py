@@ -2,11 +2,14 @@
 ``train()`` mode returns a tensor with a ``grad_fn``, so the reference's loop runs unchanged
 (``pred = self.arch(in_batch); loss = cal_loss(pred, gt); loss.backward(); optimizer.step()``, Adam lr 5e-4).
 
-Supported: fp32 modules with ``hidden_size=256`` (full-band BiLSTM H = 128; narrow-band LSTM H = 256 online or BiLSTM
-H = 128 offline), ``input_size`` a multiple of 4 up to 16 and an output width ``2 * (input_size // 2 - 1) * max_track``
-that is a multiple of 4; ``offline_inference=False``.  Every other configuration (the two-microphone default
-``IPDnet()`` with hidden 128, bf16 modules, ``offline_inference=True``, ``forward_stream``) keeps raising the
-forward-only error ("... call .eval() first").
+Trainable (``trainable()``): fp32 modules with ``hidden_size`` 256 (full-band BiLSTM H = 128; narrow-band LSTM H = 256
+online or BiLSTM H = 128 offline) or 128, the reference's default (full-band BiLSTM H = 64; narrow-band LSTM H = 128
+online or BiLSTM H = 64 offline), ``input_size`` a multiple of 4 up to 16 and an output width
+``2 * (input_size // 2 - 1) * max_track`` that is a multiple of 4; ``offline_inference=False``.  ``IPDnet.forward`` routes
+here by itself only at hidden 256 (``supported()``); at hidden 128 the train-mode forward is the opt-in
+``IPDnet.forward_train`` (``MyModel(..., train_on_device=True)`` in ``IPDnet/train_step.py``), and ``forward`` keeps
+raising the forward-only error ("... call .eval() first") — as it does for bf16 modules, ``offline_inference=True`` and
+``forward_stream``.
 
 ``IPDnetTrainGraph`` runs, over the C-ABI kernels only (no ATen compute; plumbing copies and the weight packing aside):
 
@@ -16,14 +19,14 @@ forward-only error ("... call .eval() first").
     backward  conv head backward (fnssl_conv3x3_act_pool_backward, fnssl_conv3x3_causal_backward_data into D3's 256
               channels, fnssl_conv3x3_weight_grads) -> site 3 -> narrow-2 BPTT (c0g = 256) -> site 2 -> full-2 BPTT
               (c0g = 256) -> site 1 -> narrow-1 BPTT (c0g = 256) -> site 0 -> full-1 BPTT (c0g = 0), with
-              fnssl_lstm_weight_grads per layer.  No residual sums: the skips are concatenations, whose x part gets
+              fnssl_lstm_weight_grads per layer (256 = hidden_size; 128 at the default width).  No residual sums: the skips are concatenations, whose x part gets
               no gradient.
 
 Dropout (p = 0.2, every FNblock of the reference): sites 0-3 are block_1.dropout_full, block_1.dropout_narr,
 block_2.dropout_full, block_2.dropout_narr.  nn.Dropout's Bernoulli stream cannot be reproduced outside torch's RNG; the
 keep mask of site s is the library's keep-scale hash (``fnssl_train_combine``, restated as
-``oracle.train_ref.dropout_scale``) with seed ``train.layer_seed(base, s)`` over the LOGICAL [nb, nt, nf, 256]
-activation, element index ((u * nt + t) * nf + f) * 256 + c with u the GLOBAL utterance index.  ``base`` follows
+``oracle.train_ref.dropout_scale``) with seed ``train.layer_seed(base, s)`` over the LOGICAL [nb, nt, nf, hidden_size]
+activation, element index ((u * nt + t) * nf + f) * hidden_size + c with u the GLOBAL utterance index.  ``base`` follows
 ``FN_SSL``'s rules (``fnssl.autograd``): ``module.dropout_seed`` (default ``torch.initial_seed()``) and
 ``module.dropout_calls`` (incremented per train-mode forward), or ``module.force_dropout_base`` pinned.  The first
 utterance of the call is global utterance ``module.utt_offset`` (default rank * nb under an initialised process group,
@@ -41,21 +44,29 @@ import torch
 from . import autograd, ops, train
 
 SITES = ("block_1.dropout_full", "block_1.dropout_narr", "block_2.dropout_full", "block_2.dropout_narr")
-CH = 256                     # FN-block output channels at hidden_size 256
+CH = 256                     # FN-block output channels at hidden_size 256, the width ``IPDnet.forward`` routes by itself
+WIDTHS = (128, 256)          # hidden sizes with training kernels: full-band BiLSTM H = 64 / 128
 
 
 def _param_key(module):
     return tuple((p.data_ptr(), p._version, str(p.device)) for p in module.parameters())
 
 
-def supported(model, offline_inference=False) -> bool:
-    """Whether ``IPDnet.forward`` in train mode has a HIP training path for this module and call."""
+def trainable(model, offline_inference=False) -> bool:
+    """Whether the HIP training path (``IPDnet.forward_train``) takes this module and call."""
     if offline_inference or next(model.parameters()).dtype != torch.float32:
         return False
     nc, cout = model.input_size, model.cnn_out_dim
     blocks = (model.block_1, model.block_2)
-    return (model.hidden_size == 256 and 4 <= nc <= 16 and nc % 4 == 0 and cout > 0 and cout % 4 == 0 and
+    return (model.hidden_size in WIDTHS and 4 <= nc <= 16 and nc % 4 == 0 and cout > 0 and cout % 4 == 0 and
             model.conv.cnn_hidden_dim == 128 and all(abs(float(b.dropout) - 0.2) < 1e-12 for b in blocks))
+
+
+def supported(model, offline_inference=False) -> bool:
+    """Whether ``IPDnet.forward`` in train mode routes to the HIP training path by itself: the trainable modules of
+    hidden_size 256.  (The default width trains through ``IPDnet.forward_train``: its ``forward`` keeps the
+    forward-only error in train mode.)"""
+    return model.hidden_size == CH and trainable(model, offline_inference)
 
 
 def dropout_sites(model):
@@ -97,10 +108,11 @@ class IPDnetTrainGraph:
         nc = model.input_size
         b1, b2 = model.block_1, model.block_2
         self.nc, self.cout = nc, model.cnn_out_dim
+        ch = self.ch = model.hidden_size                            # FN-block output channels
         self.lf1 = _Lstm("block_1.fullLstm", "full", b1.fullLstm, nc, 0, 0)
-        self.ln1 = _Lstm("block_1.narrLstm", "narrow", b1.narrLstm, CH, nc, CH)
-        self.lf2 = _Lstm("block_2.fullLstm", "full", b2.fullLstm, CH, nc, CH)
-        self.ln2 = _Lstm("block_2.narrLstm", "narrow", b2.narrLstm, CH, nc, CH)
+        self.ln1 = _Lstm("block_1.narrLstm", "narrow", b1.narrLstm, ch, nc, ch)
+        self.lf2 = _Lstm("block_2.fullLstm", "full", b2.fullLstm, ch, nc, ch)
+        self.ln2 = _Lstm("block_2.narrLstm", "narrow", b2.narrLstm, ch, nc, ch)
         self.lstms = (self.lf1, self.ln1, self.lf2, self.ln2)
         self._packed, self._packed_key = None, None
 
@@ -118,9 +130,9 @@ class IPDnetTrainGraph:
                     bw[L.name].append(torch.from_numpy(ops.pack_lstm_bwd_host(g("weight_ih"), g("weight_hh"),
                                                                               L.c0g)).to(dev))
             cv = self.model.conv
-            conv_fw = (ops.pack_conv3x3(cv.conv1.weight, CH, self.nc, dev), ops.pack_conv3x3(cv.conv2.weight, 128, 0, dev),
+            conv_fw = (ops.pack_conv3x3(cv.conv1.weight, self.ch, self.nc, dev), ops.pack_conv3x3(cv.conv2.weight, 128, 0, dev),
                        ops.pack_conv3x3(cv.conv3.weight, 128, 0, dev))
-            conv_bw = (ops.pack_conv3x3_backward_data(cv.conv1.weight, CH, dev),
+            conv_bw = (ops.pack_conv3x3_backward_data(cv.conv1.weight, self.ch, dev),
                        ops.pack_conv3x3_backward_data(cv.conv2.weight, 128, dev),
                        ops.pack_conv3x3_backward_data(cv.conv3.weight, 128, dev))
             self._packed, self._packed_key = (fw, bw, conv_fw, conv_bw), key
@@ -130,6 +142,7 @@ class IPDnetTrainGraph:
         """x [nb, nc, nf, nt] -> (conv 3 output [nb, nf, nt // 12, cout], saved activations for ``backward``)."""
         nb, nc, nf, nt = x.shape
         dev = x.device
+        CH = self.ch
         fw, _, cfw, _ = self.streams(dev)
         lf1, ln1, lf2, ln2 = self.lstms
         XF = ops.nchw_to_seq(x)                                        # [b, t, f, nc]
@@ -168,6 +181,7 @@ class IPDnetTrainGraph:
         """Accumulate every parameter gradient given dL/dY3 ([nb, nf, nt // 12, cout]); ``grads``: name -> tensor."""
         nb, nf, nt = saved["shape"]
         dev = dY3.device
+        CH = self.ch
         _, bw, _, cbw = self.streams(dev)
         lf1, ln1, lf2, ln2 = self.lstms
         XF, XN, res = saved["XF"], saved["XN"], saved["res"]
@@ -181,7 +195,7 @@ class IPDnetTrainGraph:
         dP1 = ops.conv3x3_causal_backward_data(dZ2, cbw[1], 128)
         dZ1 = ops.conv3x3_act_pool_backward(dP1, saved["Y1"], 3, "relu")
         ops.conv3x3_weight_grads(dZ1, D3.permute(0, 2, 1, 3), XN.permute(0, 2, 1, 3), grads["conv.conv1.weight"])
-        dY = ops.conv3x3_causal_backward_data(dZ1, cbw[0], CH)          # [nb, nf, nt, 256] = dL/dD3, narrow storage
+        dY = ops.conv3x3_causal_backward_data(dZ1, cbw[0], CH)          # [nb, nf, nt, CH] = dL/dD3, narrow storage
         del dZ1, dP1, dZ2, dP2, dZ3
 
         def weight_grads(L, dA, x0, x2, h):
@@ -201,13 +215,13 @@ class IPDnetTrainGraph:
         DN2 = ln2.natural(nb, nt, nf, CH, dev)
         train.combine(DN2, masked=(dY.permute(0, 2, 1, 3),), seed32=seeds[3], b0=b0)       # site 3 backward
         del dY
-        dv = bptt(ln2, DN2, D2, XN, saved["N2"])                                          # narrow 2, c0g = 256
+        dv = bptt(ln2, DN2, D2, XN, saved["N2"])                                          # narrow 2, c0g = CH
         DF2 = lf2.natural(nb, nt, nf, CH, dev)
         train.combine(DF2, masked=dv, seed32=seeds[2], b0=b0)                             # site 2 backward
-        du = bptt(lf2, DF2, D1, XF, saved["F2"])                                          # full 2, c0g = 256
+        du = bptt(lf2, DF2, D1, XF, saved["F2"])                                          # full 2, c0g = CH
         DN1 = ln1.natural(nb, nt, nf, CH, dev)
         train.combine(DN1, masked=du, seed32=seeds[1], b0=b0)                             # site 1 backward
-        dv = bptt(ln1, DN1, D0, XN, saved["N1"])                                          # narrow 1, c0g = 256
+        dv = bptt(ln1, DN1, D0, XN, saved["N1"])                                          # narrow 1, c0g = CH
         DF1 = lf1.natural(nb, nt, nf, CH, dev)
         train.combine(DF1, masked=dv, seed32=seeds[0], b0=b0)                             # site 0 backward
         bptt(lf1, DF1, XF, None, saved["F1"])                                             # full 1, c0g = 0
@@ -246,7 +260,7 @@ class IPDnetTrainFunction(torch.autograd.Function):
 
 
 def train_forward(model, x):
-    """``IPDnet.forward`` in train mode (supported configurations): x [nb, nc, nf, nt] ->
+    """``IPDnet.forward`` / ``IPDnet.forward_train`` in train mode (trainable configurations): x [nb, nc, nf, nt] ->
     [nb, nt // 12, 2 nf, nc / 2 - 1, max_track] with a ``grad_fn``."""
     ops._need_dev(x)
     if x.ndim != 4 or x.shape[1] != model.input_size or x.shape[3] < ops.SEG_FRAMES:

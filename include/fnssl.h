@@ -224,7 +224,7 @@ typedef struct {
   size_t workspace_bytes;
   int variant;         /* 0 = default; see DESIGN.md (kernel variants)        */
   /* training forward (autograd's "save for backward"): when non-NULL the kernel also stores the gate
-   * activations and cell state, >= fnssl_lstm_reserve_bytes(); hidden 128/256, no src1 / out_sum.  */
+   * activations and cell state, >= fnssl_lstm_reserve_bytes(); hidden 64/128/256, no src1 / out_sum.  */
   float* reserve;
   size_t reserve_bytes;
   /* streaming (uni-directional layers only): 1 = continue a sequence.  h_{-1} is read from the row
@@ -362,6 +362,8 @@ size_t fnssl_lstm_bwd_workspace_bytes(int nseq, int hidden, int ndir);
  *   dx  the gradient of the first c0g input channels, one slab per direction [.., dir * c0g + ch]
  *       (the caller adds the two directions).
  * Views are addressed like fnssl_lstm_desc's (q / q_inner, q % q_inner, step).
+ * hidden: 64, 128 or 256.  (64 — the default IPDnet's full-band and offline narrow-band layers — always runs one wave per
+ * 16-sequence group: its 64 or 192 output channels are one or three output slices, which no 2 or 4 waves divide.)
  */
 typedef struct {
   const float* reserve;
