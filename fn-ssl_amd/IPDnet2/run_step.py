@@ -9,7 +9,7 @@ prediction, a frame-level PIT-MSE loss and the ACC / MDR / FAR / MAE / RMSE metr
     validation_step / test_step  :173-221   the loss, then ``IPDnet2.Module.PredDOA(mic_location=gt_batch[-3])``: the MSE
                                  template search of all tracks and the metrics, logged as ``valid/<m>`` / ``test/<m>`` when a
                                  trainer is attached and kept on ``last_metrics``
-    predict_step      :225-229
+    predict_step      :225-229   and ``predict_stream``, the same from a stream of samples (fnssl/stream.py)
     configure_optimizers :330-339   AdamW(lr 5e-4) + ExponentialLR(0.975)
 
 Frame-count alignment (:183-189).  When the prediction has more frames than the targets the reference cuts the prediction;
@@ -148,6 +148,24 @@ class MyModel(_Base):
         """batch [nb, nch, ns] -> the first utterance's prediction [nt', 512, nmic - 1, max_track] (:225-229)."""
         data_batch = self.data_preprocess(mic_sig_batch=batch.permute(0, 2, 1))
         return self.forward(data_batch[0])[0]
+
+    @torch.no_grad()
+    def predict_stream(self, chunk, state=None, last: bool = False):
+        """Online ``predict_step``: chunk [nb, nch, n] = the NEXT n samples (any n) -> (preds, state).  ``preds`` is the
+        first utterance's [new frames, 512, nmic - 1, max_track] for the groups of 5 transform frames this chunk completes
+        (a frame is complete 256 samples after its centre), or None when it completes none; ``state`` (None for the first
+        chunk) is the ``fnssl.stream.OnlineLocalizer`` that carries the sample tail, the normalisation and the network
+        state.  ``last=True`` says that the signal ends with this chunk: the groups only the known end completes (the last
+        frame reflects at it) are returned with the chunk's own, and the stream is finished."""
+        from fnssl import stream
+        if state is None:
+            state = stream.OnlineLocalizer(self.arch, stream.CentredStreamFrontEnd(
+                chunk.shape[1], sample_length=249, eps=1e-6, segment_frames=self.arch.time_compression_ratio))
+        preds = [state.push(chunk.permute(0, 2, 1).to(self.dev).float())[0]]
+        if last:
+            preds.append(state.finish()[0])
+        preds = [p[0] for p in preds if p is not None]
+        return (None if not preds else preds[0] if len(preds) == 1 else torch.cat(preds, dim=0)), state
 
     def cal_loss(self, pred_batch=None, gt_batch=None, mode='train'):
         """Frame-level PIT-MSE (:237-251) in one HIP kernel.  ``mode='train'``: the loss, a 0-d device tensor; otherwise

@@ -13,6 +13,14 @@
 // The tile's spectra live in LDS while they fit (12 frames x 4 channels = 96 KiB beside the transform staging) and in a
 // caller-owned scratch inside the state otherwise (8 channels: 192 KiB): written in A, re-read in C by other waves of the
 // SAME workgroup behind the workgroup barrier, whose workgroup-scope release / acquire is all that needs (one CU, one L1).
+//
+// IPDnet2's transform (fnssl_stream_frontend_centred) is the same kernel with two compile-time parameters: hop 320, and
+// CENTRED = torch.stft(center=True), where frame t covers samples 320 t - 256 .. 320 t + 255 of the signal extended by
+// reflection.  The index is folded per sample in phase A exactly as the whole-signal kernels fold it (the start always,
+// the end only once the caller knows the total length); everything after the fetch is the code of the hop-256
+// instantiations, whose bits therefore stay what they were.  Its tile is 10 frames (two of the 5-frame groups IPDnet2's
+// time pooling consumes): 10 frames x 5 channels = 100 KiB of spectra beside the 37 KiB of staging, so the shipped
+// five-microphone array (and six channels) stays in LDS; from 7 channels on a full tile goes through the scratch.
 #include <cstdint>
 
 #include "host.h"
@@ -28,13 +36,17 @@ using namespace fnssl_frontend;
 constexpr int kStreamWaves = 16;
 constexpr int kStreamThreads = kStreamWaves * 64;
 constexpr int kStreamTile = 12;            // frames per pass: the chunk the online models consume
+constexpr int kCentredTile = 10;           // the centred hop-320 entry: two groups of IPDnet2's time pooling
+constexpr int kCentredHop = 320;
 constexpr int kStreamMaxCh = 16;
 constexpr size_t kLdsBudget = 160 * 1024;
 constexpr size_t kStateAlign = 256;
 
 struct StreamParams {
-  const float* sig;        // first sample of frame `frame0`
+  const float* sig;        // first sample of frame `frame0`; CENTRED: sample `sample0` of the signal
   long long sb, sn, sc;
+  long long sample0;       // CENTRED: absolute index of sig's first sample
+  long long total;         // CENTRED: length of the whole signal, negative while it is not known (no end reflection)
   int nch, nchain, ch_mode;
   int frame0, nframes, tile, sample_length;
   const float* ca;         // [sample_length + 1], indexed by min(t, sample_length)
@@ -57,8 +69,9 @@ bool spectra_in_lds(int nch, int nchain, int tile) {
   return fixed_lds_floats(nch, nchain, tile) * sizeof(float) + spectra_bytes(nch, tile) <= kLdsBudget;
 }
 
-template <int ARRAY>
+template <int ARRAY, int CENTRED>
 __global__ void __launch_bounds__(kStreamThreads) stream_frontend_kernel(const StreamParams p) {
+  constexpr int HOP = CENTRED ? kCentredHop : kHop;
   extern __shared__ __attribute__((aligned(16))) float smem_stream[];
   float2* tw = reinterpret_cast<float2*>(smem_stream);                  // [kTwiddles]
   float* hann = smem_stream + 2 * kTwiddles;                            // [512]
@@ -83,11 +96,28 @@ __global__ void __launch_bounds__(kStreamThreads) stream_frontend_kernel(const S
     // A: transforms, one wave per (frame, channel)
     for (int w = wave; w < n * p.nch; w += kStreamWaves) {
       const int f = w / p.nch, c = w - f * p.nch;
-      const float* xc = ub + (long long)c * p.sc + (long long)(f0 + f) * kHop * p.sn;
+      if (CENTRED) {
+        // torch.stft(center=True): the frame starts half a window before 320 t; reflection at both ends as an index fold,
+        // in the order of stft_rows_kernel; the host has checked that every folded index lies in the window
+        const float* xc = ub + (long long)c * p.sc;
+        const long long n0 = (long long)(p.frame0 + f0 + f) * HOP - kWin / 2;
+        auto at = [&](long long src) {
+          src = src < 0 ? -src : src;
+          src = (p.total >= 0 && src >= p.total) ? 2 * (p.total - 1) - src : src;
+          return xc[(src - p.sample0) * p.sn];
+        };
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = lane + 64 * r;
-        window_store(z, hann, m, xc[(long long)(2 * m) * p.sn], xc[(long long)(2 * m + 1) * p.sn]);
+        for (int r = 0; r < 4; ++r) {
+          const int m = lane + 64 * r;
+          window_store(z, hann, m, at(n0 + 2 * m), at(n0 + 2 * m + 1));
+        }
+      } else {
+        const float* xc = ub + (long long)c * p.sc + (long long)(f0 + f) * HOP * p.sn;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int m = lane + 64 * r;
+          window_store(z, hann, m, xc[(long long)(2 * m) * p.sn], xc[(long long)(2 * m + 1) * p.sn]);
+        }
       }
       wave_lds_sync();
       fft256_radix4(z, tw, lane);
@@ -162,6 +192,34 @@ bool bad_shape(int nb, int nch, int mode, int ch_mode) {
   return nb <= 0 || nch < (mode == FNSSL_STREAM_PAIR ? 2 : 1) || nch > kStreamMaxCh;
 }
 
+// Carve the state, size the LDS and launch: p holds the problem; nb workgroups.
+int launch_stream(StreamParams p, int nb, bool array, bool centred, void* state, const char* name, void* stream) {
+  p.mu = static_cast<float*>(state);
+  const bool in_lds = spectra_in_lds(p.nch, p.nchain, p.tile);
+  p.scratch = in_lds ? nullptr : reinterpret_cast<float2*>(static_cast<char*>(state) + mu_bytes(nb, p.nchain));
+  const size_t lds = fixed_lds_floats(p.nch, p.nchain, p.tile) * sizeof(float) + (in_lds ? spectra_bytes(p.nch, p.tile) : 0);
+  hipStream_t st = fnssl::as_stream(stream);
+  fnssl::TimedLaunch tl(name, st);
+  if (centred)
+    return enqueue(st, Kernel{stream_frontend_kernel<1, 1>, kStreamThreads, lds, "stream_frontend_kernel"}, (unsigned)nb, p);
+  return fnssl::with_bool(array, [&](auto ARRAY) {
+    return enqueue(st, Kernel{stream_frontend_kernel<ARRAY, 0>, kStreamThreads, lds, "stream_frontend_kernel"}, (unsigned)nb, p);
+  });
+}
+
+// The signal indices frame t of the centred hop-320 transform reads after folding, [lo, hi]: the start fold always, the
+// end fold when the total length is known (total >= 0; the caller has checked t <= total / 320 and total > 256).
+void centred_reach(long long t, long long total, long long& lo, long long& hi) {
+  const long long a = t * kCentredHop - kWin / 2, b = a + kWin - 1;
+  lo = a < 0 ? 0 : a;
+  hi = a < 0 && -a > b ? -a : b;
+  if (total >= 0 && hi >= total) {
+    const long long folded = 2 * (total - 1) - hi;
+    lo = folded < lo ? folded : lo;
+    hi = total - 1;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -208,16 +266,64 @@ int fnssl_stream_frontend(const float* sig, int nb, int ns, int nch, long long s
   p.ca = coef_a;
   p.cb = coef_b;
   p.eps = eps;
-  p.mu = static_cast<float*>(state);
-  const bool in_lds = spectra_in_lds(nch, p.nchain, p.tile);
-  p.scratch = in_lds ? nullptr : reinterpret_cast<float2*>(static_cast<char*>(state) + mu_bytes(nb, p.nchain));
   p.x = x;
-  const size_t lds = fixed_lds_floats(nch, p.nchain, p.tile) * sizeof(float) + (in_lds ? spectra_bytes(nch, p.tile) : 0);
-  hipStream_t st = fnssl::as_stream(stream);
-  fnssl::TimedLaunch tl("stream_frontend", st);
-  return fnssl::with_bool(mode == FNSSL_STREAM_ARRAY, [&](auto ARRAY) {
-    return enqueue(st, Kernel{stream_frontend_kernel<ARRAY>, kStreamThreads, lds, "stream_frontend_kernel"}, (unsigned)nb, p);
-  });
+  return launch_stream(p, nb, mode == FNSSL_STREAM_ARRAY, false, state, "stream_frontend", stream);
+}
+
+size_t fnssl_stream_frontend_centred_state_bytes(int nb, int nch, int max_new_frames) {
+  if (nb <= 0 || nch < 1 || nch > kStreamMaxCh || max_new_frames <= 0) return 0;
+  const int tile = max_new_frames < kCentredTile ? max_new_frames : kCentredTile;
+  return mu_bytes(nb, 1) + (spectra_in_lds(nch, 1, tile) ? 0 : (size_t)nb * spectra_bytes(nch, tile));
+}
+
+int fnssl_stream_frontend_centred(const float* sig, int nb, int ns, int nch, long long sb, long long sn, long long sc,
+                                  long long sample0, int frame0, int nframes, long long total, const float* coef_a,
+                                  const float* coef_b, int sample_length, float eps, void* state, size_t state_bytes,
+                                  float* x, void* stream) {
+  FNSSL_REQUIRE(sig && coef_a && coef_b && state && x, "stream_frontend_centred: null pointer");
+  FNSSL_REQUIRE(nb > 0, "stream_frontend_centred: empty batch (nb %d)", nb);
+  FNSSL_REQUIRE(nch >= 1 && nch <= kStreamMaxCh, "stream_frontend_centred: 1 to %d channels (%d given)", kStreamMaxCh, nch);
+  FNSSL_REQUIRE(nframes > 0, "stream_frontend_centred: frame count %d", nframes);
+  FNSSL_REQUIRE(frame0 >= 0 && (long long)frame0 + nframes < (1ll << 31) / kCentredHop,
+                "stream_frontend_centred: first frame %d", frame0);
+  FNSSL_REQUIRE(sample_length > 0, "stream_frontend_centred: sample_length %d", sample_length);
+  FNSSL_REQUIRE(total < 0 || total > kWin / 2,
+                "stream_frontend_centred: total length %lld is too short for reflect padding of %d", total, kWin / 2);
+  const long long last = (long long)frame0 + nframes - 1;
+  FNSSL_REQUIRE(total < 0 || last <= total / kCentredHop,
+                "stream_frontend_centred: frame %lld does not exist in a signal of total length %lld", last, total);
+  FNSSL_REQUIRE(ns > 0 && sample0 >= 0, "stream_frontend_centred: window of %d samples at %lld", ns, sample0);
+  for (long long t = frame0; t <= last; ++t) {
+    long long lo, hi;
+    centred_reach(t, total, lo, hi);
+    FNSSL_REQUIRE(lo >= sample0 && hi < sample0 + ns,
+                  "stream_frontend_centred: frame %lld reads samples %lld..%lld, the window holds %lld..%lld", t, lo, hi,
+                  sample0, sample0 + ns - 1);
+  }
+  const size_t need = fnssl_stream_frontend_centred_state_bytes(nb, nch, nframes);
+  FNSSL_REQUIRE(state_bytes >= need,
+                "stream_frontend_centred: state of %zu bytes, fnssl_stream_frontend_centred_state_bytes asks for %zu",
+                state_bytes, need);
+  FNSSL_REQUIRE(((uintptr_t)sig | (uintptr_t)coef_a | (uintptr_t)coef_b) % 4 == 0 && (uintptr_t)state % 16 == 0 &&
+                    (uintptr_t)x % 16 == 0,
+                "stream_frontend_centred: misaligned pointer (samples and coefficients 4 bytes, state and output 16)");
+  StreamParams p{};
+  p.sig = sig;
+  p.sb = sb; p.sn = sn; p.sc = sc;
+  p.sample0 = sample0;
+  p.total = total;
+  p.nch = nch;
+  p.nchain = 1;
+  p.ch_mode = FNSSL_CH_MODE_M;
+  p.frame0 = frame0;
+  p.nframes = nframes;
+  p.tile = nframes < kCentredTile ? nframes : kCentredTile;
+  p.sample_length = sample_length;
+  p.ca = coef_a;
+  p.cb = coef_b;
+  p.eps = eps;
+  p.x = x;
+  return launch_stream(p, nb, true, true, state, "stream_frontend_centred", stream);
 }
 
 }  // extern "C"

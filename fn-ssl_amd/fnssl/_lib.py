@@ -66,6 +66,7 @@ SYMBOLS = [
     "fnssl_ipd2doa_tracks", "fnssl_doa_metrics",
     "fnssl_doa_metrics_ex", "fnssl_ipd2doa_mse_tracks", "fnssl_ipdnet2_targets",
     "fnssl_stream_frontend_state_bytes", "fnssl_stream_frontend",
+    "fnssl_stream_frontend_centred_state_bytes", "fnssl_stream_frontend_centred",
     "fnssl_sn_mamba_backward_workspace_bytes", "fnssl_sn_mamba_backward_chunk", "fnssl_sn_mamba_backward",
     "fnssl_sn_fconv_backward_workspace_bytes", "fnssl_sn_fconv_backward",
     "fnssl_sn_full_backward_workspace_bytes", "fnssl_sn_full_backward",
@@ -238,6 +239,9 @@ def load():
     lib.fnssl_stream_frontend_state_bytes.argtypes = [i, i, i, i, i]
     lib.fnssl_stream_frontend_state_bytes.restype = sz
     lib.fnssl_stream_frontend.argtypes = [vp, i, i, i, ll, ll, ll, i, i, i, i, vp, vp, i, f, vp, sz, vp, vp]
+    lib.fnssl_stream_frontend_centred_state_bytes.argtypes = [i, i, i]
+    lib.fnssl_stream_frontend_centred_state_bytes.restype = sz
+    lib.fnssl_stream_frontend_centred.argtypes = [vp, i, i, i, ll, ll, ll, ll, i, i, ll, vp, vp, i, f, vp, sz, vp, vp]
     lib.fnssl_pair_features.argtypes = [vp, vp, vp, vp, i, i, i, i, f, vp, vp, i, vp]
     lib.fnssl_nchw_to_seq.argtypes = [vp, i, i, i, i, vp, vp]
     lib.fnssl_lstm_packed_floats.argtypes = [i, i, i]

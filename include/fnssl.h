@@ -799,6 +799,34 @@ int fnssl_stream_frontend(const float* sig, int nb, int ns, int nch, long long s
                           int ch_mode, int frame0, int nframes, const float* coef_a, const float* coef_b,
                           int sample_length, float eps, void* state, size_t state_bytes, float* x, void* stream);
 
+/* ---- streamed front end of IPDnet2 (additive: FNSSL_ABI_VERSION stays 19) -----------------------------------------------
+ * The same kernel for torch.stft(center=True, pad_mode='reflect') with hop 320: frame t covers samples
+ * 320 t - 256 .. 320 t + 255 of the signal extended by reflection, folded per sample as fnssl_stft_ex(center = 1) folds
+ * them (src < 0 -> -src, then src >= total -> 2 (total - 1) - src).  Array normalisation only (mu per utterance over all
+ * channels); x [nb, nframes, 256, 2 * nch] = layout 0 of fnssl_array_features on fnssl_stft_ex(hop 320, center 1), bit
+ * for bit, whatever the sequence of calls.  While the stream is open (total < 0) a frame t >= 1 can be asked for once
+ * sample 320 t + 255 has arrived and frame 0 once sample 256 has; only the last frame total / 320 of a signal can touch
+ * the end reflection, it reaches back to sample 320 t - 257 at most, and it is asked for with total given.
+ *
+ * Bytes of the caller-owned state (zeroed before the first call): the carried mu [nb] and, where a tile of 10 frames of
+ * spectra does not fit the LDS (more than 6 channels), the scratch.  0 for nb <= 0, nch outside 1..16,
+ * max_new_frames <= 0. */
+size_t fnssl_stream_frontend_centred_state_bytes(int nb, int nch, int max_new_frames);
+
+/*
+ *   sig            sample `sample0` of the signal (absolute index, >= 0): sample sample0 + n of channel c of utterance b
+ *                  at sig[b*sb + n*sn + c*sc], n < ns
+ *   frame0         absolute index of the first frame of this call; nframes > 0
+ *   total          the length of the whole signal once it is known (> 256, frame0 + nframes - 1 <= total / 320), else < 0
+ *   coef_a/b, sample_length, eps, state, x   as fnssl_stream_frontend (IPDnet2: sample_length 249)
+ * FNSSL_E_INVALID before any launch: null or misaligned pointers, nch outside 1..16, a window [sample0, sample0 + ns)
+ * that does not hold every index the frames read after folding, total in 0..256, a state that is too small.
+ */
+int fnssl_stream_frontend_centred(const float* sig, int nb, int ns, int nch, long long sb, long long sn, long long sc,
+                                  long long sample0, int frame0, int nframes, long long total, const float* coef_a,
+                                  const float* coef_b, int sample_length, float eps, void* state, size_t state_bytes,
+                                  float* x, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* IPDnet head (next row 8f-3): causal 3x3 Conv2d + time pooling              */
 /* ------------------------------------------------------------------------- */
