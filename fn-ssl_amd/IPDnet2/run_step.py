@@ -167,6 +167,20 @@ class MyModel(_Base):
         preds = [p[0] for p in preds if p is not None]
         return (None if not preds else preds[0] if len(preds) == 1 else torch.cat(preds, dim=0)), state
 
+    def open_stream_pool(self, nch: int, slots: int, localize: bool = False, mic_location=None):
+        """A ``fnssl.stream.StreamPool`` on ``self.arch``: ``slots`` independent streams of ``nch`` microphones, each with
+        its own start, chunk sizes and end, served by one set of launches per push (``pool.open()``, ``pool.push({slot:
+        chunk [n, nch]}, last=())``, ``pool.close(slot)``).  ``localize=True`` maps every prediction to (DOA, activity,
+        spectrum) of its two tracks with the template search of ``PredDOA`` on ``mic_location`` [nmic, 3]."""
+        from fnssl import stream
+        entry = None
+        if localize:
+            if mic_location is None:
+                raise ValueError("open_stream_pool: localize=True needs mic_location [nmic, 3]")
+            pd = PredDOA(mic_location=mic_location, dev=self.dev)
+            entry = lambda p: pd._search(p[..., :2], 1)                     # noqa: E731
+        return stream.StreamPool(self.arch, nch, slots, localize=entry, sample_length=249, eps=1e-6)
+
     def cal_loss(self, pred_batch=None, gt_batch=None, mode='train'):
         """Frame-level PIT-MSE (:237-251) in one HIP kernel.  ``mode='train'``: the loss, a 0-d device tensor; otherwise
         (loss, ipd_gt [nb * nt, nsrc, D], the prediction [nb * nt, nsrc, D] with its tracks in the best permutation),

@@ -21,7 +21,14 @@
 // instantiations, whose bits therefore stay what they were.  Its tile is 10 frames (two of the 5-frame groups IPDnet2's
 // time pooling consumes): 10 frames x 5 channels = 100 KiB of spectra beside the 37 KiB of staging, so the shipped
 // five-microphone array (and six channels) stays in LDS; from 7 channels on a full tile goes through the scratch.
+//
+// A pool of independent streams (fnssl_stream_frontend_centred_pool) is the third compile-time parameter, POOL: workgroup
+// i serves the stream of descriptor i (its own first frame, frame count, window, total length, state row and output row;
+// a fresh stream starts from mu = 0 without a memset), so ONE launch serves any subset of the pool's slots, each at its
+// own position.  Its tile is always the full 10 frames, so the scratch rows keep the spacing the state was sized with.
 #include <cstdint>
+#include <type_traits>
+#include <vector>
 
 #include "host.h"
 #include "frontend_core.h"
@@ -57,6 +64,21 @@ struct StreamParams {
   float* x;                // pair: [nb * np, nframes, 256, 4]; array: [nb, nframes, 256, 2 nch]
 };
 
+// The pool entry (fnssl_stream_frontend_centred_pool): every workgroup is an independent stream and takes what the other
+// instantiations share (first frame, frame count, window position, total length, signal base, state row, output row)
+// from its own descriptor.  The descriptors travel by value in the kernel arguments, so a push makes no host-to-device
+// copy and owns no staging buffer the next push could overwrite; kPoolMaxDesc of them and the shared parameters stay
+// under the 4 KiB the kernel-argument segment holds.
+constexpr int kPoolMaxDesc = FNSSL_STREAM_POOL_MAX_DESC;
+
+struct PoolParams {
+  StreamParams p;          // the shared part: strides, channels, tables, eps, state, x; frame0 / nframes / sample0 / total unused
+  int out_frames;          // frames of one row of x
+  fnssl_stream_pool_desc d[kPoolMaxDesc];
+};
+static_assert(sizeof(fnssl_stream_pool_desc) == 48, "the descriptor is part of the ABI (fnssl/_lib.py mirrors it)");
+static_assert(sizeof(PoolParams) <= 4096, "the descriptors of one launch must fit the kernel-argument segment");
+
 // floats of the fixed LDS carve; the spectra ([tile * nch * 256] float2) follow when they fit
 __host__ __device__ inline int fixed_lds_floats(int nch, int nchain, int tile) {
   const int n = 2 * kTwiddles + kWin + kStreamWaves * 512 + tile * nch + nchain * tile + tile + nchain;
@@ -69,9 +91,28 @@ bool spectra_in_lds(int nch, int nchain, int tile) {
   return fixed_lds_floats(nch, nchain, tile) * sizeof(float) + spectra_bytes(nch, tile) <= kLdsBudget;
 }
 
-template <int ARRAY, int CENTRED>
-__global__ void __launch_bounds__(kStreamThreads) stream_frontend_kernel(const StreamParams p) {
+template <int ARRAY, int CENTRED, int POOL = 0>
+__global__ void __launch_bounds__(kStreamThreads)
+stream_frontend_kernel(const std::conditional_t<POOL != 0, PoolParams, StreamParams> args) {
   constexpr int HOP = CENTRED ? kCentredHop : kHop;
+  const StreamParams& p = [&]() -> const StreamParams& {
+    if constexpr (POOL) return args.p; else return args;
+  }();
+  // what a workgroup works on: shared by the launch, or (POOL) its own descriptor, read once into wave-uniform values
+  int frame0, nframes;
+  long long sample0, sig_total, sig_base, srow, xrow, xframes;
+  bool fresh = false;
+  if constexpr (POOL) {
+    const fnssl_stream_pool_desc& d = args.d[blockIdx.x];
+    frame0 = d.frame0; nframes = d.nframes;
+    sample0 = d.sample0; sig_total = d.total; sig_base = d.sig_offset;
+    srow = d.slot; xrow = d.out_row; xframes = args.out_frames;
+    fresh = d.fresh != 0;
+  } else {
+    frame0 = p.frame0; nframes = p.nframes;
+    sample0 = p.sample0; sig_total = p.total; sig_base = (long long)blockIdx.x * p.sb;
+    srow = blockIdx.x; xrow = blockIdx.x; xframes = p.nframes;
+  }
   extern __shared__ __attribute__((aligned(16))) float smem_stream[];
   float2* tw = reinterpret_cast<float2*>(smem_stream);                  // [kTwiddles]
   float* hann = smem_stream + 2 * kTwiddles;                            // [512]
@@ -82,17 +123,16 @@ __global__ void __launch_bounds__(kStreamThreads) stream_frontend_kernel(const S
   float* mu_s = ca_s + p.tile;                                          // [nchain]: the carried mu
   float2* spec = reinterpret_cast<float2*>(smem_stream + fixed_lds_floats(p.nch, p.nchain, p.tile));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long b = blockIdx.x;
-  if (p.scratch) spec = p.scratch + b * p.tile * p.nch * kNF;
+  if (p.scratch) spec = p.scratch + srow * p.tile * p.nch * kNF;
   fill_tables(tw, hann, tid, kStreamThreads);
-  for (int i = tid; i < p.nchain; i += kStreamThreads) mu_s[i] = p.mu[b * p.nchain + i];
+  for (int i = tid; i < p.nchain; i += kStreamThreads) mu_s[i] = fresh ? 0.f : p.mu[srow * p.nchain + i];   // a fresh slot starts from mu_{-1} = 0
   float2* z = zbuf + wave * 256;
-  const float* ub = p.sig + b * p.sb;
+  const float* ub = p.sig + sig_base;
   const int rowlen = kNF * 2 * p.nch;                                   // array mode: floats of a frame's feature row
-  for (int f0 = 0; f0 < p.nframes; f0 += p.tile) {
-    const int n = min(p.tile, p.nframes - f0);
+  for (int f0 = 0; f0 < nframes; f0 += p.tile) {
+    const int n = min(p.tile, nframes - f0);
     __syncthreads();               // tables and mu_s ready; the previous tile's pack is done with spec / bm_s
-    for (int i = tid; i < n; i += kStreamThreads) ca_s[i] = p.ca[min(p.frame0 + f0 + i, p.sample_length)];
+    for (int i = tid; i < n; i += kStreamThreads) ca_s[i] = p.ca[min(frame0 + f0 + i, p.sample_length)];
     // A: transforms, one wave per (frame, channel)
     for (int w = wave; w < n * p.nch; w += kStreamWaves) {
       const int f = w / p.nch, c = w - f * p.nch;
@@ -100,11 +140,11 @@ __global__ void __launch_bounds__(kStreamThreads) stream_frontend_kernel(const S
         // torch.stft(center=True): the frame starts half a window before 320 t; reflection at both ends as an index fold,
         // in the order of stft_rows_kernel; the host has checked that every folded index lies in the window
         const float* xc = ub + (long long)c * p.sc;
-        const long long n0 = (long long)(p.frame0 + f0 + f) * HOP - kWin / 2;
+        const long long n0 = (long long)(frame0 + f0 + f) * HOP - kWin / 2;
         auto at = [&](long long src) {
           src = src < 0 ? -src : src;
-          src = (p.total >= 0 && src >= p.total) ? 2 * (p.total - 1) - src : src;
-          return xc[(src - p.sample0) * p.sn];
+          src = (sig_total >= 0 && src >= sig_total) ? 2 * (sig_total - 1) - src : src;
+          return xc[(src - sample0) * p.sn];
         };
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -138,7 +178,7 @@ __global__ void __launch_bounds__(kStreamThreads) stream_frontend_kernel(const S
       for (int t = lane; t < n; t += 64) {
         const float* s = msum_s + t * p.nch;
         const float mean = ARRAY ? array_mean(s, 1, p.nch) : pair_mean(s[mi], s[mj]);
-        bm[t] = ema_term(p.cb[min(p.frame0 + f0 + t, p.sample_length)], mean);
+        bm[t] = ema_term(p.cb[min(frame0 + f0 + t, p.sample_length)], mean);
       }
       float m = mu_s[ch];
       ema_scan_tile(bm, ca_s, n, m, lane);
@@ -148,7 +188,7 @@ __global__ void __launch_bounds__(kStreamThreads) stream_frontend_kernel(const S
     // C: features
     if (ARRAY) {
       // the tile's rows [n][256][Re ch 0.. | Im ch 0..] are one contiguous piece of x: float4 stores
-      float* o = p.x + (b * p.nframes + f0) * (long long)rowlen;
+      float* o = p.x + (xrow * xframes + f0) * (long long)rowlen;
       const int total = n * rowlen;                                     // multiple of 4
       for (int e0 = 4 * tid; e0 < total; e0 += 4 * kStreamThreads) {
         float v[4];
@@ -172,12 +212,12 @@ __global__ void __launch_bounds__(kStreamThreads) stream_frontend_kernel(const S
         const float2 xi = spec[((long long)f * p.nch + mi) * kNF + k];
         const float2 xj = spec[((long long)f * p.nch + mj) * kNF + k];
         const float4 o = pair_feature(xi, xj, feature_den(bm_s[ch * p.tile + f], p.eps));
-        reinterpret_cast<float4*>(p.x)[((b * p.nchain + ch) * p.nframes + f0 + f) * kNF + k] = o;
+        reinterpret_cast<float4*>(p.x)[((xrow * p.nchain + ch) * xframes + f0 + f) * kNF + k] = o;
       }
     }
   }
   __syncthreads();
-  for (int i = tid; i < p.nchain; i += kStreamThreads) p.mu[b * p.nchain + i] = mu_s[i];
+  for (int i = tid; i < p.nchain; i += kStreamThreads) p.mu[srow * p.nchain + i] = mu_s[i];
 }
 
 int chains(int nch, int mode, int ch_mode) { return mode == FNSSL_STREAM_ARRAY ? 1 : fnssl_num_pairs(nch, ch_mode); }
@@ -324,6 +364,84 @@ int fnssl_stream_frontend_centred(const float* sig, int nb, int ns, int nch, lon
   p.eps = eps;
   p.x = x;
   return launch_stream(p, nb, true, true, state, "stream_frontend_centred", stream);
+}
+
+int fnssl_stream_frontend_centred_pool(const float* sig, int nslots, int nch, long long sn, long long sc,
+                                       const fnssl_stream_pool_desc* desc, int ndesc, const float* coef_a,
+                                       const float* coef_b, int sample_length, float eps, void* state, size_t state_bytes,
+                                       float* x, int out_rows, int out_frames, void* stream) {
+  FNSSL_REQUIRE(sig && desc && coef_a && coef_b && state && x, "stream_frontend_centred_pool: null pointer");
+  FNSSL_REQUIRE(nslots > 0, "stream_frontend_centred_pool: empty pool (%d slots)", nslots);
+  FNSSL_REQUIRE(nch >= 1 && nch <= kStreamMaxCh, "stream_frontend_centred_pool: 1 to %d channels (%d given)", kStreamMaxCh, nch);
+  FNSSL_REQUIRE(ndesc > 0, "stream_frontend_centred_pool: %d descriptors", ndesc);
+  FNSSL_REQUIRE(out_rows > 0 && out_frames > 0, "stream_frontend_centred_pool: output of %d rows x %d frames", out_rows, out_frames);
+  FNSSL_REQUIRE(sample_length > 0, "stream_frontend_centred_pool: sample_length %d", sample_length);
+  // the state is sized, and its scratch rows are spaced, for full tiles whatever the frame counts of this call
+  const size_t need = fnssl_stream_frontend_centred_state_bytes(nslots, nch, kCentredTile);
+  FNSSL_REQUIRE(state_bytes >= need,
+                "stream_frontend_centred_pool: state of %zu bytes, fnssl_stream_frontend_centred_state_bytes asks for %zu",
+                state_bytes, need);
+  FNSSL_REQUIRE(((uintptr_t)sig | (uintptr_t)coef_a | (uintptr_t)coef_b) % 4 == 0 && (uintptr_t)state % 16 == 0 &&
+                    (uintptr_t)x % 16 == 0,
+                "stream_frontend_centred_pool: misaligned pointer (samples and coefficients 4 bytes, state and output 16)");
+  // every descriptor is checked before the first launch
+  std::vector<char> slot_seen(nslots, 0), row_seen(out_rows, 0);
+  for (int i = 0; i < ndesc; ++i) {
+    const fnssl_stream_pool_desc& d = desc[i];
+    FNSSL_REQUIRE(d.slot >= 0 && d.slot < nslots, "stream_frontend_centred_pool: descriptor %d: slot %d of %d", i, d.slot, nslots);
+    FNSSL_REQUIRE(!slot_seen[d.slot], "stream_frontend_centred_pool: descriptor %d: slot %d appears twice", i, d.slot);
+    slot_seen[d.slot] = 1;
+    FNSSL_REQUIRE(d.out_row >= 0 && d.out_row < out_rows, "stream_frontend_centred_pool: descriptor %d: output row %d of %d", i,
+                  d.out_row, out_rows);
+    FNSSL_REQUIRE(!row_seen[d.out_row], "stream_frontend_centred_pool: descriptor %d: output row %d appears twice", i, d.out_row);
+    row_seen[d.out_row] = 1;
+    FNSSL_REQUIRE(d.nframes > 0 && d.nframes <= out_frames, "stream_frontend_centred_pool: descriptor %d: %d frames in rows of %d",
+                  i, d.nframes, out_frames);
+    FNSSL_REQUIRE(d.frame0 >= 0 && (long long)d.frame0 + d.nframes < (1ll << 31) / kCentredHop,
+                  "stream_frontend_centred_pool: descriptor %d: first frame %d", i, d.frame0);
+    FNSSL_REQUIRE(d.total < 0 || d.total > kWin / 2,
+                  "stream_frontend_centred_pool: descriptor %d: total length %lld is too short for reflect padding of %d", i,
+                  d.total, kWin / 2);
+    const long long last = (long long)d.frame0 + d.nframes - 1;
+    FNSSL_REQUIRE(d.total < 0 || last <= d.total / kCentredHop,
+                  "stream_frontend_centred_pool: descriptor %d: frame %lld does not exist in a signal of total length %lld", i,
+                  last, d.total);
+    FNSSL_REQUIRE(d.ns > 0 && d.sample0 >= 0, "stream_frontend_centred_pool: descriptor %d: window of %d samples at %lld", i, d.ns,
+                  d.sample0);
+    for (long long t = d.frame0; t <= last; ++t) {
+      long long lo, hi;
+      centred_reach(t, d.total, lo, hi);
+      FNSSL_REQUIRE(lo >= d.sample0 && hi < d.sample0 + d.ns,
+                    "stream_frontend_centred_pool: descriptor %d: frame %lld reads samples %lld..%lld, the window holds %lld..%lld",
+                    i, t, lo, hi, d.sample0, d.sample0 + d.ns - 1);
+    }
+  }
+  PoolParams pp{};
+  StreamParams& p = pp.p;
+  p.sig = sig;
+  p.sn = sn; p.sc = sc;
+  p.nch = nch;
+  p.nchain = 1;
+  p.ch_mode = FNSSL_CH_MODE_M;
+  p.tile = kCentredTile;
+  p.sample_length = sample_length;
+  p.ca = coef_a;
+  p.cb = coef_b;
+  p.eps = eps;
+  p.x = x;
+  p.mu = static_cast<float*>(state);
+  const bool in_lds = spectra_in_lds(nch, 1, kCentredTile);
+  p.scratch = in_lds ? nullptr : reinterpret_cast<float2*>(static_cast<char*>(state) + mu_bytes(nslots, 1));
+  pp.out_frames = out_frames;
+  const size_t lds = fixed_lds_floats(nch, 1, kCentredTile) * sizeof(float) + (in_lds ? spectra_bytes(nch, kCentredTile) : 0);
+  hipStream_t st = fnssl::as_stream(stream);
+  fnssl::TimedLaunch tl("stream_frontend_centred_pool", st);
+  for (int i0 = 0; i0 < ndesc; i0 += kPoolMaxDesc) {      // more active slots than one launch carries: more launches
+    const int n = ndesc - i0 < kPoolMaxDesc ? ndesc - i0 : kPoolMaxDesc;
+    for (int i = 0; i < n; ++i) pp.d[i] = desc[i0 + i];
+    FNSSL_TRY(enqueue(st, Kernel{stream_frontend_kernel<1, 1, 1>, kStreamThreads, lds, "stream_frontend_kernel"}, (unsigned)n, pp));
+  }
+  return FNSSL_OK;
 }
 
 }  // extern "C"

@@ -26,6 +26,9 @@
 // depthwise conv in front of x_proj) are DPP row shifts between the 16 lanes of a tile.  DESIGN.md section 10
 // has the measurements that led from one to the other.  The Mamba block's shape constants and the matrix-pipe helpers
 // are in spatialnet_common.h, shared with the block's backward (spatialnet_train.hip).
+#include <cstdint>
+#include <vector>
+
 #include "spatialnet_common.h"
 #include "tuning.h"
 
@@ -1590,6 +1593,65 @@ struct SnWsLayout {               // fnssl_sn_forward
   }
 };
 
+// The carried state of fnssl_sn_forward, in floats: segment-major with the batch inside each segment — the encoder taps
+// [nb][enc_row], then per Mamba block k = 2 l + j the conv taps [nb][conv_row] and the SSM state [nb][ssm_row].  The one
+// place that knows it: fnssl_sn_state_floats sizes it, fnssl_sn_forward carves it, fnssl_sn_state_rows moves rows of it.
+struct SnStateLayout {
+  size_t nb, enc_row, conv_row, ssm_row;
+  int nblocks;                                            // 2 per layer
+  __host__ __device__ SnStateLayout(size_t nb_, size_t enc_row_, size_t conv_row_, size_t ssm_row_, int nblocks_)
+      : nb(nb_), enc_row(enc_row_), conv_row(conv_row_), ssm_row(ssm_row_), nblocks(nblocks_) {}
+  SnStateLayout(const fnssl_sn_net* net, int nb_, int nf)
+      : SnStateLayout((size_t)nb_, (size_t)net->dim_input * nf * (KE - 1), (size_t)(nf / 16) * (KC - 1) * E,
+                      (size_t)(nf / 16) * E * NST, 2 * net->num_layers) {}
+  __host__ __device__ SnStateLayout batch(size_t n) const { return SnStateLayout(n, enc_row, conv_row, ssm_row, nblocks); }
+  __host__ __device__ size_t conv(int k) const { return nb * (enc_row + (size_t)k * (conv_row + ssm_row)); }   // enc at 0
+  __host__ __device__ size_t ssm(int k) const { return conv(k) + nb * conv_row; }
+  __host__ __device__ size_t row_floats() const { return enc_row + (size_t)nblocks * (conv_row + ssm_row); }
+  __host__ __device__ size_t total() const { return nb * row_floats(); }
+  // float i of a batch row's concatenated segments -> its place in the state of batch row b
+  // (32-bit arithmetic inside the row: fnssl_sn_state_rows checks that a row stays below 2^32 floats)
+  __host__ __device__ size_t at(size_t b, unsigned i) const {
+    if (i < enc_row) return b * enc_row + i;
+    i -= (unsigned)enc_row;
+    const unsigned blk = (unsigned)(conv_row + ssm_row);
+    const unsigned k = i / blk;
+    i -= k * blk;
+    return i < conv_row ? conv((int)k) + b * conv_row + i : ssm((int)k) + b * ssm_row + (i - (unsigned)conv_row);
+  }
+};
+static_assert(((KC - 1) * E) % 4 == 0 && (E * NST) % 4 == 0 && (KE - 1) % 4 == 0,
+              "every row of the carried state is a whole number of float4 (sn_state_rows_kernel)");
+
+constexpr int kRowsMax = FNSSL_SN_ROWS_MAX;
+struct SnRowsParams {
+  float4* pool;
+  float4* compact;
+  SnStateLayout lay{0, 0, 0, 0, 0};                       // of one row; .batch(n) places it in a state of n rows
+  unsigned nslots, nrows, row0;                           // this launch serves compact rows row0 .. row0 + gridDim.y - 1
+  int scatter;
+  unsigned short slot[kRowsMax];
+  unsigned char fresh[kRowsMax];
+};
+static_assert(sizeof(SnRowsParams) <= 4096, "the slot list of one launch must fit the kernel-argument segment");
+
+// Rows of the pool's state <-> rows of a compact state, across every segment: blockIdx.y is the compact row, the x
+// dimension strides over the row's float4s.  Consecutive threads copy consecutive float4s of one segment row on both
+// sides (a row's segments are thousands of floats long), so the copy streams; no LDS, no atomics.
+__global__ void __launch_bounds__(256) sn_state_rows_kernel(const SnRowsParams p) {
+  const unsigned a = blockIdx.y;
+  const size_t slot = p.slot[a], crow = p.row0 + a;
+  const bool zero = !p.scatter && p.fresh[a];
+  const SnStateLayout pool = p.lay.batch(p.nslots), comp = p.lay.batch(p.nrows);
+  const unsigned nq = (unsigned)(p.lay.row_floats() / 4);
+  for (unsigned q = blockIdx.x * 256 + threadIdx.x; q < nq; q += gridDim.x * 256) {
+    float4* const pp = p.pool + pool.at(slot, 4 * q) / 4;
+    float4* const cp = p.compact + comp.at(crow, 4 * q) / 4;
+    if (p.scatter) *pp = *cp;
+    else *cp = zero ? make_float4(0.f, 0.f, 0.f, 0.f) : *pp;
+  }
+}
+
 }  // namespace
 
 static bool precision_ok(int p) { return p == FNSSL_PRECISION_FP32 || p == FNSSL_PRECISION_BF16; }
@@ -1829,8 +1891,7 @@ size_t fnssl_sn_forward_workspace_bytes(int nb, int nf, int nt) {
 
 size_t fnssl_sn_state_floats(const fnssl_sn_net* net, int nb, int nf) {
   if (!net || nb <= 0 || nf <= 0) return 0;
-  const size_t nseq = (size_t)nb * (nf / 16);
-  return (size_t)nb * net->dim_input * nf * (KE - 1) + (size_t)net->num_layers * 2 * nseq * (3 * E + E * NST);
+  return SnStateLayout(net, nb, nf).total();
 }
 
 int fnssl_sn_forward(const fnssl_sn_net* net, const float* x, long long x_sb, long long x_sc, long long x_sf,
@@ -1852,11 +1913,10 @@ int fnssl_sn_forward(const fnssl_sn_net* net, const float* x, long long x_sb, lo
   float *const a0 = ws.a0.floats(base), *const a1 = ws.a1.floats(base), *const a2 = ws.a2.floats(base), *const a3 = ws.a3.floats(base);
   float* const mws = ws.mamba.floats(base);
   const size_t mws_bytes = ws.mamba.bytes;
-  const size_t nseq = (size_t)nb * nfc;
+  const SnStateLayout sl(net, nb, nf);
   float* st_enc = state;
-  float* st_m = state ? state + (size_t)nb * net->dim_input * nf * (KE - 1) : nullptr;
-  auto conv_st = [&](int l, int j) { return st_m ? st_m + ((size_t)l * 2 + j) * nseq * (3 * E + E * NST) : nullptr; };
-  auto ssm_st = [&](int l, int j) { return st_m ? conv_st(l, j) + nseq * 3 * E : nullptr; };
+  auto conv_st = [&](int l, int j) { return state ? state + sl.conv(2 * l + j) : nullptr; };
+  auto ssm_st = [&](int l, int j) { return state ? state + sl.ssm(2 * l + j) : nullptr; };
   auto strides = [&](int f, long long& sb, long long& st, long long& sf, int t) {
     sf = H;
     st = (long long)f * H;
@@ -1892,6 +1952,48 @@ int fnssl_sn_forward(const fnssl_sn_net* net, const float* x, long long x_sb, lo
                                   sf2, mws, mws_bytes, prec, stream));
   }
   return fnssl_sn_head(&v3, nb, nt2, nfc, net->wfiP, net->bfiP, net->wdT, net->bd, out, stream);
+}
+
+int fnssl_sn_state_rows(const fnssl_sn_net* net, int nslots, int nf, float* pool_state, int nrows, float* compact_state,
+                        const int* slots, const unsigned char* fresh, int direction, void* stream) {
+  FNSSL_REQUIRE(net && pool_state && compact_state && slots, "sn_state_rows: null pointer");
+  FNSSL_REQUIRE(net->num_layers >= 1 && net->num_layers <= FNSSL_SN_MAX_LAYERS, "sn_state_rows: 1..%d layers", FNSSL_SN_MAX_LAYERS);
+  FNSSL_REQUIRE(net->dim_input > 0 && (nf == 128 || nf == 256), "sn_state_rows: dim_input %d, num_freqs %d (128 or 256)",
+                net->dim_input, nf);
+  FNSSL_REQUIRE(direction == FNSSL_SN_ROWS_GATHER || direction == FNSSL_SN_ROWS_SCATTER, "sn_state_rows: direction %d", direction);
+  FNSSL_REQUIRE(nslots > 0 && nslots <= 65535 && nrows > 0 && nrows <= nslots, "sn_state_rows: %d rows of %d slots", nrows, nslots);
+  FNSSL_REQUIRE((uintptr_t)pool_state % 16 == 0 && (uintptr_t)compact_state % 16 == 0 && pool_state != compact_state,
+                "sn_state_rows: the states must be 16-byte aligned and distinct");
+  std::vector<char> seen(nslots, 0);
+  for (int a = 0; a < nrows; ++a) {
+    FNSSL_REQUIRE(slots[a] >= 0 && slots[a] < nslots, "sn_state_rows: row %d: slot %d of %d", a, slots[a], nslots);
+    FNSSL_REQUIRE(!seen[slots[a]], "sn_state_rows: row %d: slot %d appears twice", a, slots[a]);
+    seen[slots[a]] = 1;
+  }
+  SnRowsParams p{};
+  p.pool = reinterpret_cast<float4*>(pool_state);
+  p.compact = reinterpret_cast<float4*>(compact_state);
+  p.lay = SnStateLayout(net, 1, nf);
+  FNSSL_REQUIRE(p.lay.row_floats() % 4 == 0 && p.lay.enc_row % 4 == 0 && p.lay.row_floats() < (1ull << 32),
+                "sn_state_rows: a row of %zu floats", p.lay.row_floats());
+  p.nslots = (unsigned)nslots;
+  p.nrows = (unsigned)nrows;
+  p.scatter = direction == FNSSL_SN_ROWS_SCATTER;
+  hipStream_t s = fnssl::as_stream(stream);
+  fnssl::TimedLaunch tl(p.scatter ? "sn_state_scatter" : "sn_state_gather", s);
+  // enough workgroups per row to fill the device at one row, at most 8 float4 per thread
+  const size_t nq = p.lay.row_floats() / 4;
+  const unsigned gx = (unsigned)((nq + 256 * 8 - 1) / (256 * 8));
+  for (int r0 = 0; r0 < nrows; r0 += kRowsMax) {
+    const int n = nrows - r0 < kRowsMax ? nrows - r0 : kRowsMax;
+    p.row0 = (unsigned)r0;
+    for (int a = 0; a < n; ++a) {
+      p.slot[a] = (unsigned short)slots[r0 + a];
+      p.fresh[a] = fresh ? fresh[r0 + a] : 0;
+    }
+    FNSSL_TRY(enqueue(s, Kernel{sn_state_rows_kernel, 256, 0, "sn_state_rows_kernel"}, dim3(gx, (unsigned)n), p));
+  }
+  return FNSSL_OK;
 }
 
 }  // extern "C"

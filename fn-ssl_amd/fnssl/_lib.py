@@ -67,6 +67,7 @@ SYMBOLS = [
     "fnssl_doa_metrics_ex", "fnssl_ipd2doa_mse_tracks", "fnssl_ipdnet2_targets",
     "fnssl_stream_frontend_state_bytes", "fnssl_stream_frontend",
     "fnssl_stream_frontend_centred_state_bytes", "fnssl_stream_frontend_centred",
+    "fnssl_stream_frontend_centred_pool", "fnssl_sn_state_rows",
     "fnssl_sn_mamba_backward_workspace_bytes", "fnssl_sn_mamba_backward_chunk", "fnssl_sn_mamba_backward",
     "fnssl_sn_fconv_backward_workspace_bytes", "fnssl_sn_fconv_backward",
     "fnssl_sn_full_backward_workspace_bytes", "fnssl_sn_full_backward",
@@ -128,6 +129,16 @@ class WgradDesc(C.Structure):
                 ("nseq", C.c_longlong), ("nsteps", C.c_int), ("hidden", C.c_int), ("ndir", C.c_int),
                 ("g_wih", C.c_void_p * 2), ("g_whh", C.c_void_p * 2), ("g_bih", C.c_void_p * 2), ("g_bhh", C.c_void_p * 2),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+STREAM_POOL_MAX_DESC = 64                   # include/fnssl.h: FNSSL_STREAM_POOL_MAX_DESC (descriptors of one launch)
+SN_ROWS_GATHER, SN_ROWS_SCATTER = 0, 1      # include/fnssl.h: FNSSL_SN_ROWS_*
+
+
+class StreamPoolDesc(C.Structure):
+    """include/fnssl.h: fnssl_stream_pool_desc, one stream of a fnssl_stream_frontend_centred_pool call (48 bytes)."""
+    _fields_ = [("slot", C.c_int), ("frame0", C.c_int), ("nframes", C.c_int), ("out_row", C.c_int), ("fresh", C.c_int),
+                ("ns", C.c_int), ("sample0", C.c_longlong), ("total", C.c_longlong), ("sig_offset", C.c_longlong)]
 
 
 class BtfView(C.Structure):
@@ -242,6 +253,8 @@ def load():
     lib.fnssl_stream_frontend_centred_state_bytes.argtypes = [i, i, i]
     lib.fnssl_stream_frontend_centred_state_bytes.restype = sz
     lib.fnssl_stream_frontend_centred.argtypes = [vp, i, i, i, ll, ll, ll, ll, i, i, ll, vp, vp, i, f, vp, sz, vp, vp]
+    lib.fnssl_stream_frontend_centred_pool.argtypes = [vp, i, i, ll, ll, C.POINTER(StreamPoolDesc), i, vp, vp, i, f, vp, sz,
+                                                       vp, i, i, vp]
     lib.fnssl_pair_features.argtypes = [vp, vp, vp, vp, i, i, i, i, f, vp, vp, i, vp]
     lib.fnssl_nchw_to_seq.argtypes = [vp, i, i, i, i, vp, vp]
     lib.fnssl_lstm_packed_floats.argtypes = [i, i, i]
@@ -377,6 +390,7 @@ def load():
     lib.fnssl_sn_state_floats.argtypes = [C.POINTER(SnNet), i, i]
     lib.fnssl_sn_state_floats.restype = sz
     lib.fnssl_sn_forward.argtypes = [C.POINTER(SnNet), vp, ll, ll, ll, ll, i, i, i, vp, i, vp, vp, sz, vp]
+    lib.fnssl_sn_state_rows.argtypes = [C.POINTER(SnNet), i, i, vp, i, vp, C.POINTER(C.c_int), C.POINTER(C.c_ubyte), i, vp]
     lib.fnssl_timing_enable.argtypes = [i]
     lib.fnssl_timing_select.argtypes = [C.c_char_p]
     lib.fnssl_timing_collect.argtypes = [i, vp, vp, vp, vp]

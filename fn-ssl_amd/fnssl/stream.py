@@ -16,8 +16,14 @@ transform with hop 320 and reflect padding, normalisation over all channels), fr
 
 ``OnlineLocalizer`` chains a front end to a model's ``forward_stream`` (and optionally a prediction -> DOA callable);
 the Lightning drop-ins of FN-SSL, IPDnet and IPDnet2 expose it as ``predict_stream``.
+
+``StreamPool`` (front end alone: ``PoolFrontEnd``) serves independent IPDnet2 streams, each with its own start, chunk
+sizes and end, with one set of launches per push: ``pool_plan_push`` is the host arithmetic, DESIGN.md 3.3b the design.
 """
 from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -121,32 +127,85 @@ def _stream_coefs(sample_length: int, normalise: bool, device):
 # --------------------------------------------------------------------------- #
 # front ends
 # --------------------------------------------------------------------------- #
+class _TailBuffer:
+    """Device sample storage ``[rows, capacity, nch]`` for streamed front ends.  The rows are grouped into lanes that
+    advance on their own: lane k keeps the samples of its frames not emitted yet (its tail) at
+    ``buf[rows_k, start[k]:start[k] + len[k]]``.  A lock-step front end has one lane of all its rows, a pool one lane per
+    slot.  The capacity follows the largest push, not the length of a stream: an append that does not fit behind a
+    lane's tail moves that tail to the front, and one that does not fit the buffer doubles it (every lane's tail then
+    moves to the front of the new buffer)."""
+
+    def __init__(self, rows: int, nch: int, capacity: int, device, lanes: int = 1):
+        self.buf = torch.empty((rows, capacity, nch), dtype=torch.float32, device=device)
+        self.lane_rows = [slice(None)] if lanes == 1 else [slice(k, k + 1) for k in range(lanes)]
+        self.start = [0] * lanes
+        self.len = [0] * lanes
+
+    @property
+    def capacity(self) -> int:
+        return self.buf.shape[1]
+
+    def window(self, k: int = 0):
+        return self.buf[self.lane_rows[k], self.start[k]:self.start[k] + self.len[k]]
+
+    def _to_front(self, k: int, buf):
+        """Lane k's tail to the front of ``buf`` (the buffer itself, or its larger successor)."""
+        n = self.len[k]
+        if n and (buf is not self.buf or self.start[k]):
+            tail = self.window(k)
+            buf[self.lane_rows[k], :n].copy_(tail.clone() if buf is self.buf else tail)
+        self.start[k] = 0
+
+    def append(self, k: int, chunk):
+        """``chunk [rows of lane k, n, nch]`` (any strides: read in place) behind lane k's tail."""
+        n = chunk.shape[1]
+        if self.start[k] + self.len[k] + n > self.capacity:
+            if self.len[k] + n <= self.capacity:
+                self._to_front(k, self.buf)
+            else:
+                buf = torch.empty((self.buf.shape[0], 2 * (self.len[k] + n), self.buf.shape[2]), dtype=torch.float32,
+                                  device=self.buf.device)
+                for j in range(len(self.len)):
+                    self._to_front(j, buf)
+                self.buf = buf
+        at = self.start[k] + self.len[k]
+        self.buf[self.lane_rows[k], at:at + n].copy_(chunk)
+        self.len[k] += n
+
+    def drop(self, k: int, n: int):
+        """Lane k has consumed its first ``n`` samples: the next append moves what is left."""
+        self.start[k] += n
+        self.len[k] -= n
+
+    def clear(self, k: int):
+        self.start[k] = self.len[k] = 0
+
+
 class _SampleTail:
     """The device-side sample buffer of a streamed front end: the samples of the frames not emitted yet (the tail) in a
-    buffer whose capacity follows the largest push, and the kernel's carried state beside it."""
+    one-lane ``_TailBuffer``, and the kernel's carried state beside it."""
 
     def reset(self):
         """Forget the stream: the next push is sample 0 again (of any batch size, on any device)."""
         self.frames = 0
         self.nb = None
-        self._buf = None                 # [nb, capacity, nch]; the tail is _buf[:, _start:_start + _len]
-        self._start = self._len = 0
+        self._tail = None                # the one-lane _TailBuffer [nb, capacity, nch], allocated by the first push
         self._state = None
 
     @property
     def tail_samples(self) -> int:
         """Samples kept for frames not emitted yet (below the front end's tail bound)."""
-        return self._len
+        return 0 if self._tail is None else self._tail.len[0]
 
     @property
     def buffer_samples(self) -> int:
         """Capacity of the device-side sample buffer, per channel and utterance."""
-        return 0 if self._buf is None else self._buf.shape[1]
+        return 0 if self._tail is None else self._tail.capacity
 
     def _allocate(self, chunk, state_bytes: int, bound: int):
         self.nb = chunk.shape[0]
         self._state = torch.zeros(state_bytes, dtype=torch.uint8, device=chunk.device)      # mu_{-1} = 0
-        self._buf = torch.empty((self.nb, 2 * bound, self.nch), dtype=torch.float32, device=chunk.device)
+        self._tail = _TailBuffer(self.nb, self.nch, 2 * bound, chunk.device)
 
     def _accept(self, chunk):
         """The checks of a pushed chunk; opens the stream on the first one."""
@@ -155,23 +214,12 @@ class _SampleTail:
             raise RuntimeError("fnssl.stream: expected a chunk [nb, n, %d], got %s" % (self.nch, tuple(chunk.shape)))
         if self.nb is None:
             self._open(chunk)
-        elif chunk.shape[0] != self.nb or chunk.device != self._buf.device:
+        elif chunk.shape[0] != self.nb or chunk.device != self._tail.buf.device:
             raise RuntimeError("fnssl.stream: the stream was opened with %d utterances on %s, got %d on %s (reset() first)"
-                               % (self.nb, self._buf.device, chunk.shape[0], chunk.device))
+                               % (self.nb, self._tail.buf.device, chunk.shape[0], chunk.device))
 
     def _append(self, chunk):
-        n = chunk.shape[1]
-        if self._start + self._len + n > self._buf.shape[1]:
-            # move the tail to the front of a buffer that holds it and the chunk; the capacity follows the largest push,
-            # not the length of the stream
-            cap = self._buf.shape[1] if self._len + n <= self._buf.shape[1] else 2 * (self._len + n)
-            buf = self._buf if cap == self._buf.shape[1] else torch.empty((self.nb, cap, self.nch), dtype=torch.float32,
-                                                                           device=self._buf.device)
-            tail = self._buf[:, self._start:self._start + self._len]
-            buf[:, :self._len].copy_(tail.clone() if buf is self._buf else tail)
-            self._buf, self._start = buf, 0
-        self._buf[:, self._start + self._len:self._start + self._len + n].copy_(chunk)   # any strides: read in place
-        self._len += n
+        self._tail.append(0, chunk)
 
 
 class StreamFrontEnd(_SampleTail):
@@ -210,22 +258,22 @@ class StreamFrontEnd(_SampleTail):
     @ops.on_device
     def push(self, chunk):
         self._accept(chunk)
-        emit, keep = plan_push(self._len, chunk.shape[1], self.segment_frames)
+        emit, keep = plan_push(self.tail_samples, chunk.shape[1], self.segment_frames)
         if chunk.shape[1]:
             self._append(chunk)
         x = torch.empty((self.nb * self.nrows, emit, ops.NF, self.width), dtype=torch.float32, device=chunk.device)
         if emit == 0:
             return x
-        win = self._buf[:, self._start:self._start + self._len]
+        win = self._tail.window()
         ca, cb = _stream_coefs(self.sample_length, self.normalise, chunk.device)
         sb, sn, sc = win.stride()
         check(_lib.load().fnssl_stream_frontend(
-            ops._ptr(win), self.nb, self._len, self.nch, sb, sn, sc, STREAM_MODE[self.mode], CH_MODE[self.ch_mode],
+            ops._ptr(win), self.nb, win.shape[1], self.nch, sb, sn, sc, STREAM_MODE[self.mode], CH_MODE[self.ch_mode],
             self.frames, emit, ops._ptr(ca), ops._ptr(cb), self.sample_length, self.eps, ops._ptr(self._state),
             self._state.numel(), ops._ptr(x), ops._stream()), "stream_frontend")
         self.frames += emit
-        self._start += HOP * emit         # consumed samples are dropped: the next append moves what is left
-        self._len = keep
+        self._tail.drop(0, HOP * emit)    # consumed samples are dropped: the next append moves what is left
+        assert self.tail_samples == keep
         return x
 
     def finish(self):
@@ -265,7 +313,7 @@ class CentredStreamFrontEnd(_SampleTail):
     @property
     def samples(self) -> int:
         """Samples pushed so far."""
-        return centred_tail_start(self.frames) + self._len
+        return centred_tail_start(self.frames) + self.tail_samples
 
     def _open(self, chunk):
         nb = chunk.shape[0]
@@ -276,21 +324,20 @@ class CentredStreamFrontEnd(_SampleTail):
 
     def _emit(self, emit: int, total: int):
         """Frames [frames, frames + emit) from the tail; ``total`` < 0 while the stream is open."""
-        dev = self._buf.device
+        dev = self._tail.buf.device
         x = torch.empty((self.nb, emit, ops.NF, self.width), dtype=torch.float32, device=dev)
         if emit == 0:
             return x
-        win = self._buf[:, self._start:self._start + self._len]
+        win = self._tail.window()
         ca, cb = _stream_coefs(self.sample_length, self.normalise, dev)
         sb, sn, sc = win.stride()
         check(_lib.load().fnssl_stream_frontend_centred(
-            ops._ptr(win), self.nb, self._len, self.nch, sb, sn, sc, centred_tail_start(self.frames), self.frames, emit,
+            ops._ptr(win), self.nb, win.shape[1], self.nch, sb, sn, sc, centred_tail_start(self.frames), self.frames, emit,
             total, ops._ptr(ca), ops._ptr(cb), self.sample_length, self.eps, ops._ptr(self._state), self._state.numel(),
             ops._ptr(x), ops._stream()), "stream_frontend_centred")
         drop = centred_tail_start(self.frames + emit) - centred_tail_start(self.frames)
         self.frames += emit
-        self._start += drop               # consumed samples are dropped: the next append moves what is left
-        self._len -= drop
+        self._tail.drop(0, drop)          # consumed samples are dropped: the next append moves what is left
         return x
 
     @ops.on_device
@@ -298,11 +345,11 @@ class CentredStreamFrontEnd(_SampleTail):
         if self.finished:
             raise RuntimeError("fnssl.stream: the stream has been finished (reset() starts a new one)")
         self._accept(chunk)
-        emit, keep = centred_plan_push(self._len, chunk.shape[1], self.segment_frames, self.frames)
+        emit, keep = centred_plan_push(self.tail_samples, chunk.shape[1], self.segment_frames, self.frames)
         if chunk.shape[1]:
             self._append(chunk)
         x = self._emit(emit, -1)
-        assert self._len == keep
+        assert self.tail_samples == keep
         return x
 
     def finish(self):
@@ -312,10 +359,10 @@ class CentredStreamFrontEnd(_SampleTail):
         if total <= WIN // 2:             # the whole-signal transform's own condition (torch.stft's for reflect padding)
             raise RuntimeError("fnssl.stream: signal of %d samples is too short for reflect padding of %d" % (total, WIN // 2))
         emit, _ = centred_plan_finish(total, self.segment_frames, self.frames)
-        with torch.cuda.device(self._buf.device):
+        with torch.cuda.device(self._tail.buf.device):
             x = self._emit(emit, total)
         self.finished = True
-        self._start = self._len = 0
+        self._tail.clear(0)
         return x
 
 
@@ -372,3 +419,315 @@ class OnlineLocalizer:
 
     def finish(self):
         return self._forward(self.frontend.finish())
+
+
+# --------------------------------------------------------------------------- #
+# a pool of independent IPDnet2 streams
+# --------------------------------------------------------------------------- #
+class PoolGroup(NamedTuple):
+    """One group of ``group`` frames that one slot emits in one round of a pool push."""
+    slot: int
+    frame0: int          # absolute index of the group's first frame
+    sample0: int         # absolute index of the first sample the slot still holds = centred_tail_start(frame0)
+    ns: int              # samples it holds from there on
+    total: int           # length of the slot's whole signal where this group needs it (it follows the end), else -1
+    fresh: bool          # the slot's first group: mu and the network state start from zero
+
+
+def pool_plan_push(streams: dict, new: dict, last=(), group: int = 5):
+    """The host arithmetic of ``StreamPool.push``.  ``streams``: slot -> (frames emitted, samples in the tail) of every
+    open, unfinished slot; ``new``: slot -> samples arriving; ``last``: the slots whose signal ends with them.  Returns
+    (rounds, after): in round r every slot that completes more than r groups emits exactly its r-th one (a ``PoolGroup``,
+    in slot order), so every row of a round has the same frame count; ``after``: slot -> (frames, tail) once the push is
+    done (a finished slot keeps no tail).  The groups of a slot are those of ``centred_plan_push`` on the arriving samples
+    and then, for a slot in ``last``, of ``centred_plan_finish`` on the length that is then known.  Nothing is modified;
+    an error (unknown slot, a signal of 256 samples or fewer that ends) is raised before anything is planned."""
+    last = set(last)
+    for slot in list(new) + list(last):
+        if slot not in streams:
+            raise KeyError("pool_plan_push: slot %r is not an open, unfinished stream" % (slot,))
+    per_slot, after = {}, {}
+    for slot in sorted(set(new) | last):
+        frames, tail = streams[slot]
+        n = int(new.get(slot, 0))
+        emit, keep = centred_plan_push(tail, n, group, frames)
+        arrived = centred_tail_start(frames) + tail + n
+        totals = [-1] * (emit // group)
+        if slot in last:
+            if arrived <= WIN // 2:
+                raise RuntimeError("fnssl.stream: slot %d ends after %d samples, too short for reflect padding of %d"
+                                   % (slot, arrived, WIN // 2))
+            more, keep = centred_plan_finish(arrived, group, frames + emit)
+            totals += [arrived] * (more // group)
+        per_slot[slot] = [PoolGroup(slot, f0, centred_tail_start(f0), arrived - centred_tail_start(f0), total, f0 == 0)
+                          for f0, total in ((frames + group * r, t) for r, t in enumerate(totals))]
+        after[slot] = (frames + group * len(totals), keep)
+    depth = max([len(g) for g in per_slot.values()], default=0)
+    rounds = [[g[r] for g in per_slot.values() if len(g) > r] for r in range(depth)]
+    return rounds, after
+
+
+def pool_pack_descriptors(groups, group: int, sig_offset_of):
+    """The ``PoolGroup``s of a round -> the ctypes descriptor array of ``fnssl_stream_frontend_centred_pool`` (row a of
+    the output belongs to groups[a]; the library cuts the array into launches of ``_lib.STREAM_POOL_MAX_DESC``) and the
+    sizes of those launches.  ``sig_offset_of(g)``: floats from the storage's base to the slot's sample ``g.sample0``."""
+    descs = (_lib.StreamPoolDesc * len(groups))()
+    for a, g in enumerate(groups):
+        descs[a] = _lib.StreamPoolDesc(slot=g.slot, frame0=g.frame0, nframes=group, out_row=a, fresh=int(g.fresh), ns=g.ns,
+                                       sample0=g.sample0, total=g.total, sig_offset=sig_offset_of(g))
+    m = _lib.STREAM_POOL_MAX_DESC
+    return descs, [min(m, len(groups) - i) for i in range(0, len(groups), m)]
+
+
+class _Slot:
+    """Host-side position of one stream of a pool."""
+    __slots__ = ("frames", "finished")
+
+    def __init__(self):
+        self.frames, self.finished = 0, False
+
+
+class PoolFrontEnd:
+    """IPDnet2's front end for ``slots`` independent streams: ``open() -> slot``, ``push({slot: chunk [n, nch]}, last=())
+    -> [(groups, x [A, segment_frames, 256, 2 * nch]), ...]``, one entry per round of ``pool_plan_push`` and ONE
+    ``fnssl_stream_frontend_centred_pool`` call each (row a of x holds the frames of groups[a]); ``close(slot)`` frees a
+    slot, whose next stream starts from mu = 0 by descriptor, without a launch; ``reset()`` closes all.  Every slot's
+    emitted frames are the bits of ``ops.preprocess_ipdnet2`` on its own signal, cut to whole groups."""
+
+    def __init__(self, nch: int, slots: int, sample_length: int = CENTRED_SAMPLE_LENGTH, eps: float = 1e-6,
+                 segment_frames: int = 5):
+        if int(slots) <= 0:
+            raise ValueError("PoolFrontEnd: %r slots" % (slots,))
+        if int(nch) < 1:
+            raise ValueError("PoolFrontEnd: %d channels" % int(nch))
+        if int(sample_length) <= 0 or int(segment_frames) <= 0:
+            raise ValueError("PoolFrontEnd: sample_length %r, segment_frames %r" % (sample_length, segment_frames))
+        self.nch, self.nslots = int(nch), int(slots)
+        self.sample_length, self.eps, self.group = int(sample_length), float(eps), int(segment_frames)
+        self.launches = 0                # kernel launches so far (a call cuts its descriptors into launches of 64)
+        self._tails = self._state = None
+        self.reset()
+
+    def reset(self):
+        """Close every slot.  The device buffers stay as they are: nothing is zeroed."""
+        self._slots = {}
+        if self._tails is not None:
+            for k in range(self.nslots):
+                self._tails.clear(k)
+
+    def open(self) -> int:
+        for slot in range(self.nslots):
+            if slot not in self._slots:
+                self._slots[slot] = _Slot()
+                return slot
+        raise RuntimeError("fnssl.stream: all %d slots of the pool are open" % self.nslots)
+
+    def close(self, slot: int):
+        self._stream(slot, finished_ok=True)
+        del self._slots[slot]
+        if self._tails is not None:
+            self._tails.clear(slot)
+
+    def _stream(self, slot, finished_ok=False):
+        st = self._slots.get(slot)
+        if st is None:
+            raise KeyError("fnssl.stream: slot %r of the pool is not open" % (slot,))
+        if st.finished and not finished_ok:
+            raise RuntimeError("fnssl.stream: the stream of slot %d has been finished (close() it; open() starts a new one)" % slot)
+        return st
+
+    def frames(self, slot: int) -> int:
+        """Frames the slot's stream has emitted so far."""
+        return self._stream(slot, True).frames
+
+    def finished(self, slot: int) -> bool:
+        return self._stream(slot, True).finished
+
+    def tail_samples(self, slot: int) -> int:
+        self._stream(slot, True)
+        return 0 if self._tails is None else self._tails.len[slot]
+
+    def samples(self, slot: int) -> int:
+        """Samples pushed into the slot's stream so far (0 once it is finished: its tail is dropped)."""
+        return centred_tail_start(self._stream(slot, True).frames) + self.tail_samples(slot)
+
+    @property
+    def buffer_samples(self) -> int:
+        return 0 if self._tails is None else self._tails.capacity
+
+    @property
+    def device(self):
+        return None if self._tails is None else self._tails.buf.device
+
+    def _allocate(self, device):
+        nbytes = _lib.load().fnssl_stream_frontend_centred_state_bytes(self.nslots, self.nch, 1 << 20)
+        if nbytes == 0:
+            raise RuntimeError("fnssl.stream: no centred streamed front end for %d slots x %d channels" % (self.nslots, self.nch))
+        self._state = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        self._tails = _TailBuffer(self.nslots, self.nch, 2 * centred_tail_bound(self.group), device, lanes=self.nslots)
+
+    def _launch(self, groups):
+        buf = self._tails.buf
+        x = torch.empty((len(groups), self.group, ops.NF, 2 * self.nch), dtype=torch.float32, device=buf.device)
+        sb, sn, sc = buf.stride()
+        base = {g.slot: centred_tail_start(self._slots[g.slot].frames) for g in groups}     # absolute index of the tail's first sample
+
+        def sig_offset(g):
+            at = g.sample0 - base[g.slot]
+            assert at >= 0 and at + g.ns == self._tails.len[g.slot]       # the window lies inside the slot's tail
+            return g.slot * sb + (self._tails.start[g.slot] + at) * sn
+
+        descs, launches = pool_pack_descriptors(groups, self.group, sig_offset)
+        ca, cb = _stream_coefs(self.sample_length, True, buf.device)
+        check(_lib.load().fnssl_stream_frontend_centred_pool(
+            ops._ptr(buf), self.nslots, self.nch, sn, sc, descs, len(groups), ops._ptr(ca), ops._ptr(cb), self.sample_length,
+            self.eps, ops._ptr(self._state), self._state.numel(), ops._ptr(x), len(groups), self.group, ops._stream()),
+            "stream_frontend_centred_pool")
+        self.launches += len(launches)
+        return x
+
+    def push(self, chunks: dict, last=()):
+        last = tuple(last)
+        for slot in list(chunks) + list(last):
+            self._stream(slot)
+        device = self.device
+        for slot, chunk in chunks.items():
+            if not isinstance(chunk, torch.Tensor) or chunk.ndim != 2 or chunk.shape[1] != self.nch:
+                raise RuntimeError("fnssl.stream: slot %d: expected a chunk [n, %d], got %s"
+                                   % (slot, self.nch, tuple(getattr(chunk, "shape", ()))))
+            ops._need_dev(chunk)
+            device = chunk.device if device is None else device
+            if chunk.device != device:
+                raise RuntimeError("fnssl.stream: the pool lives on %s, slot %d was pushed a chunk on %s" % (device, slot, chunk.device))
+        tail = (lambda s: 0) if self._tails is None else (lambda s: self._tails.len[s])
+        streams = {s: (st.frames, tail(s)) for s, st in self._slots.items() if not st.finished}
+        rounds, after = pool_plan_push(streams, {s: c.shape[0] for s, c in chunks.items()}, last, self.group)
+        out = []
+        if device is not None:           # (no device yet: nothing has ever been pushed, and nothing was planned)
+            with torch.cuda.device(device):
+                if self._tails is None:
+                    self._allocate(device)
+                for slot, chunk in chunks.items():
+                    if chunk.shape[0]:
+                        self._tails.append(slot, chunk.unsqueeze(0))
+                out = [(groups, self._launch(groups)) for groups in rounds]
+        for slot, (frames, keep) in after.items():
+            st = self._slots[slot]
+            if slot in last:
+                st.finished = True
+                if self._tails is not None:
+                    self._tails.clear(slot)
+            elif self._tails is not None:
+                self._tails.drop(slot, centred_tail_start(frames) - centred_tail_start(st.frames))
+                assert self._tails.len[slot] == keep
+            st.frames = frames
+        return out
+
+    def finish(self, slot: int):
+        """The slot's signal has ended: a push of no samples with the slot in ``last``."""
+        return self.push({}, last=(slot,))
+
+
+class StreamPool:
+    """``slots`` independent IPDnet2 streams on one device, each with its own sample tail, frame count, normalisation
+    ``mu``, network state and end; ``model`` is an ``OnlineSpatialNet`` (fp32 or bf16) in eval mode.
+
+    ``open() -> slot``; ``push({slot: chunk [n, nch]}, last=()) -> {slot: (pred [g, 512, nmic - 1, 2], doa)}`` for the
+    slots that completed g >= 1 groups of 5 frames (n is free per slot, 0 allowed; slots in ``last`` end with their chunk
+    and also emit what only the known end completes); ``finish(slot)``; ``close(slot)`` frees a slot, whose next
+    ``open()`` starts from zero without a launch; ``reset()`` closes all.  ``doa`` is None without ``localize``, else a
+    list with one entry per group: what ``localize(pred [A, 1, 512, nmic - 1, 2])`` returned for the A rows of a network
+    call, narrowed to this stream along ``localize_batch_dim`` (1: the layout of ``PredDOA._search``).
+
+    The device work of a push is per ROUND (a real-time push is one round; a catch-up push that completes several groups
+    of a slot takes one per group), whatever the number of slots: one ``fnssl_stream_frontend_centred_pool`` call
+    (``PoolFrontEnd``), ONE ``fnssl_sn_forward`` on the round's rows — in place on the pool's state when they are all
+    slots in order and none is fresh, otherwise on a compact state between one gather and one scatter
+    (``fnssl_sn_state_rows``) —, and ``localize``.  Fresh rows (a stream's first group) ride in the carried rows' call:
+    the gather hands them zeros, and a zeroed state under ``carry=True`` gives the bits of ``forward_stream(x, None)``, in
+    fp32 and in bf16 (DESIGN 3.3b; tests/test_gpu_stream_pool.py::test_first_group_finding)."""
+
+    def __init__(self, model, nch: int, slots: int, localize=None, sample_length: int = CENTRED_SAMPLE_LENGTH,
+                 eps: float = 1e-6, localize_batch_dim: int = 1):
+        if not hasattr(model, "time_compression_ratio") or not hasattr(model, "device_net"):
+            raise ValueError("StreamPool: the model must be an OnlineSpatialNet (IPDnet2), got %s" % type(model).__name__)
+        self.frontend = PoolFrontEnd(nch, slots, sample_length, eps, model.time_compression_ratio)
+        if model.encoder.in_channels != 2 * self.frontend.nch:
+            raise ValueError("StreamPool: the front end emits %d feature channels, the network takes %d"
+                             % (2 * self.frontend.nch, model.encoder.in_channels))
+        self.model, self.localize, self.localize_batch_dim = model, localize, int(localize_batch_dim)
+        self.nslots = self.frontend.nslots
+        # as OnlineLocalizer: a zero-frame call runs forward_stream's checks of the module (eval mode) and stops at its
+        # shape check, so a module in train() mode fails here and not at the first completed group
+        try:
+            model.forward_stream(torch.zeros((1, 2 * self.frontend.nch, ops.NF, 0)))
+        except RuntimeError as e:
+            if "chunks must be positive multiples" not in str(e):
+                raise
+        self.in_place = True             # False: every call of the network goes through gather and scatter (tests)
+        self.gathers = self.scatters = 0
+        self._dn = self._net_state = self._compact = None
+
+    def open(self) -> int:
+        return self.frontend.open()
+
+    def close(self, slot: int):
+        self.frontend.close(slot)
+
+    def reset(self):
+        self.frontend.reset()
+
+    def _rows(self, slots, direction, fresh=None):
+        n = len(slots)
+        check(_lib.load().fnssl_sn_state_rows(
+            C.byref(self._dn.net), self.nslots, self._dn.num_freqs, ops._ptr(self._net_state), n, ops._ptr(self._compact),
+            (C.c_int * n)(*slots), None if fresh is None else (C.c_ubyte * n)(*[int(f) for f in fresh]), direction,
+            ops._stream()), "sn_state_rows")
+        if direction == _lib.SN_ROWS_GATHER:
+            self.gathers += 1
+        else:
+            self.scatters += 1
+
+    def _network(self, x, groups):
+        """The network on a round's rows ``x [n, 5, 256, 2 nch]``.  In place on the pool's state when the rows are all
+        slots in order and all carried (or all fresh: ``carry=False`` reads no state); else on the compact state: gather
+        (zeros for fresh rows; skipped when all rows are fresh), forward, scatter."""
+        # fetched per call, as forward_stream does: weights or a dtype changed since the last push are picked up (the
+        # model re-packs them when its parameters changed), while the carried state keeps its layout
+        self._dn = self.model.device_net(x.device)
+        if self._net_state is None:
+            self._net_state = self._dn.new_state(self.nslots)
+        slots = [g.slot for g in groups]
+        fresh = [g.fresh for g in groups]
+        carry = not all(fresh)
+        xv = x.permute(0, 3, 2, 1)                                        # a view: nothing is moved
+        if self.in_place and slots == list(range(self.nslots)) and (not carry or not any(fresh)):
+            return self._dn.forward(xv, state=self._net_state, carry=carry)
+        if self._compact is None:        # as large as the pool's state: holds the compact state of any number of rows
+            self._compact = torch.empty_like(self._net_state)
+        if carry:
+            self._rows(slots, _lib.SN_ROWS_GATHER, fresh)
+        nfloats = _lib.load().fnssl_sn_state_floats(C.byref(self._dn.net), len(slots), self._dn.num_freqs)
+        pred = self._dn.forward(xv, state=self._compact[:nfloats], carry=carry)
+        self._rows(slots, _lib.SN_ROWS_SCATTER)
+        return pred
+
+    @torch.no_grad()
+    def push(self, chunks: dict, last=()):
+        out = {}
+        for groups, x in self.frontend.push(chunks, last):
+            with torch.cuda.device(x.device):
+                pred = self._network(x, groups)
+                doa = self.localize(pred) if self.localize is not None else None
+            for a, g in enumerate(groups):
+                preds, doas = out.setdefault(g.slot, ([], []))
+                preds.append(pred[a])
+                if doa is not None:
+                    one = lambda t: t.narrow(self.localize_batch_dim, a, 1)   # noqa: E731
+                    doas.append(tuple(one(t) for t in doa) if isinstance(doa, (tuple, list)) else one(doa))
+        return {slot: (torch.cat(preds, dim=0), doas if self.localize is not None else None)
+                for slot, (preds, doas) in out.items()}
+
+    def finish(self, slot: int):
+        """``push({slot: no samples}, last=(slot,))``: the groups only the known end completes."""
+        return self.push({}, last=(slot,))

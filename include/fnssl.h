@@ -827,6 +827,37 @@ int fnssl_stream_frontend_centred(const float* sig, int nb, int ns, int nch, lon
                                   const float* coef_b, int sample_length, float eps, void* state, size_t state_bytes,
                                   float* x, void* stream);
 
+/* ---- a pool of independent IPDnet2 streams (additive: FNSSL_ABI_VERSION stays 19) -----------------------------------------
+ * fnssl_stream_frontend_centred for any subset of the slots of a pool in ONE launch: workgroup i serves descriptor i, a
+ * stream with its own position.  The descriptors travel by value in the kernel arguments (no host-to-device copy, no
+ * staging buffer); one launch carries FNSSL_STREAM_POOL_MAX_DESC of them, more descriptors take more launches.
+ *   slot        row of the state (mu, scratch) the stream owns, < nslots; no slot twice in a call
+ *   frame0      absolute index of the first frame; nframes > 0 frames, <= out_frames
+ *   out_row     row of x the frames are written to, < out_rows; no row twice in a call
+ *   fresh       != 0: the slot starts a stream here; mu starts from 0 whatever the state row holds (a reset costs nothing)
+ *   ns          samples of the window
+ *   sample0     absolute index of the window's first sample;  total: as fnssl_stream_frontend_centred
+ *   sig_offset  floats from `sig` to the window's first sample of channel 0 */
+#define FNSSL_STREAM_POOL_MAX_DESC 64
+typedef struct {
+  int slot, frame0, nframes, out_row, fresh, ns;
+  long long sample0, total, sig_offset;
+} fnssl_stream_pool_desc;
+
+/*
+ *   sig          base of the sample storage; sample sample0 + n of channel c of descriptor d at
+ *                sig[d.sig_offset + n*sn + c*sc], n < d.ns
+ *   state        fnssl_stream_frontend_centred_state_bytes(nslots, nch, >= 10) bytes, indexed by SLOT: mu[nslots], then
+ *                the per-slot scratch for more than 6 channels; rows of slots not named are not touched
+ *   x            [out_rows, out_frames, 256, 2 * nch]; descriptor d writes its nframes frames at the start of row d.out_row
+ * Array normalisation and the centred hop-320 transform only.  Every descriptor is validated before the first launch, by the
+ * rules of fnssl_stream_frontend_centred; FNSSL_E_INVALID names the offending descriptor.
+ */
+int fnssl_stream_frontend_centred_pool(const float* sig, int nslots, int nch, long long sn, long long sc,
+                                       const fnssl_stream_pool_desc* desc, int ndesc, const float* coef_a,
+                                       const float* coef_b, int sample_length, float eps, void* state, size_t state_bytes,
+                                       float* x, int out_rows, int out_frames, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* IPDnet head (next row 8f-3): causal 3x3 Conv2d + time pooling              */
 /* ------------------------------------------------------------------------- */
@@ -1187,6 +1218,21 @@ size_t fnssl_sn_state_floats(const fnssl_sn_net* net, int nb, int nf);
 int fnssl_sn_forward(const fnssl_sn_net* net, const float* x, long long x_sb, long long x_sc, long long x_sf,
                      long long x_st, int nb, int nf, int nt, float* state, int carry, float* out,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- the carried state on a subset of its rows (additive: FNSSL_ABI_VERSION stays 19) -------------------------------------
+ * The state of fnssl_sn_forward is segment-major with the batch inside each segment: the encoder taps [nb][cin * nf * 4],
+ * then per layer and Mamba block the conv taps [nb * nf/16][3][192] and the SSM state [nb * nf/16][192][16].  A pool of
+ * nslots streams keeps ONE such state (batch nslots); a call of the network on `nrows` of them runs on a compact state
+ * (batch nrows) whose row a is the pool's row slots[a].  One launch moves the rows across all 1 + 4 L segments:
+ *   FNSSL_SN_ROWS_GATHER    compact row a <- pool row slots[a], or zeros where fresh[a] != 0 (fresh may be NULL)
+ *   FNSSL_SN_ROWS_SCATTER   pool row slots[a] <- compact row a (fresh is ignored)
+ * slots (host memory, distinct, each < nslots) go by value in the kernel arguments, FNSSL_SN_ROWS_MAX per launch.  A pure
+ * float4 copy: rows of slots not listed are not touched.  Both states 16-byte aligned and distinct. */
+#define FNSSL_SN_ROWS_GATHER 0
+#define FNSSL_SN_ROWS_SCATTER 1
+#define FNSSL_SN_ROWS_MAX 256
+int fnssl_sn_state_rows(const fnssl_sn_net* net, int nslots, int nf, float* pool_state, int nrows, float* compact_state,
+                        const int* slots, const unsigned char* fresh, int direction, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Measurement hooks (bench.py: per-kernel HIP-event timing on the launch stream) */
