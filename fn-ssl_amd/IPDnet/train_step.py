@@ -144,6 +144,15 @@ class MyModel(_Base):
         pred, _ = state.push(chunk.permute(0, 2, 1).to(self.dev))
         return (None if pred is None else pred[0]), state
 
+    def open_stream_pool(self, nch: int, slots: int, localize: bool = False):
+        """A ``fnssl.stream.LstmStreamPool`` on ``self.arch``: ``slots`` independent streams of ``nch`` microphones, each
+        with its own start and chunk sizes, served by one front-end launch and one network call per push
+        (``pool.open()``, ``pool.push({slot: chunk [n, nch]})``, ``pool.close(slot)``).  ``localize=True`` maps every
+        prediction to ``get_metric._localize``'s (DOA, VAD), narrowed to the slot's row."""
+        from fnssl import stream
+        return stream.LstmStreamPool(self.arch, nch, slots, localize=self.get_metric._localize if localize else None,
+                                     sample_length=280, eps=1e-6)
+
     def cal_loss(self, pred_batch=None, gt_batch=None, batch_idx=None):
         """Frame-level PIT-MSE (:196-206) — one HIP kernel that emits its own gradient; a scalar with a ``grad_fn``."""
         return ipdnet_step.PitMSE.apply(pred_batch, gt_batch[1])

@@ -26,6 +26,8 @@
 // i serves the stream of descriptor i (its own first frame, frame count, window, total length, state row and output row;
 // a fresh stream starts from mu = 0 without a memset), so ONE launch serves any subset of the pool's slots, each at its
 // own position.  Its tile is always the full 10 frames, so the scratch rows keep the spacing the state was sized with.
+// fnssl_stream_frontend_pool is the same for the hop-256 models (<0, 0, 1> FN-SSL pairs, <1, 0, 1> IPDnet arrays), with
+// the full 12-frame tile: a descriptor's np pair rows follow each other in x (row out_row * np + pair).
 #include <cstdint>
 #include <type_traits>
 #include <vector>
@@ -440,6 +442,83 @@ int fnssl_stream_frontend_centred_pool(const float* sig, int nslots, int nch, lo
     const int n = ndesc - i0 < kPoolMaxDesc ? ndesc - i0 : kPoolMaxDesc;
     for (int i = 0; i < n; ++i) pp.d[i] = desc[i0 + i];
     FNSSL_TRY(enqueue(st, Kernel{stream_frontend_kernel<1, 1, 1>, kStreamThreads, lds, "stream_frontend_kernel"}, (unsigned)n, pp));
+  }
+  return FNSSL_OK;
+}
+
+int fnssl_stream_frontend_pool(const float* sig, int nslots, int nch, long long sn, long long sc, int mode, int ch_mode,
+                               const fnssl_stream_pool_desc* desc, int ndesc, const float* coef_a, const float* coef_b,
+                               int sample_length, float eps, void* state, size_t state_bytes, float* x, int out_rows,
+                               int out_frames, void* stream) {
+  FNSSL_REQUIRE(sig && desc && coef_a && coef_b && state && x, "stream_frontend_pool: null pointer");
+  FNSSL_REQUIRE(mode == FNSSL_STREAM_PAIR || mode == FNSSL_STREAM_ARRAY, "stream_frontend_pool: mode %d", mode);
+  FNSSL_REQUIRE(mode == FNSSL_STREAM_ARRAY || ch_mode == FNSSL_CH_MODE_M || ch_mode == FNSSL_CH_MODE_MM,
+                "stream_frontend_pool: ch_mode %d", ch_mode);
+  FNSSL_REQUIRE(nslots > 0, "stream_frontend_pool: empty pool (%d slots)", nslots);
+  FNSSL_REQUIRE(nch >= (mode == FNSSL_STREAM_PAIR ? 2 : 1), "stream_frontend_pool: %d channels (pair mode needs >= 2)", nch);
+  FNSSL_REQUIRE(nch <= kStreamMaxCh, "stream_frontend_pool: at most %d channels (%d given)", kStreamMaxCh, nch);
+  FNSSL_REQUIRE(ndesc > 0, "stream_frontend_pool: %d descriptors", ndesc);
+  FNSSL_REQUIRE(out_rows > 0 && out_frames > 0, "stream_frontend_pool: output of %d rows x %d frames", out_rows, out_frames);
+  FNSSL_REQUIRE(sample_length > 0, "stream_frontend_pool: sample_length %d", sample_length);
+  const bool array = mode == FNSSL_STREAM_ARRAY;
+  const int nchain = chains(nch, mode, ch_mode);
+  // the state is sized, and its scratch rows are spaced, for full tiles whatever the frame counts of this call
+  const size_t need = fnssl_stream_frontend_state_bytes(nslots, nch, mode, ch_mode, kStreamTile);
+  FNSSL_REQUIRE(state_bytes >= need, "stream_frontend_pool: state of %zu bytes, fnssl_stream_frontend_state_bytes asks for %zu",
+                state_bytes, need);
+  FNSSL_REQUIRE(((uintptr_t)sig | (uintptr_t)coef_a | (uintptr_t)coef_b) % 4 == 0 && (uintptr_t)state % 16 == 0 &&
+                    (uintptr_t)x % 16 == 0,
+                "stream_frontend_pool: misaligned pointer (samples and coefficients 4 bytes, state and output 16)");
+  // every descriptor is checked before the first launch
+  std::vector<char> slot_seen(nslots, 0), row_seen(out_rows, 0);
+  for (int i = 0; i < ndesc; ++i) {
+    const fnssl_stream_pool_desc& d = desc[i];
+    FNSSL_REQUIRE(d.slot >= 0 && d.slot < nslots, "stream_frontend_pool: descriptor %d: slot %d of %d", i, d.slot, nslots);
+    FNSSL_REQUIRE(!slot_seen[d.slot], "stream_frontend_pool: descriptor %d: slot %d appears twice", i, d.slot);
+    slot_seen[d.slot] = 1;
+    FNSSL_REQUIRE(d.out_row >= 0 && d.out_row < out_rows, "stream_frontend_pool: descriptor %d: output row %d of %d", i,
+                  d.out_row, out_rows);
+    FNSSL_REQUIRE(!row_seen[d.out_row], "stream_frontend_pool: descriptor %d: output row %d appears twice", i, d.out_row);
+    row_seen[d.out_row] = 1;
+    FNSSL_REQUIRE(d.nframes > 0 && d.nframes <= out_frames, "stream_frontend_pool: descriptor %d: %d frames in rows of %d", i,
+                  d.nframes, out_frames);
+    FNSSL_REQUIRE(d.frame0 >= 0 && (long long)d.frame0 + d.nframes < (1ll << 31),
+                  "stream_frontend_pool: descriptor %d: first frame %d", i, d.frame0);
+    FNSSL_REQUIRE(d.sample0 == (long long)kHop * d.frame0,
+                  "stream_frontend_pool: descriptor %d: the window starts at sample %lld, frame %d starts at %lld", i, d.sample0,
+                  d.frame0, (long long)kHop * d.frame0);
+    FNSSL_REQUIRE(d.total < 0, "stream_frontend_pool: descriptor %d: total length %lld (the hop-256 transform has no end "
+                  "reflection: pass a negative total)", i, d.total);
+    FNSSL_REQUIRE((long long)d.ns >= (long long)(d.nframes - 1) * kHop + kWin,
+                  "stream_frontend_pool: descriptor %d: %d frames need %lld samples, the window has %d", i, d.nframes,
+                  (long long)(d.nframes - 1) * kHop + kWin, d.ns);
+  }
+  PoolParams pp{};
+  StreamParams& p = pp.p;
+  p.sig = sig;
+  p.sn = sn; p.sc = sc;
+  p.nch = nch;
+  p.nchain = nchain;
+  p.ch_mode = ch_mode;
+  p.tile = kStreamTile;
+  p.sample_length = sample_length;
+  p.ca = coef_a;
+  p.cb = coef_b;
+  p.eps = eps;
+  p.x = x;
+  p.mu = static_cast<float*>(state);
+  const bool in_lds = spectra_in_lds(nch, nchain, kStreamTile);
+  p.scratch = in_lds ? nullptr : reinterpret_cast<float2*>(static_cast<char*>(state) + mu_bytes(nslots, nchain));
+  pp.out_frames = out_frames;
+  const size_t lds = fixed_lds_floats(nch, nchain, kStreamTile) * sizeof(float) + (in_lds ? spectra_bytes(nch, kStreamTile) : 0);
+  hipStream_t st = fnssl::as_stream(stream);
+  fnssl::TimedLaunch tl("stream_frontend_pool", st);
+  for (int i0 = 0; i0 < ndesc; i0 += kPoolMaxDesc) {      // more active slots than one launch carries: more launches
+    const int n = ndesc - i0 < kPoolMaxDesc ? ndesc - i0 : kPoolMaxDesc;
+    for (int i = 0; i < n; ++i) pp.d[i] = desc[i0 + i];
+    FNSSL_TRY(fnssl::with_bool(array, [&](auto ARRAY) {
+      return enqueue(st, Kernel{stream_frontend_kernel<ARRAY, 0, 1>, kStreamThreads, lds, "stream_frontend_kernel"}, (unsigned)n, pp);
+    }));
   }
   return FNSSL_OK;
 }

@@ -171,9 +171,10 @@ int fnssl_lstm_pack(const float* w_ih, const float* w_hh, const float* b_ih, con
 // ---- the forward workspace -------------------------------------------------------------------------------------------
 // cell state at the front (a multiple of 256 bytes): one float4 per (lane, slice) per wave; the tail workgroup is padded to a
 // whole workgroup (<= 16 waves), which the kSpareTasks spare slots per direction cover for every variant (cell_record)
+static size_t cell_group_bytes(int hidden) { return (size_t)(hidden / 16) * 64 * 16; }   // one task's record, one direction
 static size_t cell_scratch_bytes(int nseq, int hidden, int ndir) {
   const size_t tasks = (size_t)(nseq + 15) / 16 + kSpareTasks;
-  return tasks * ndir * (size_t)(hidden / 16) * 64 * 16 + 256;
+  return tasks * ndir * cell_group_bytes(hidden) + 256;
 }
 // the pair- / quad-interleaved copy of a weight stream (lstm_static3.h, lstm_static4.h): room for the largest stream of the
 // hidden size (c0 + c2 <= 272 channels) per direction
@@ -219,6 +220,13 @@ static LstmWsLayout lstm_ws_layout(int nseq, int hidden, int ndir, int precision
   L.carry = {L.cluster.end(), (precision == FNSSL_PRECISION_FP32 && hidden == 256 && ndir == 1) ? L.cell.bytes : 0};
   L.total = L.carry.end();
   return L;
+}
+
+// what a pool of streams moves per 16-sequence group of a one-direction streaming workspace: the record cell_scratch_bytes
+// counts per task, for the hidden sizes check_fwd_desc admits
+int fnssl_lstm_cell_group_floats(int hidden) {
+  const bool streams = hidden == 16 || hidden == 32 || hidden == 64 || hidden == 128 || hidden == 256;
+  return streams ? (int)(cell_group_bytes(hidden) / sizeof(float)) : 0;
 }
 
 int fnssl_lstm_plan_rounds(int hidden, int nseq, int ndir, int ncu, int* waves_per_wg, int cap) {

@@ -68,6 +68,7 @@ SYMBOLS = [
     "fnssl_stream_frontend_state_bytes", "fnssl_stream_frontend",
     "fnssl_stream_frontend_centred_state_bytes", "fnssl_stream_frontend_centred",
     "fnssl_stream_frontend_centred_pool", "fnssl_sn_state_rows",
+    "fnssl_stream_frontend_pool", "fnssl_state_rows", "fnssl_lstm_cell_group_floats",
     "fnssl_sn_mamba_backward_workspace_bytes", "fnssl_sn_mamba_backward_chunk", "fnssl_sn_mamba_backward",
     "fnssl_sn_fconv_backward_workspace_bytes", "fnssl_sn_fconv_backward",
     "fnssl_sn_full_backward_workspace_bytes", "fnssl_sn_full_backward",
@@ -139,6 +140,14 @@ class StreamPoolDesc(C.Structure):
     """include/fnssl.h: fnssl_stream_pool_desc, one stream of a fnssl_stream_frontend_centred_pool call (48 bytes)."""
     _fields_ = [("slot", C.c_int), ("frame0", C.c_int), ("nframes", C.c_int), ("out_row", C.c_int), ("fresh", C.c_int),
                 ("ns", C.c_int), ("sample0", C.c_longlong), ("total", C.c_longlong), ("sig_offset", C.c_longlong)]
+
+
+STATE_ROWS_MAX_SEGS = 8                     # include/fnssl.h: FNSSL_STATE_ROWS_MAX_SEGS
+
+
+class StateSeg(C.Structure):
+    """include/fnssl.h: fnssl_state_seg, one batch-leading tensor of a carried state and its compact counterpart."""
+    _fields_ = [("pool", C.c_void_p), ("compact", C.c_void_p), ("row_floats", C.c_longlong)]
 
 
 class BtfView(C.Structure):
@@ -255,6 +264,9 @@ def load():
     lib.fnssl_stream_frontend_centred.argtypes = [vp, i, i, i, ll, ll, ll, ll, i, i, ll, vp, vp, i, f, vp, sz, vp, vp]
     lib.fnssl_stream_frontend_centred_pool.argtypes = [vp, i, i, ll, ll, C.POINTER(StreamPoolDesc), i, vp, vp, i, f, vp, sz,
                                                        vp, i, i, vp]
+    lib.fnssl_stream_frontend_pool.argtypes = [vp, i, i, ll, ll, i, i, C.POINTER(StreamPoolDesc), i, vp, vp, i, f, vp, sz, vp,
+                                               i, i, vp]
+    lib.fnssl_state_rows.argtypes = [C.POINTER(StateSeg), i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_ubyte), i, vp]
     lib.fnssl_pair_features.argtypes = [vp, vp, vp, vp, i, i, i, i, f, vp, vp, i, vp]
     lib.fnssl_nchw_to_seq.argtypes = [vp, i, i, i, i, vp, vp]
     lib.fnssl_lstm_packed_floats.argtypes = [i, i, i]
@@ -294,6 +306,7 @@ def load():
     lib.fnssl_lstm_backward.argtypes = [C.POINTER(LstmBwdDesc), vp]
     lib.fnssl_lstm_backward_plan.argtypes = [C.POINTER(LstmBwdDesc), C.POINTER(C.c_int)]
     lib.fnssl_lstm_backward_status.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_uint)]
+    lib.fnssl_lstm_cell_group_floats.argtypes = [i]
     lib.fnssl_lstm_plan_rounds.argtypes = [i, i, i, i, vp, i]
     lib.fnssl_lstm_plan.argtypes = [C.POINTER(LstmDesc), vp, vp]
     lib.fnssl_mfma_f32_peak.argtypes = [vp, sz, i, i, vp, vp]

@@ -19,6 +19,8 @@ the Lightning drop-ins of FN-SSL, IPDnet and IPDnet2 expose it as ``predict_stre
 
 ``StreamPool`` (front end alone: ``PoolFrontEnd``) serves independent IPDnet2 streams, each with its own start, chunk
 sizes and end, with one set of launches per push: ``pool_plan_push`` is the host arithmetic, DESIGN.md 3.3b the design.
+``LstmStreamPool`` (front end alone: ``HopPoolFrontEnd``) is the same for the hop-256 models, FN-SSL and IPDnet, whose
+carried state is ``forward_stream``'s dict of tensors and LSTM workspaces: ``hop_pool_plan_push``, DESIGN.md 3.3c.
 """
 from __future__ import annotations
 
@@ -731,3 +733,319 @@ class StreamPool:
     def finish(self, slot: int):
         """``push({slot: no samples}, last=(slot,))``: the groups only the known end completes."""
         return self.push({}, last=(slot,))
+
+
+# --------------------------------------------------------------------------- #
+# a pool of independent hop-256 streams: FN-SSL / IPDnet
+# --------------------------------------------------------------------------- #
+def hop_pool_plan_push(streams: dict, new: dict, group: int = 12):
+    """The host arithmetic of ``HopPoolFrontEnd.push``.  ``streams``: slot -> (frames emitted, samples in the tail) of every
+    open slot; ``new``: slot -> samples arriving.  Returns (rounds, after) as ``pool_plan_push`` does: in round r every slot
+    that completes more than r groups emits its r-th one (a ``PoolGroup`` with ``total = -1``, in slot order); ``after``:
+    slot -> (frames, tail) once the push is done, which is ``plan_push`` per slot.  There is no ``last``: a hop-256 frame
+    depends on its own samples only, so the end of a stream completes nothing (``StreamFrontEnd.finish``).  Nothing is
+    modified; an unknown slot raises before anything is planned."""
+    for slot in new:
+        if slot not in streams:
+            raise KeyError("hop_pool_plan_push: slot %r is not an open stream" % (slot,))
+    per_slot, after = {}, {}
+    for slot in sorted(new):
+        frames, tail = streams[slot]
+        have = tail + int(new[slot])
+        emit, keep = plan_push(tail, int(new[slot]), group)
+        per_slot[slot] = [PoolGroup(slot, f0, HOP * f0, have - HOP * (f0 - frames), -1, f0 == 0)
+                          for f0 in range(frames, frames + emit, group)]
+        after[slot] = (frames + emit, keep)
+    depth = max([len(g) for g in per_slot.values()], default=0)
+    rounds = [[g[r] for g in per_slot.values() if len(g) > r] for r in range(depth)]
+    return rounds, after
+
+
+class HopPoolFrontEnd(PoolFrontEnd):
+    """The front end of FN-SSL (mode ``'pair'``) / IPDnet (mode ``'array'``) for ``slots`` independent streams, with the
+    surface of ``PoolFrontEnd`` (no ``last`` / ``finish``: the end of a hop-256 stream completes nothing): ``push({slot:
+    chunk [n, nch]}) -> [(groups, x), ...]``, one entry per round of ``hop_pool_plan_push`` and ONE
+    ``fnssl_stream_frontend_pool`` call each.  The frames of groups[a] are rows ``a * nrows .. a * nrows + nrows - 1`` of
+    ``x [A * nrows, segment_frames, 256, 4]`` (pair mode, ``nrows`` = microphone pairs) or row a of ``x [A, segment_frames,
+    256, 2 * nch]`` (array mode).  Every slot's emitted frames are the bits of ``ops.pair_features`` /
+    ``ops.array_features`` on its own signal."""
+
+    def __init__(self, mode: str, nch: int, slots: int, ch_mode: str = "MM", sample_length: int = None, eps: float = 1e-6,
+                 segment_frames: int = 12):
+        if mode not in STREAM_MODE:
+            raise ValueError("HopPoolFrontEnd: mode must be 'pair' or 'array', got %r" % (mode,))
+        if mode == "pair" and ch_mode not in CH_MODE:
+            raise ValueError("HopPoolFrontEnd: ch_mode must be 'M' or 'MM', got %r" % (ch_mode,))
+        if int(slots) <= 0:
+            raise ValueError("HopPoolFrontEnd: %r slots" % (slots,))
+        if int(nch) < (2 if mode == "pair" else 1):
+            raise ValueError("HopPoolFrontEnd: %d channels" % int(nch))
+        sample_length = DEFAULT_SAMPLE_LENGTH[mode] if sample_length is None else sample_length
+        if int(sample_length) <= 0 or int(segment_frames) <= 0:
+            raise ValueError("HopPoolFrontEnd: sample_length %r, segment_frames %r" % (sample_length, segment_frames))
+        self.mode, self.ch_mode = mode, ch_mode if mode == "pair" else "M"
+        self.nch, self.nslots = int(nch), int(slots)
+        self.sample_length, self.eps, self.group = int(sample_length), float(eps), int(segment_frames)
+        self.nrows = ops.num_pairs(self.nch, self.ch_mode) if mode == "pair" else 1      # feature rows per slot
+        self.width = 4 if mode == "pair" else 2 * self.nch
+        self.launches = 0
+        self._tails = self._state = None
+        self.reset()
+
+    def samples(self, slot: int) -> int:
+        """Samples pushed into the slot's stream so far."""
+        return HOP * self._stream(slot).frames + self.tail_samples(slot)
+
+    def _allocate(self, device):
+        # sized for full 12-frame tiles, as the library spaces the scratch rows of arrays that do not fit the LDS
+        nbytes = _lib.load().fnssl_stream_frontend_state_bytes(self.nslots, self.nch, STREAM_MODE[self.mode],
+                                                               CH_MODE[self.ch_mode], ops.SEG_FRAMES)
+        if nbytes == 0:
+            raise RuntimeError("fnssl.stream: no streamed front end for %d slots x %d channels (mode %r)"
+                               % (self.nslots, self.nch, self.mode))
+        self._state = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        self._tails = _TailBuffer(self.nslots, self.nch, 2 * tail_bound(self.group), device, lanes=self.nslots)
+
+    def _launch(self, groups):
+        buf = self._tails.buf
+        x = torch.empty((len(groups) * self.nrows, self.group, ops.NF, self.width), dtype=torch.float32, device=buf.device)
+        sb, sn, sc = buf.stride()
+
+        def sig_offset(g):
+            at = g.sample0 - HOP * self._slots[g.slot].frames             # the lane starts with the next frame to emit
+            assert at >= 0 and at + g.ns == self._tails.len[g.slot]       # the window lies inside the slot's tail
+            return g.slot * sb + (self._tails.start[g.slot] + at) * sn
+
+        descs, launches = pool_pack_descriptors(groups, self.group, sig_offset)
+        ca, cb = _stream_coefs(self.sample_length, True, buf.device)
+        check(_lib.load().fnssl_stream_frontend_pool(
+            ops._ptr(buf), self.nslots, self.nch, sn, sc, STREAM_MODE[self.mode], CH_MODE[self.ch_mode], descs, len(groups),
+            ops._ptr(ca), ops._ptr(cb), self.sample_length, self.eps, ops._ptr(self._state), self._state.numel(), ops._ptr(x),
+            len(groups), self.group, ops._stream()), "stream_frontend_pool")
+        self.launches += len(launches)
+        return x
+
+    def push(self, chunks: dict):
+        for slot in chunks:
+            self._stream(slot)
+        device = self.device
+        for slot, chunk in chunks.items():
+            if not isinstance(chunk, torch.Tensor) or chunk.ndim != 2 or chunk.shape[1] != self.nch:
+                raise RuntimeError("fnssl.stream: slot %d: expected a chunk [n, %d], got %s"
+                                   % (slot, self.nch, tuple(getattr(chunk, "shape", ()))))
+            ops._need_dev(chunk)
+            device = chunk.device if device is None else device
+            if chunk.device != device:
+                raise RuntimeError("fnssl.stream: the pool lives on %s, slot %d was pushed a chunk on %s" % (device, slot, chunk.device))
+        tail = (lambda s: 0) if self._tails is None else (lambda s: self._tails.len[s])
+        streams = {s: (st.frames, tail(s)) for s, st in self._slots.items()}
+        rounds, after = hop_pool_plan_push(streams, {s: c.shape[0] for s, c in chunks.items()}, self.group)
+        out = []
+        if device is not None:           # (no device yet: nothing has ever been pushed, and nothing was planned)
+            with torch.cuda.device(device):
+                if self._tails is None:
+                    self._allocate(device)
+                for slot, chunk in chunks.items():
+                    if chunk.shape[0]:
+                        self._tails.append(slot, chunk.unsqueeze(0))
+                out = [(groups, self._launch(groups)) for groups in rounds]
+        for slot, (frames, keep) in after.items():
+            st = self._slots[slot]
+            if self._tails is not None:
+                self._tails.drop(slot, HOP * (frames - st.frames))
+                assert self._tails.len[slot] == keep
+            st.frames = frames
+        return out
+
+    def finish(self, slot: int):
+        """The end of a stream completes nothing here: a hop-256 frame depends on its own samples only."""
+        self._stream(slot)
+        return []
+
+
+def _lstm_pool_kind(model):
+    """'pair' for an ``FN_SSL``, 'array' for a fixed-array ``IPDnet``: told apart by the modules ``forward_stream`` of
+    each walks."""
+    if all(hasattr(model, a) for a in ("block_1", "block_2", "block_3", "emb2ipd", "forward_stream")):
+        return "pair"
+    if all(hasattr(model, a) for a in ("block_1", "block_2", "conv", "cnn_out_dim", "forward_stream")):
+        return "array"
+    raise ValueError("LstmStreamPool: the model must be an FN_SSL or a fixed-array IPDnet, got %s" % type(model).__name__)
+
+
+class LstmStreamPool:
+    """``slots`` independent FN-SSL / IPDnet streams on one device, each with its own sample tail, frame count,
+    normalisation ``mu`` and network state; ``model`` is an online fp32 ``FN_SSL`` (front end 'pair') or ``IPDnet`` (front
+    end 'array') in eval mode — the errors for anything else are ``forward_stream``'s own, raised here.
+
+    ``open() -> slot``; ``push({slot: chunk [n, nch]}) -> {slot: (pred, doa)}`` for the slots that completed g >= 1 groups
+    of 12 frames (n is free per slot, 0 allowed): ``pred`` is the slot's rows of ``forward_stream``'s prediction — ``[np, g,
+    512]`` (FN-SSL) or ``[1, g, 512, nch - 1, ntrack]`` (IPDnet) —; ``close(slot)`` frees a slot, whose next ``open()``
+    starts from zero without a launch; ``reset()`` closes all.  ``doa`` is None without ``localize``, else a list with one
+    entry per group: what ``localize(pred of the call's rows)`` returned (a tensor, or a tuple / list / dict of tensors),
+    narrowed to this slot's rows along ``localize_batch_dim``.
+
+    The device work of a push is per ROUND (a real-time push is one round), whatever the number of slots: one
+    ``fnssl_stream_frontend_pool`` call and ONE ``model.forward_stream`` call on the round's rows.  The state is
+    ``forward_stream``'s dict for ``slots`` streams: the call runs in place on it when its rows are all slots in order and
+    all carried, otherwise on a compact dict between one gather and one scatter (``fnssl_state_rows``) over the segments of
+    ``_segments``: per narrow-band layer the slot's cell records at the front of the LSTM workspace
+    (``fnssl_lstm_cell_group_floats``; everything behind them is rebuilt by each call) and the h / tail tensors.  Fresh
+    rows (a stream's first group) ride in the carried rows' call: the gather hands them zeros, and a zeroed state under
+    carry gives the bits of ``forward_stream(x, None)`` (DESIGN 3.3c;
+    tests/test_gpu_stream_pool_lstm.py::test_first_group_finding)."""
+
+    # forward_stream's carried tensors beside the workspaces: (key, index in the list or None)
+    _TENSORS = {"pair": (("h", 0), ("h", 1), ("h", 2)),
+                "array": (("n_tail", 0), ("n_tail", 1), ("x_tail", None), ("p_tail", 0), ("p_tail", 1))}
+
+    def __init__(self, model, nch: int, slots: int, ch_mode: str = "MM", localize=None, localize_batch_dim: int = 0,
+                 sample_length: int = None, eps: float = 1e-6):
+        self.kind = _lstm_pool_kind(model)
+        self.frontend = HopPoolFrontEnd(self.kind, nch, slots, ch_mode, sample_length, eps, ops.SEG_FRAMES)
+        if model.input_size != self.frontend.width:
+            raise ValueError("LstmStreamPool: the front end emits %d feature channels, the network takes %d"
+                             % (self.frontend.width, model.input_size))
+        self.model, self.localize, self.localize_batch_dim = model, localize, int(localize_batch_dim)
+        self.nslots, self.np = self.frontend.nslots, self.frontend.nrows
+        # as OnlineLocalizer: a zero-frame call runs forward_stream's checks of the module (eval mode, online, fp32) and
+        # stops at its shape check
+        try:
+            model.forward_stream(torch.zeros((1, self.frontend.width, ops.NF, 0)))
+        except RuntimeError as e:
+            if "expected [nb" not in str(e):
+                raise
+        self.in_place = True             # False: every call of the network goes through gather and scatter (tests)
+        self.gathers = self.scatters = 0
+        self._pool = self._compact = None
+
+    def open(self) -> int:
+        return self.frontend.open()
+
+    def close(self, slot: int):
+        self.frontend.close(slot)
+
+    def reset(self):
+        self.frontend.reset()
+
+    # ---- the state ---------------------------------------------------------
+    def _blocks(self):
+        m = self.model
+        return (m.block_1, m.block_2, m.block_3) if self.kind == "pair" else (m.block_1, m.block_2)
+
+    def _new_state(self, device):
+        """``forward_stream``'s dict for ``nslots`` streams, all zero (what its own ``state=None`` branch builds, with the
+        h tensors of FN-SSL present)."""
+        rows, nf = self.nslots * self.np, ops.NF
+        blocks = self._blocks()
+        state = {"ws": [ops.lstm_state_workspace(rows * nf, b.narr_hidden_size, device) for b in blocks],
+                 "shape": (rows, nf), "frames": 0}
+        if self.kind == "pair":
+            state["h"] = [torch.zeros((rows, nf, b.narr_hidden_size), device=device) for b in blocks]
+        else:
+            hid = self.model.conv.cnn_hidden_dim
+            state["n_tail"] = [torch.zeros((rows, nf, 2, b.narr_hidden_size), device=device) for b in blocks]
+            state["x_tail"] = torch.zeros((rows, 2, nf, self.model.input_size), device=device)
+            state["p_tail"] = [torch.zeros((rows, nf, 2, hid), device=device) for _ in range(2)]
+        return state
+
+    @staticmethod
+    def _get(state, key, idx):
+        return state[key] if idx is None else state[key][idx]
+
+    def _call_state(self, store, rows):
+        """The dict of one ``forward_stream`` call on the first ``rows`` batch rows of ``store`` (views: a call on fewer
+        rows uses the front of every tensor, and of every workspace — its check only asks for enough bytes), carried."""
+        state = {"ws": store["ws"], "shape": (rows, ops.NF), "frames": ops.SEG_FRAMES}
+        for key, idx in self._TENSORS[self.kind]:
+            t = self._get(store, key, idx)[:rows]
+            if idx is None:
+                state[key] = t
+            else:
+                state.setdefault(key, [None] * len(store[key]))[idx] = t
+        return state
+
+    def _segments(self, pool, compact):
+        """The ctypes segment table of ``fnssl_state_rows``: per block the slot's cell records in the workspace, then the
+        carried tensors.  Rebuilt from ``data_ptr()`` per call: ``forward_stream`` replaces the tensors it returns."""
+        lib = _lib.load()
+        segs = []
+        for k, b in enumerate(self._blocks()):
+            cell = lib.fnssl_lstm_cell_group_floats(b.narr_hidden_size)
+            if cell == 0:
+                raise RuntimeError("fnssl.stream: no streaming LSTM kernel for hidden size %d" % b.narr_hidden_size)
+            segs.append((pool["ws"][k], compact["ws"][k], self.np * (ops.NF // 16) * cell))
+        for key, idx in self._TENSORS[self.kind]:
+            p, c = self._get(pool, key, idx), self._get(compact, key, idx)
+            segs.append((p, c, self.np * p[0].numel()))
+        table = (_lib.StateSeg * len(segs))()
+        for j, (p, c, row) in enumerate(segs):
+            if not (p.is_contiguous() and c.is_contiguous() and p.dtype == c.dtype == torch.float32):
+                raise RuntimeError("fnssl.stream: segment %d of the carried state is not a dense float32 tensor" % j)
+            table[j] = _lib.StateSeg(p.data_ptr(), c.data_ptr(), row)
+        return table
+
+    def _rows(self, pool, compact, slots, direction, fresh=None):
+        n = len(slots)
+        table = self._segments(pool, compact)
+        check(_lib.load().fnssl_state_rows(
+            table, len(table), self.nslots, n, (C.c_int * n)(*slots),
+            None if fresh is None else (C.c_ubyte * n)(*[int(f) for f in fresh]), direction, ops._stream()), "state_rows")
+        if direction == _lib.SN_ROWS_GATHER:
+            self.gathers += 1
+        else:
+            self.scatters += 1
+
+    def _adopt(self, store, returned):
+        """``forward_stream`` replaced the carried tensors of the call's dict: the ones of a full-size call become the store's."""
+        for key, idx in self._TENSORS[self.kind]:
+            if idx is None:
+                store[key] = returned[key]
+            else:
+                store[key][idx] = returned[key][idx]
+
+    def _network(self, x, groups):
+        """The network on a round's rows ``x [n * np, 12, 256, C]``.  In place on the pool's state when the rows are all
+        slots in order and all carried; else on the compact state: gather (zeros for fresh rows), forward, scatter."""
+        if self._pool is None:
+            self._pool = self._new_state(x.device)
+        slots = [g.slot for g in groups]
+        fresh = [g.fresh for g in groups]
+        xv = x.permute(0, 3, 2, 1)                                        # a view: nothing is moved
+        if self.in_place and slots == list(range(self.nslots)) and not any(fresh):
+            pred, state = self.model.forward_stream(xv, self._call_state(self._pool, x.shape[0]))
+            self._adopt(self._pool, state)
+            return pred
+        if self._compact is None:        # as large as the pool's state: holds the compact state of any number of rows
+            self._compact = self._new_state(x.device)
+        self._rows(self._pool, self._compact, slots, _lib.SN_ROWS_GATHER, fresh)
+        pred, state = self.model.forward_stream(xv, self._call_state(self._compact, x.shape[0]))
+        # the scatter reads the tensors the call returned; the compact store keeps its own full-size ones
+        self._rows(self._pool, state, slots, _lib.SN_ROWS_SCATTER)
+        return pred
+
+    def _narrow(self, out, a, n):
+        """Row a of n of what ``localize`` returned."""
+        if isinstance(out, dict):
+            return {k: self._narrow(v, a, n) for k, v in out.items()}
+        if isinstance(out, (tuple, list)):
+            return tuple(self._narrow(v, a, n) for v in out)
+        if not isinstance(out, torch.Tensor):
+            return out
+        per = out.shape[self.localize_batch_dim] // n
+        return out.narrow(self.localize_batch_dim, a * per, per)
+
+    @torch.no_grad()
+    def push(self, chunks: dict):
+        out = {}
+        for groups, x in self.frontend.push(chunks):
+            with torch.cuda.device(x.device):
+                pred = self._network(x, groups)
+                doa = self.localize(pred) if self.localize is not None else None
+            for a, g in enumerate(groups):
+                preds, doas = out.setdefault(g.slot, ([], []))
+                preds.append(pred[a * self.np:(a + 1) * self.np])
+                if doa is not None:
+                    doas.append(self._narrow(doa, a, len(groups)))
+        return {slot: (torch.cat(preds, dim=1), doas if self.localize is not None else None)
+                for slot, (preds, doas) in out.items()}

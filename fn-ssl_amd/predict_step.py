@@ -259,3 +259,12 @@ class MyModel(_Base):
             state = stream.OnlineLocalizer(self.arch, stream.StreamFrontEnd("pair", chunk.shape[1], self.ch_mode, 298, 1e-6))
         pred, _ = state.push(chunk.permute(0, 2, 1).to(self.dev))
         return pred, state
+
+    def open_stream_pool(self, nch: int, slots: int, localize: bool = False):
+        """A ``fnssl.stream.LstmStreamPool`` on ``self.arch``: ``slots`` independent streams of ``nch`` microphones, each
+        with its own start and chunk sizes, served by one front-end launch and one network call per push
+        (``pool.open()``, ``pool.push({slot: chunk [n, nch]})``, ``pool.close(slot)``).  ``localize=True`` maps every
+        prediction to the DOA dict of ``get_metric.predgt2DOA``, narrowed to the slot's rows."""
+        from fnssl import stream
+        entry = (lambda p: self.get_metric.predgt2DOA(pred_batch=p)[0]) if localize else None
+        return stream.LstmStreamPool(self.arch, nch, slots, self.ch_mode, localize=entry, sample_length=298, eps=1e-6)

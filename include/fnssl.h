@@ -290,6 +290,11 @@ size_t fnssl_lstm_workspace_bytes(int nseq, int hidden, int ndir);
  * 256 with one direction, the cell-state snapshot (~1 KiB per sequence), where the bf16 "wide" calls need ~513 B per
  * sequence; training / streaming / per-stream caches should size with this one. */
 size_t fnssl_lstm_workspace_bytes_ex(int nseq, int hidden, int ndir, int precision);
+/* Floats of one 16-sequence group's cell record in a ONE-direction workspace (16 * hidden): the carried cell state sits at
+ * the workspace's front as one record per group, whatever the launch geometry, so sequences 16 g .. 16 g + 15 own floats
+ * g * n .. (g + 1) * n - 1, and a streaming caller can move whole groups between workspaces without knowing a record's
+ * interior.  0 for a hidden size without a streaming kernel.  (Additive: FNSSL_ABI_VERSION stays 19.) */
+int fnssl_lstm_cell_group_floats(int hidden);
 
 /* Host-only query of the launch planner of fnssl_lstm_forward (full-chip fp32 launches, hidden 128 / 256): the rounds
  * (one launch each, one workgroup of waves_per_wg[i] waves per CU) it runs for nseq sequences per direction on ncu CUs.
@@ -858,6 +863,27 @@ int fnssl_stream_frontend_centred_pool(const float* sig, int nslots, int nch, lo
                                        const float* coef_b, int sample_length, float eps, void* state, size_t state_bytes,
                                        float* x, int out_rows, int out_frames, void* stream);
 
+/* ---- a pool of independent hop-256 streams: FN-SSL / IPDnet (additive: FNSSL_ABI_VERSION stays 19) ------------------------
+ * fnssl_stream_frontend for any subset of the slots of a pool in ONE launch: workgroup i serves fnssl_stream_pool_desc i.
+ * The hop-256 transform is not centred and has no end reflection, so of a descriptor
+ *   sample0     must equal 256 * frame0 (the window starts with the first sample of frame frame0)
+ *   total       must be negative
+ *   ns          >= (nframes - 1) * 256 + 512
+ * and the other fields are those of fnssl_stream_frontend_centred_pool.
+ *   mode, ch_mode   as fnssl_stream_frontend
+ *   state        fnssl_stream_frontend_state_bytes(nslots, nch, mode, ch_mode, 12) bytes, indexed by SLOT: mu[nslots][chains],
+ *                then the per-slot scratch of arrays whose 12-frame tile does not fit the LDS; a fresh descriptor starts from
+ *                mu = 0 whatever its row holds; rows of slots not named are not touched
+ *   x            pair mode: [out_rows * np, out_frames, 256, 4], descriptor d writes rows d.out_row * np .. + np - 1;
+ *                array mode: [out_rows, out_frames, 256, 2 * nch], descriptor d writes row d.out_row
+ * Every descriptor is validated before the first launch; FNSSL_E_INVALID names the offending descriptor.  More than
+ * FNSSL_STREAM_POOL_MAX_DESC descriptors take more launches.
+ */
+int fnssl_stream_frontend_pool(const float* sig, int nslots, int nch, long long sn, long long sc, int mode, int ch_mode,
+                               const fnssl_stream_pool_desc* desc, int ndesc, const float* coef_a, const float* coef_b,
+                               int sample_length, float eps, void* state, size_t state_bytes, float* x, int out_rows,
+                               int out_frames, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* IPDnet head (next row 8f-3): causal 3x3 Conv2d + time pooling              */
 /* ------------------------------------------------------------------------- */
@@ -1233,6 +1259,23 @@ int fnssl_sn_forward(const fnssl_sn_net* net, const float* x, long long x_sb, lo
 #define FNSSL_SN_ROWS_MAX 256
 int fnssl_sn_state_rows(const fnssl_sn_net* net, int nslots, int nf, float* pool_state, int nrows, float* compact_state,
                         const int* slots, const unsigned char* fresh, int direction, void* stream);
+
+/* ---- rows of a carried state that is a list of tensors (additive: FNSSL_ABI_VERSION stays 19) ------------------------------
+ * The general form of fnssl_sn_state_rows for the LSTM models, whose carried state is a list of batch-leading tensors: a
+ * segment is one such tensor of the pool ([nslots][row_floats]) and its compact counterpart ([>= nrows][row_floats]).
+ *   FNSSL_SN_ROWS_GATHER    compact row a <- pool row slots[a] of every segment, or zeros where fresh[a] != 0 (fresh may be NULL)
+ *   FNSSL_SN_ROWS_SCATTER   pool row slots[a] <- compact row a of every segment (fresh is ignored)
+ * row_floats: a positive multiple of 4 below 2^32; all pointers 16-byte aligned and distinct; 1..FNSSL_STATE_ROWS_MAX_SEGS
+ * segments.  The table and the slots (host memory, distinct, each < nslots) go by value in the kernel arguments, one launch
+ * per 64 rows.  A pure float4 copy: rows of slots not listed are not touched. */
+#define FNSSL_STATE_ROWS_MAX_SEGS 8
+typedef struct {
+  float* pool;
+  float* compact;
+  long long row_floats;
+} fnssl_state_seg;
+int fnssl_state_rows(const fnssl_state_seg* segs, int nsegs, int nslots, int nrows, const int* slots,
+                     const unsigned char* fresh, int direction, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Measurement hooks (bench.py: per-kernel HIP-event timing on the launch stream) */
