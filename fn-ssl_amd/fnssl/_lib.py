@@ -74,6 +74,7 @@ SYMBOLS = [
     "fnssl_sn_full_backward_workspace_bytes", "fnssl_sn_full_backward",
     "fnssl_sn_encoder_backward_workspace_bytes", "fnssl_sn_encoder_backward",
     "fnssl_sn_head_backward_workspace_bytes", "fnssl_sn_head_backward",
+    "fnssl_rir_plan", "fnssl_rir_workspace_bytes", "fnssl_rir_ism", "fnssl_rir_tail", "fnssl_rir_trajectory",
 ]
 
 
@@ -148,6 +149,23 @@ STATE_ROWS_MAX_SEGS = 8                     # include/fnssl.h: FNSSL_STATE_ROWS_
 class StateSeg(C.Structure):
     """include/fnssl.h: fnssl_state_seg, one batch-leading tensor of a carried state and its compact counterpart."""
     _fields_ = [("pool", C.c_void_p), ("compact", C.c_void_p), ("row_floats", C.c_longlong)]
+
+
+RIR_MAX_ISM_SAMPLES = 8192                  # include/fnssl.h: FNSSL_RIR_MAX_ISM_SAMPLES
+RIR_MAX_IMAGES_AXIS = 1024                  # include/fnssl.h: FNSSL_RIR_MAX_IMAGES_AXIS
+RIR_TRAJ_MAX_BATCH = 16                     # include/fnssl.h: FNSSL_RIR_TRAJ_MAX_BATCH
+
+
+class RirPlanInfo(C.Structure):
+    """include/fnssl.h: fnssl_rir_plan_info, the image chunks and the launch geometry of fnssl_rir_ism."""
+    _fields_ = [(n, C.c_int) for n in ("images", "chunk_images", "nchunks", "last_chunk_images", "grid_x", "grid_y", "threads",
+                                       "lds_bytes")] + [("workspace_bytes", C.c_size_t)]
+
+
+class RirTrajItem(C.Structure):
+    """include/fnssl.h: fnssl_rir_traj_item, one (signal, RIR set) pair of a fnssl_rir_trajectory call (48 bytes)."""
+    _fields_ = [("x", C.c_void_p), ("rirs", C.c_void_p), ("w_ini", C.c_void_p), ("y", C.c_void_p),
+                ("ns", C.c_int), ("len", C.c_int), ("npts", C.c_int), ("m", C.c_int)]
 
 
 class BtfView(C.Structure):
@@ -267,6 +285,13 @@ def load():
     lib.fnssl_stream_frontend_pool.argtypes = [vp, i, i, ll, ll, i, i, C.POINTER(StreamPoolDesc), i, vp, vp, i, f, vp, sz, vp,
                                                i, i, vp]
     lib.fnssl_state_rows.argtypes = [C.POINTER(StateSeg), i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_ubyte), i, vp]
+    f3, f6, i3 = C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 6), C.POINTER(C.c_int * 3)
+    lib.fnssl_rir_plan.argtypes = [i, i, i3, i, i, C.POINTER(RirPlanInfo)]
+    lib.fnssl_rir_workspace_bytes.argtypes = [i, i, i3, i, i]
+    lib.fnssl_rir_workspace_bytes.restype = sz
+    lib.fnssl_rir_ism.argtypes = [f3, f6, vp, i, vp, i, i3, i, i, C.c_double, C.c_double, vp, vp, sz, vp]
+    lib.fnssl_rir_tail.argtypes = [f3, f6, vp, i, vp, i, i, i, C.c_double, C.c_double, C.c_ulonglong, vp, vp]
+    lib.fnssl_rir_trajectory.argtypes = [C.POINTER(RirTrajItem), i, vp]
     lib.fnssl_pair_features.argtypes = [vp, vp, vp, vp, i, i, i, i, f, vp, vp, i, vp]
     lib.fnssl_nchw_to_seq.argtypes = [vp, i, i, i, i, vp, vp]
     lib.fnssl_lstm_packed_floats.argtypes = [i, i, i]

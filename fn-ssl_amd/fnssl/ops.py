@@ -1061,3 +1061,104 @@ def timing_collect(cap: int = 64):
     fl = (C.c_double * cap)()
     n = _lib.load().fnssl_timing_collect(cap, names, ms, cnt, fl)
     return {names[i].value.decode(): {"ms": ms[i], "count": cnt[i], "flops": fl[i]} for i in range(n)}
+
+
+# --------------------------------------------------------------------------- #
+# room simulation (csrc/rir.hip; the gpuRIR-named surface is fnssl/rir.py)
+# --------------------------------------------------------------------------- #
+def _rir_host(room_sz, beta, nb_img):
+    room = [float(v) for v in np.asarray(room_sz, dtype=np.float64).reshape(-1)]
+    bet = [float(v) for v in np.asarray(beta, dtype=np.float64).reshape(-1)]
+    if len(room) != 3 or len(bet) != 6:
+        raise ValueError("fnssl.rir: room_sz has 3 entries and beta 6, got %d and %d" % (len(room), len(bet)))
+    out = [(C.c_float * 3)(*room), (C.c_float * 6)(*bet)]
+    if nb_img is not None:
+        nb = [int(v) for v in np.asarray(nb_img).reshape(-1)]
+        if len(nb) != 3:
+            raise ValueError("fnssl.rir: nb_img has 3 entries, got %d" % len(nb))
+        out.append((C.c_int * 3)(*nb))
+    return out
+
+
+def rir_plan(m_src: int, m_rcv: int, nb_img, nism: int, cus: int = 0) -> dict:
+    """Host only (fnssl_rir_plan): the image chunks per RIR and the launch geometry ``rir_ism`` takes for these sizes on a
+    device of ``cus`` compute units (0: the current device)."""
+    nb = (C.c_int * 3)(*[int(v) for v in nb_img])
+    info = _lib.RirPlanInfo()
+    check(_lib.load().fnssl_rir_plan(int(m_src), int(m_rcv), C.byref(nb), int(nism), int(cus), C.byref(info)), "rir_plan")
+    return {n: int(getattr(info, n)) for n, _ in _lib.RirPlanInfo._fields_}
+
+
+def _rir_positions(pos_src, pos_rcv):
+    _need_dev(pos_src, pos_rcv)
+    if pos_src.ndim != 2 or pos_src.shape[1] != 3 or pos_rcv.ndim != 2 or pos_rcv.shape[1] != 3:
+        raise RuntimeError("fnssl.rir: positions are [M, 3], got %s and %s" % (tuple(pos_src.shape), tuple(pos_rcv.shape)))
+    return pos_src.contiguous(), pos_rcv.contiguous()
+
+
+@on_device
+def rir_ism(pos_src, pos_rcv, room_sz, beta, nb_img, nism: int, nsamples: int, fs: float, c: float = 343.0, out=None):
+    """Image-source part (fnssl_rir_ism): pos_src [M_src, 3], pos_rcv [M_rcv, 3] -> RIRs [M_src, M_rcv, nsamples] with samples
+    [0, nism) written (the rest zero unless ``out`` is given)."""
+    pos_src, pos_rcv = _rir_positions(pos_src, pos_rcv)
+    room, bet, nb = _rir_host(room_sz, beta, nb_img)
+    ms, mr = pos_src.shape[0], pos_rcv.shape[0]
+    lib = _lib.load()
+    if out is None:
+        out = torch.zeros((ms, mr, int(nsamples)), dtype=torch.float32, device=pos_src.device)
+    else:
+        _need_dev(out)
+        if tuple(out.shape) != (ms, mr, int(nsamples)) or not out.is_contiguous() or out.device != pos_src.device:
+            raise RuntimeError("fnssl.rir_ism: out must be a contiguous [%d, %d, %d] on %s, got %s on %s"
+                               % (ms, mr, int(nsamples), pos_src.device, tuple(out.shape), out.device))
+    wsb = lib.fnssl_rir_workspace_bytes(ms, mr, C.byref(nb), int(nism), 0)
+    ws = torch.empty(max(wsb, 4) // 4, dtype=torch.float32, device=pos_src.device)
+    check(lib.fnssl_rir_ism(C.byref(room), C.byref(bet), _ptr(pos_src), ms, _ptr(pos_rcv), mr, C.byref(nb), int(nism),
+                            int(nsamples), float(fs), float(c), _ptr(out), _ptr(ws), ws.numel() * 4, _stream()), "rir_ism")
+    return out
+
+
+@on_device
+def rir_tail(rir, pos_src, pos_rcv, room_sz, beta, nism: int, fs: float, c: float = 343.0, seed: int = 0):
+    """Diffuse tail (fnssl_rir_tail), in place: samples [nism, nsamples) of ``rir`` [M_src, M_rcv, nsamples] from its samples
+    [0, nism).  Returns ``rir``."""
+    pos_src, pos_rcv = _rir_positions(pos_src, pos_rcv)
+    _need_dev(rir)
+    ms, mr = pos_src.shape[0], pos_rcv.shape[0]
+    if rir.ndim != 3 or tuple(rir.shape[:2]) != (ms, mr) or not rir.is_contiguous():
+        raise RuntimeError("fnssl.rir_tail: expected a contiguous [%d, %d, nSamples], got %s" % (ms, mr, tuple(rir.shape)))
+    room, bet = _rir_host(room_sz, beta, None)
+    check(_lib.load().fnssl_rir_tail(C.byref(room), C.byref(bet), _ptr(pos_src), ms, _ptr(pos_rcv), mr, int(nism),
+                                     int(rir.shape[2]), float(fs), float(c), int(seed) & (2 ** 64 - 1), _ptr(rir), _stream()),
+          "rir_tail")
+    return rir
+
+
+@on_device
+def rir_trajectory_batch(signals, rirs, w_inis):
+    """Moving-source mixing of several independent (signal [ns], RIRs [npts, M, len], w_ini int32 [npts + 1]) triples in one
+    launch (fnssl_rir_trajectory) -> list of [ns + len - 1, M]."""
+    n = len(signals)
+    if not (n == len(rirs) == len(w_inis)) or n < 1:
+        raise RuntimeError("fnssl.rir_trajectory_batch: %d signals, %d RIR sets, %d w_ini" % (n, len(rirs), len(w_inis)))
+    outs, keep = [], []
+    items = (_lib.RirTrajItem * _lib.RIR_TRAJ_MAX_BATCH)()
+    lib = _lib.load()
+    for k0 in range(0, n, _lib.RIR_TRAJ_MAX_BATCH):
+        k1 = min(n, k0 + _lib.RIR_TRAJ_MAX_BATCH)
+        for k in range(k0, k1):
+            x, r, w = signals[k], rirs[k], w_inis[k]
+            _need_dev(x, r)
+            if not isinstance(w, torch.Tensor) or not w.is_cuda or w.dtype != torch.int32:
+                raise RuntimeError("fnssl.rir_trajectory_batch: w_ini must be an int32 ROCm tensor")
+            if x.ndim != 1 or r.ndim != 3 or w.ndim != 1 or w.numel() != r.shape[0] + 1 or x.numel() < 1:
+                raise RuntimeError("fnssl.rir_trajectory_batch: item %d: signal %s, RIRs %s, w_ini %s"
+                                   % (k, tuple(x.shape), tuple(r.shape), tuple(w.shape)))
+            x, r, w = x.contiguous(), r.contiguous(), w.contiguous()
+            y = torch.empty((x.numel() + r.shape[2] - 1, r.shape[1]), dtype=torch.float32, device=x.device)
+            keep.append((x, r, w))
+            outs.append(y)
+            items[k - k0] = _lib.RirTrajItem(x.data_ptr(), r.data_ptr(), w.data_ptr(), y.data_ptr(), x.numel(), r.shape[2],
+                                             r.shape[0], r.shape[1])
+        check(lib.fnssl_rir_trajectory(items, k1 - k0, _stream()), "rir_trajectory")
+    return outs

@@ -1277,6 +1277,64 @@ typedef struct {
 int fnssl_state_rows(const fnssl_state_seg* segs, int nsegs, int nslots, int nrows, const int* slots,
                      const unsigned char* fresh, int direction, void* stream);
 
+/* ---- room simulation (additive: FNSSL_ABI_VERSION stays 19) ------------------------------------------------------------------
+ * What gpuRIR does in the reference's Simu.py / Dataset.py (AcousticScene.simulate): fnssl/rir.py carries its names.  The
+ * model is DESIGN.md §17; it is written from the published formulas and is NOT bit compatible with gpuRIR.
+ * Common arguments: room_sz[3], beta[6] (walls x0, x1, y0, y1, z0, z1; 0 .. 1) and nb_img[3] are HOST arrays; pos_src
+ * [m_src][3], pos_rcv [m_rcv][3] and rir [m_src][m_rcv][nsamples] are DEVICE float arrays; nism / nsamples are the even
+ * sample counts of the image-source part and of the whole RIR (fnssl/rir.py: sample_counts).  m_src * m_rcv <= 65535.
+ *
+ * fnssl_rir_ism writes rir[..][0 .. nism): per axis the images n = i - floor(N / 2), i = 0 .. N - 1, at n L + p (n even) or
+ * (n + 1) L - p (n odd), |n| reflections (for n > 0 ceil(n / 2) on the far wall), amplitude prod beta^count / (4 pi d); every
+ * image adds amp * 0.5 (1 + cos(2 pi (t - tau) / Tw)) * sinc(t - tau) for |t - tau| <= Tw / 2, tau = d fs / c, Tw = 8e-3 fs samples,
+ * clipped to [0, nism).  One wave per workgroup owns an LDS tile of nism <= FNSSL_RIR_MAX_ISM_SAMPLES samples (a longer
+ * image-source part fails with FNSSL_E_INVALID naming the limit); the images of a RIR are split into chunks of whole waves
+ * over several workgroups (fnssl_rir_plan reports them) whose partial tiles go to `workspace` and are added in chunk order.
+ * No float atomics: two runs give the same bits.  nb_img[a] <= FNSSL_RIR_MAX_IMAGES_AXIS; fs from 250 Hz to 63.8 kHz.
+ *
+ * fnssl_rir_plan is host only: `cus` <= 0 asks the current device, tests pass 256.  fnssl_rir_workspace_bytes is its
+ * workspace_bytes (0 for one chunk, and 0 for arguments fnssl_rir_plan refuses). */
+#define FNSSL_RIR_MAX_ISM_SAMPLES 8192
+#define FNSSL_RIR_MAX_IMAGES_AXIS 1024
+typedef struct {
+  int images;              /* per RIR: nb_img[0] * nb_img[1] * nb_img[2] */
+  int chunk_images;        /* images per workgroup, a multiple of 64 */
+  int nchunks;             /* workgroups per RIR */
+  int last_chunk_images;   /* the ragged last chunk */
+  int grid_x, grid_y;      /* nchunks, m_src * m_rcv */
+  int threads;             /* 64 */
+  int lds_bytes;           /* dynamic LDS of one workgroup */
+  size_t workspace_bytes;
+} fnssl_rir_plan_info;
+int fnssl_rir_plan(int m_src, int m_rcv, const int* nb_img, int nism, int cus, fnssl_rir_plan_info* out);
+size_t fnssl_rir_workspace_bytes(int m_src, int m_rcv, const int* nb_img, int nism, int cus);
+int fnssl_rir_ism(const float* room_sz, const float* beta, const float* pos_src, int m_src, const float* pos_rcv, int m_rcv,
+                  const int* nb_img, int nism, int nsamples, double fs, double c, float* rir, void* workspace,
+                  size_t workspace_bytes, void* stream);
+/* Writes rir[..][nism .. nsamples) from rir[..][0 .. nism) (run it after the image-source part, on the same stream): the
+ * log mean square of whole segments of Ls = round(8e-3 fs) samples from t0 = floor(tau_direct) gets a least-squares line
+ * e = a + b t through the segment centres (>= 3 segments and b < 0; otherwise b is Sabine's slope for room_sz / beta and the
+ * line goes through the last whole segment, or through the mean square of the whole part at nism / 2); sample t is
+ * sqrt(exp(a + b t)) * xi, xi = sqrt(3) / pi * ln(u / (1 - u)), u = ((w >> 9) + 0.5) / 2^23 with w word t % 4 of
+ * Philox4x32-10(key = seed, counter = (t / 4, rcv, src, 0)): the same tail for a seed whatever the launch geometry. */
+int fnssl_rir_tail(const float* room_sz, const float* beta, const float* pos_src, int m_src, const float* pos_rcv, int m_rcv,
+                   int nism, int nsamples, double fs, double c, unsigned long long seed, float* rir, void* stream);
+/* Moving-source mixing, a batch of independent (signal, RIR set) pairs in one launch (a scene: 2 sources x {full, direct
+ * path, VAD}).  Per item: x [ns], rirs [npts][m][len], w_ini [npts + 1] (int32, first sample of each point, w_ini[npts] = ns),
+ * y [ns + len - 1][m], all DEVICE arrays:
+ *   y[t][m] = sum_k rirs[p(t - k)][m][k] * x[t - k],  p(s) the point with w_ini[p] <= s < w_ini[p + 1]
+ * (samples of no point add nothing; a repeated w_ini is an empty segment).  Time domain, one running sum per output over
+ * ascending source samples: deterministic, and exact where every partial sum is representable. */
+#define FNSSL_RIR_TRAJ_MAX_BATCH 16
+typedef struct {
+  const float* x;
+  const float* rirs;
+  const int* w_ini;
+  float* y;
+  int ns, len, npts, m;
+} fnssl_rir_traj_item;
+int fnssl_rir_trajectory(const fnssl_rir_traj_item* items, int nitems, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* Measurement hooks (bench.py: per-kernel HIP-event timing on the launch stream) */
 /* ------------------------------------------------------------------------- */
