@@ -75,6 +75,8 @@ SYMBOLS = [
     "fnssl_sn_encoder_backward_workspace_bytes", "fnssl_sn_encoder_backward",
     "fnssl_sn_head_backward_workspace_bytes", "fnssl_sn_head_backward",
     "fnssl_rir_plan", "fnssl_rir_workspace_bytes", "fnssl_rir_ism", "fnssl_rir_tail", "fnssl_rir_trajectory",
+    "fnssl_anf_coherence", "fnssl_anf_factor", "fnssl_anf_status", "fnssl_anf_mean", "fnssl_anf_mix", "fnssl_scene_power",
+    "fnssl_scene_finish",
 ]
 
 
@@ -154,6 +156,11 @@ class StateSeg(C.Structure):
 RIR_MAX_ISM_SAMPLES = 8192                  # include/fnssl.h: FNSSL_RIR_MAX_ISM_SAMPLES
 RIR_MAX_IMAGES_AXIS = 1024                  # include/fnssl.h: FNSSL_RIR_MAX_IMAGES_AXIS
 RIR_TRAJ_MAX_BATCH = 16                     # include/fnssl.h: FNSSL_RIR_TRAJ_MAX_BATCH
+ANF_NFFT = 256                              # include/fnssl.h: FNSSL_ANF_NFFT
+ANF_BINS = 129                              # include/fnssl.h: FNSSL_ANF_BINS
+ANF_MAX_MICS = 16                           # include/fnssl.h: FNSSL_ANF_MAX_MICS
+ANF_MEAN_CHUNK = 16384                      # include/fnssl.h: FNSSL_ANF_MEAN_CHUNK
+SCENE_MAX_SOURCES = 4                       # include/fnssl.h: FNSSL_SCENE_MAX_SOURCES
 
 
 class RirPlanInfo(C.Structure):
@@ -292,6 +299,14 @@ def load():
     lib.fnssl_rir_ism.argtypes = [f3, f6, vp, i, vp, i, i3, i, i, C.c_double, C.c_double, vp, vp, sz, vp]
     lib.fnssl_rir_tail.argtypes = [f3, f6, vp, i, vp, i, i, i, C.c_double, C.c_double, C.c_ulonglong, vp, vp]
     lib.fnssl_rir_trajectory.argtypes = [C.POINTER(RirTrajItem), i, vp]
+    p4 = C.POINTER(vp)                                         # const float* const[<= FNSSL_SCENE_MAX_SOURCES], or NULL
+    lib.fnssl_anf_coherence.argtypes = [vp, i, i, C.c_double, i, C.c_double, vp, vp]
+    lib.fnssl_anf_factor.argtypes = [vp, i, i, i, vp, vp, vp]
+    lib.fnssl_anf_status.argtypes = [vp, i, vp, C.POINTER(C.c_uint)]
+    lib.fnssl_anf_mean.argtypes = [vp, i, ll, ll, vp, sz, vp, vp]
+    lib.fnssl_anf_mix.argtypes = [vp, ll, ll, ll, vp, vp, i, i, i, i, i, i, vp, vp]
+    lib.fnssl_scene_power.argtypes = [p4, i, i, i, vp, sz, vp, vp]
+    lib.fnssl_scene_finish.argtypes = [p4, i, vp, p4, i, i, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]
     lib.fnssl_pair_features.argtypes = [vp, vp, vp, vp, i, i, i, i, f, vp, vp, i, vp]
     lib.fnssl_nchw_to_seq.argtypes = [vp, i, i, i, i, vp, vp]
     lib.fnssl_lstm_packed_floats.argtypes = [i, i, i]

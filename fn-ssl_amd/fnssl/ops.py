@@ -1162,3 +1162,157 @@ def rir_trajectory_batch(signals, rirs, w_inis):
                                              r.shape[0], r.shape[1])
         check(lib.fnssl_rir_trajectory(items, k1 - k0, _stream()), "rir_trajectory")
     return outs
+
+
+# --------------------------------------------------------------------------- #
+# scene finish (csrc/scene.hip; the reference-named surface is fnssl/scene.py)
+# --------------------------------------------------------------------------- #
+def _need_dev_f64(t, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("fnssl: expected a ROCm device tensor (this path has no CPU implementation), got %s"
+                           % (t.device if isinstance(t, torch.Tensor) else type(t)))
+    if t.dtype != torch.float64:
+        raise RuntimeError("fnssl.%s: expected float64 (pivots of 1e-7 next to ones do not fit float32), got %s" % (what, t.dtype))
+
+
+@on_device
+def anf_coherence(mic_pos, fs: float, nfft: int = 256, c: float = 343.0):
+    """Spherical coherence (fnssl_anf_coherence): mic_pos [B, M, 3] float64 -> DC [B, M, M, nfft / 2 + 1] float64."""
+    _need_dev_f64(mic_pos, "anf_coherence")
+    if mic_pos.ndim != 3 or mic_pos.shape[2] != 3:
+        raise RuntimeError("fnssl.anf_coherence: mic_pos is [B, M, 3], got %s" % (tuple(mic_pos.shape),))
+    mic_pos = mic_pos.contiguous()
+    nb, m = mic_pos.shape[0], mic_pos.shape[1]
+    dc = torch.empty((nb, m, m, int(nfft) // 2 + 1), dtype=torch.float64, device=mic_pos.device)
+    check(_lib.load().fnssl_anf_coherence(_ptr(mic_pos), nb, m, float(fs), int(nfft), float(c), _ptr(dc), _stream()), "anf_coherence")
+    return dc
+
+
+@on_device
+def anf_factor(dc, sync: bool = True):
+    """Upper Cholesky factor per bin (fnssl_anf_factor): DC [B, M, M, bins] float64 -> (C, status).  C [B, M, M, 129] float32
+    is a view of the kernel's [B, 16, 16, 129] store (what ``anf_mix`` takes), C[b, :, :, k]^T C[b, :, :, k] = DC[b, :, :, k]
+    for k >= 1, slot 0 unused.  ``sync``: read the status words (synchronises) and raise ``numpy.linalg.LinAlgError`` naming
+    the first bin that is not positive definite, as scipy.linalg.cholesky does in the reference; else the caller reads
+    ``status`` (int32 view: -1 = fine) itself."""
+    _need_dev_f64(dc, "anf_factor")
+    if dc.ndim != 4 or dc.shape[1] != dc.shape[2]:
+        raise RuntimeError("fnssl.anf_factor: DC is [B, M, M, bins], got %s" % (tuple(dc.shape),))
+    dc = dc.contiguous()
+    nb, m, nfft = dc.shape[0], dc.shape[1], 2 * (dc.shape[3] - 1)
+    lib = _lib.load()
+    store = torch.zeros((nb, _lib.ANF_MAX_MICS, _lib.ANF_MAX_MICS, _lib.ANF_BINS), dtype=torch.float32, device=dc.device)
+    status = torch.empty((nb,), dtype=torch.int32, device=dc.device)
+    check(lib.fnssl_anf_factor(_ptr(dc), nb, m, nfft, _ptr(store), _ptr(status), _stream()), "anf_factor")
+    if sync:
+        words = (C.c_uint * nb)()
+        check(lib.fnssl_anf_status(_ptr(status), nb, _stream(), words), "anf_status")
+        bad = [(b, int(w)) for b, w in enumerate(words) if w != 0xFFFFFFFF]
+        if bad:
+            raise np.linalg.LinAlgError("fnssl.anf_factor: the coherence matrix of bin %d is not positive definite%s"
+                                        % (bad[0][1], " (item %d)" % bad[0][0] if nb > 1 else ""))
+    return store[:, :m, :m, :], status
+
+
+def _anf_store(cfac):
+    want = (_lib.ANF_MAX_MICS * _lib.ANF_MAX_MICS * _lib.ANF_BINS, _lib.ANF_MAX_MICS * _lib.ANF_BINS, _lib.ANF_BINS, 1)
+    if cfac.ndim != 4 or cfac.shape[1] != cfac.shape[2] or cfac.shape[3] != _lib.ANF_BINS or \
+            (cfac.shape[0] > 1 and cfac.stride(0) != want[0]) or tuple(cfac.stride()[1:]) != want[1:]:
+        raise RuntimeError("fnssl.anf_mix: the factor must be what anf_factor returned ([B, M, M, 129] in its [B, 16, 16, 129] store), "
+                           "got %s with strides %s" % (tuple(cfac.shape), tuple(cfac.stride())))
+
+
+@on_device
+def anf_mean(x):
+    """Mean of every row of x [B, count] (fnssl_anf_mean; rows contiguous) -> [B]."""
+    _need_dev(x)
+    if x.ndim != 2 or x.stride(1) != 1 or x.shape[1] < 1:
+        raise RuntimeError("fnssl.anf_mean: expected [B, count] with contiguous rows, got %s" % (tuple(x.shape),))
+    nb, count = x.shape
+    nchunks = (count + _lib.ANF_MEAN_CHUNK - 1) // _lib.ANF_MEAN_CHUNK
+    part = torch.empty((nb * nchunks,), dtype=torch.float32, device=x.device)
+    mean = torch.empty((nb,), dtype=torch.float32, device=x.device)
+    check(_lib.load().fnssl_anf_mean(_ptr(x), nb, count, x.stride(0) if nb > 1 else 0, _ptr(part), part.numel(), _ptr(mean),
+                                     _stream()), "anf_mean")
+    return mean
+
+
+@on_device
+def anf_mix(x, cfac, mean=None, nfft: int = 256, _tile_hops: int = 0):
+    """Habets' mixing (fnssl_anf_mix): x [B, L, M] (any strides), the factor of ``anf_factor`` (one item for all, or B) and
+    optionally mean [B] (subtracted from the samples, never from the padding) -> [B, L + ((-L) mod 64), M].
+    ``_tile_hops`` is for tests: the output hops one wave owns; the bits do not depend on it."""
+    _need_dev(x, cfac, mean)
+    if x.ndim != 3:
+        raise RuntimeError("fnssl.anf_mix: expected [B, L, M], got %s" % (tuple(x.shape),))
+    nb, length, m = x.shape
+    if m <= _lib.ANF_MAX_MICS:
+        _anf_store(cfac)
+        if cfac.shape[1] != m or cfac.shape[0] not in (1, nb):
+            raise RuntimeError("fnssl.anf_mix: a factor %s for signals %s" % (tuple(cfac.shape), tuple(x.shape)))
+    if mean is not None and (mean.shape != (nb,) or not mean.is_contiguous()):
+        raise RuntimeError("fnssl.anf_mix: mean is [B], got %s" % (tuple(mean.shape),))
+    y = torch.empty((nb, length + (-length) % 64, m), dtype=torch.float32, device=x.device)
+    sb, sn, sm = x.stride()
+    check(_lib.load().fnssl_anf_mix(_ptr(x), sb, sn, sm, _ptr(mean), _ptr(cfac), cfac.shape[0], nb, length, m, int(nfft),
+                                    int(_tile_hops), _ptr(y), _stream()), "anf_mix")
+    return y
+
+
+def _scene_rows(sigs, n, m, who):
+    arr = (C.c_void_p * _lib.SCENE_MAX_SOURCES)()
+    keep = []
+    for k, a in enumerate(sigs):
+        _need_dev(a)
+        if a.ndim != 2 or a.shape[1] != m or a.shape[0] < n:
+            raise RuntimeError("fnssl.%s: signal %d is %s, expected at least [%d, %d]" % (who, k, tuple(a.shape), n, m))
+        a = a.contiguous()
+        keep.append(a)
+        if k < _lib.SCENE_MAX_SOURCES:
+            arr[k] = a.data_ptr()
+    return arr, keep
+
+
+@on_device
+def scene_power(sigs, n: int = None):
+    """``acoustic_power`` of every channel of the sum of ``sigs`` (a tensor or a list of up to 4, each [>= n, M]; rows [0, n))
+    (fnssl_scene_power) -> [M]."""
+    sigs = [sigs] if isinstance(sigs, torch.Tensor) else list(sigs)
+    if not sigs or not isinstance(sigs[0], torch.Tensor) or sigs[0].ndim != 2:
+        raise RuntimeError("fnssl.scene_power: expected [n, M] signals")
+    n = sigs[0].shape[0] if n is None else int(n)
+    m = sigs[0].shape[1]
+    arr, keep = _scene_rows(sigs, n, m, "scene_power")
+    blocks = torch.empty((max(m * (n // 256), 1),), dtype=torch.float32, device=sigs[0].device)
+    power = torch.empty((m,), dtype=torch.float32, device=sigs[0].device)
+    check(_lib.load().fnssl_scene_power(arr, len(sigs), n, m, _ptr(blocks), blocks.numel(), _ptr(power), _stream()), "scene_power")
+    return power
+
+
+@on_device
+def scene_finish(sigs, noise, p, pn, snr_db: float, n: int, vads=None):
+    """The SNR mix and the VAD (fnssl_scene_finish): sigs / vads lists of [>= n, M], noise [>= n, M], p / pn [M] -> dict with
+    mic [n, M], g [1] and, with vads, vmax [S], vad_sources [n, S] and vad [n] (uint8)."""
+    sigs = list(sigs)
+    _need_dev(noise, p, pn)
+    m = noise.shape[1] if noise.ndim == 2 else -1
+    if noise.ndim != 2 or noise.shape[0] < n or p.shape != (m,) or pn.shape != (m,):
+        raise RuntimeError("fnssl.scene_finish: noise %s, powers %s and %s for n = %d" % (tuple(noise.shape), tuple(p.shape), tuple(pn.shape), n))
+    arr, keep = _scene_rows(sigs, n, m, "scene_finish")
+    noise, p, pn = noise.contiguous(), p.contiguous(), pn.contiguous()
+    dev = noise.device
+    ns = len(sigs)
+    out = {"mic": torch.empty((n, m), dtype=torch.float32, device=dev), "g": torch.empty((1,), dtype=torch.float32, device=dev)}
+    varr = None
+    if vads is not None:
+        if len(vads) != ns:
+            raise RuntimeError("fnssl.scene_finish: %d VAD signals for %d sources" % (len(vads), ns))
+        varr, vkeep = _scene_rows(vads, n, m, "scene_finish")
+        keep += vkeep
+        out["vmax"] = torch.empty((ns,), dtype=torch.float32, device=dev)
+        out["vad_sources"] = torch.empty((n, ns), dtype=torch.uint8, device=dev)
+        out["vad"] = torch.empty((n,), dtype=torch.uint8, device=dev)
+    check(_lib.load().fnssl_scene_finish(arr, ns, _ptr(noise), varr, int(n), m, _ptr(p), _ptr(pn), 10.0 ** (float(snr_db) / 10.0),
+                                         _ptr(out["mic"]), _ptr(out["g"]), _ptr(out.get("vmax")), _ptr(out.get("vad_sources")),
+                                         _ptr(out.get("vad")), _stream()), "scene_finish")
+    return out

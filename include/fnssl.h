@@ -1336,6 +1336,57 @@ typedef struct {
 int fnssl_rir_trajectory(const fnssl_rir_traj_item* items, int nitems, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Scene finish (csrc/scene.hip): diffuse noise field, SNR mix, source VAD   */
+/* ------------------------------------------------------------------------- */
+/* What AcousticScene.simulate() and NoiseDataset.gen_diffuse_noise / mix_signals of the reference's Dataset.py do around the
+ * three gpuRIR calls; fnssl/scene.py carries their names.  The model is DESIGN.md §18.  Every array is a DEVICE array, every
+ * sum has a fixed order and there is no float atomic: two runs give the same bits.
+ *
+ * Arbitrary noise field (Habets): nfft = 256 only (hop 64, periodic Hann), m <= FNSSL_ANF_MAX_MICS; anything else fails with
+ * FNSSL_E_INVALID naming the limit.  FNSSL_ANF_BINS = nfft / 2 + 1.
+ *
+ * fnssl_anf_coherence: mic_pos [nb][m][3] (double) -> dc [nb][m][m][BINS] (double), the spherically isotropic field
+ *   dc[p][q][k] = sinc(2 fs k d_pq / (nfft c)), sinc(x) = sin(pi x) / (pi x), ones on the diagonal.
+ * fnssl_anf_factor: dc -> cfac [nb][MAX_MICS][MAX_MICS][BINS] (float; rows and columns >= m are not touched),
+ *   cfac[..][q][p][k] the UPPER Cholesky factor of dc[..][k] for k >= 1 (dc_k = C_k^T C_k; entries below the diagonal and the
+ *   slot of bin 0 are written as zeros), computed in double by one wave per bin; the bin is the fastest index, which is what
+ *   the lanes of fnssl_anf_mix walk, and the row stride does not depend on m, which keeps its offsets constants.
+ *   status [nb]: 0xffffffff, or the smallest bin of the item whose factorisation met a pivot that is <= 0 or not finite
+ *   (that bin's entries are then unspecified).  fnssl_anf_status copies the words to the host and synchronises.
+ * fnssl_anf_mean: mean [nb] of `count` consecutive floats per item (items `item_stride` floats apart): partial sums over
+ *   chunks of FNSSL_ANF_MEAN_CHUNK elements, added in chunk order.  partial: >= nb * ceil(count / CHUNK) floats.
+ * fnssl_anf_mix: x [nb][len][m] through strides (floats) -> y [nb][len + ((-len) mod 64)][m] contiguous:
+ *   K zeros, x - mean[b] (mean NULL: 0; the padding stays zero), zeros up to a whole number of hops plus K; per frame of 256
+ *   every 64: N_q = rfft(w x_q); X_p[k] = sum_{q <= p} cfac[q][p][k] N_q[k] for k = 1 .. 128, X_p[0] = 0; o_p = irfft(X_p);
+ *   y += w o_p; y / 1.5, samples [K, K + len + pad).  cfac_items = 1: one factor for every item, else nb of them.  One wave
+ *   owns `tile_hops` output hops (0: 2 .. 16, sized so that the launch fills the device) and walks the frames that reach them
+ *   in frame order, starting three frames early from a zero accumulator: the bits do not depend on tile_hops. */
+#define FNSSL_ANF_NFFT 256
+#define FNSSL_ANF_BINS 129
+#define FNSSL_ANF_MAX_MICS 16
+#define FNSSL_ANF_MEAN_CHUNK 16384
+int fnssl_anf_coherence(const double* mic_pos, int nb, int m, double fs, int nfft, double c, double* dc, void* stream);
+int fnssl_anf_factor(const double* dc, int nb, int m, int nfft, float* cfac, unsigned* status, void* stream);
+int fnssl_anf_status(const unsigned* status, int nb, void* stream, unsigned* host_words);
+int fnssl_anf_mean(const float* x, int nb, long long count, long long item_stride, float* partial, size_t partial_floats,
+                   float* mean, void* stream);
+int fnssl_anf_mix(const float* x, long long stride_b, long long stride_n, long long stride_m, const float* mean,
+                  const float* cfac, int cfac_items, int nb, int len, int m, int nfft, int tile_hops, float* y, void* stream);
+/* acoustic_power of every channel of sum_s a[s][0 .. n)[m] (nsum <= FNSSL_SCENE_MAX_SOURCES arrays of >= n rows of m floats,
+ * added in order): mean squares of the windows of 512 every 256 (ceil((n - 511) / 256) of them, each the sum of two
+ * 256-sample block sums), power[m] = mean of those above 0.01 x the largest.  n >= 512.  fp32, fixed trees.
+ * blocks: >= m * (n / 256) floats of scratch. */
+#define FNSSL_SCENE_MAX_SOURCES 4
+int fnssl_scene_power(const float* const* a, int nsum, int n, int m, float* blocks, size_t blocks_floats, float* power,
+                      void* stream);
+/* g = sqrt(mean_m p[m] / snr_lin) / sqrt(mean_m pn[m]) (on the device, written to *g); mic[t][c] = sum_s sig[s][t][c] + g *
+ * noise[t][c] for t < n; with vad_in (ns arrays like sig, else NULL): vmax[s] = max over [0, n) x m of vad_in[s],
+ * vad_sources[t][s] = mean_c vad_in[s][t][c] > 1e-3 vmax[s], vad[t] = any_s (uint8).  ns <= FNSSL_SCENE_MAX_SOURCES. */
+int fnssl_scene_finish(const float* const* sig, int ns, const float* noise, const float* const* vad_in, int n, int m,
+                       const float* p, const float* pn, double snr_lin, float* mic, float* g, float* vmax,
+                       unsigned char* vad_sources, unsigned char* vad, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Measurement hooks (bench.py: per-kernel HIP-event timing on the launch stream) */
 /* ------------------------------------------------------------------------- */
 
