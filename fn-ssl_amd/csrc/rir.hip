@@ -2,6 +2,8 @@
 //   fnssl_rir_ism         image-source part of every (source, receiver) RIR, samples [0, nISM)
 //   fnssl_rir_tail        diffuse tail, samples [nISM, nSamples): decay fitted to the ISM part, logistic noise from Philox4x32-10
 //   fnssl_rir_trajectory  moving-source mixing: y[t, m] = sum_k RIRs[p(t - k), m, k] x[t - k], a batch of them per launch
+//   fnssl_rir_ism_batch / fnssl_rir_tail_batch   the first two for a batch of jobs (one job = one call of each) in one launch
+//                         set: the records travel in the kernel arguments, the kernels share the single forms' bodies
 // Semantics are the published algorithm (Allen & Berkley 1979; Diaz-Guerra, Miguel, Beltran 2021) written from the formulas
 // of DESIGN.md §17; nothing here is bit compatible with gpuRIR and nothing claims to be.
 //
@@ -13,6 +15,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
+#include <vector>
 
 #include "host.h"
 
@@ -51,14 +55,15 @@ __device__ __forceinline__ float lane_f(float v, int j) {
 
 // LDS: tile [nism] | squared coordinate difference per axis image [nx + ny + nz] | reflection amplitude per axis image
 // [nx + ny + nz].  Every index below is bounded by the host's checks: t in [0, nism), axis indices < n[a].
-__global__ void __launch_bounds__(kIsmThreads) rir_ism_kernel(const IsmParams p) {
+// The body of both forms: `p` is the launch's one record (rir_ism_kernel) or the job's record of a descriptor block
+// (rir_ism_batch_kernel); a workgroup is chunk `chunk` of RIR `rir` of that record.
+__device__ __forceinline__ void ism_body(const IsmParams& p, const int chunk, const int rir) {
   extern __shared__ float lds[];
   const int nx = p.n[0], ny = p.n[1], nz = p.n[2];
   float* const tile = lds;
   float* const sq = tile + p.nism;
   float* const am = sq + (nx + ny + nz);
   const int lane = threadIdx.x;
-  const int rir = blockIdx.y;
   const int src = rir / p.m_rcv, rcv = rir - src * p.m_rcv;
 
   for (int i = lane; i < p.nism; i += kIsmThreads) tile[i] = 0.f;
@@ -85,7 +90,7 @@ __global__ void __launch_bounds__(kIsmThreads) rir_ism_kernel(const IsmParams p)
   for (int r = 0; r < kIsmWinRounds; ++r) sincospif(2.f * (float)(lane + 64 * r) / p.tw, &sk[r], &ck[r]);
   __syncthreads();
 
-  const int i0 = blockIdx.x * p.chunk;
+  const int i0 = chunk * p.chunk;
   const int i1 = min(i0 + p.chunk, p.total);
   const float half = 0.5f * p.tw;
   for (int base = i0; base < i1; base += kIsmThreads) {
@@ -131,19 +136,60 @@ __global__ void __launch_bounds__(kIsmThreads) rir_ism_kernel(const IsmParams p)
     }
   }
   __syncthreads();
-  float* const dst = p.out + (long long)blockIdx.x * p.chunk_stride + (long long)rir * p.rir_stride;
+  float* const dst = p.out + (long long)chunk * p.chunk_stride + (long long)rir * p.rir_stride;
   for (int i = lane; i < p.nism; i += kIsmThreads) dst[i] = tile[i];
 }
 
+__global__ void __launch_bounds__(kIsmThreads) rir_ism_kernel(const IsmParams p) { ism_body(p, blockIdx.x, blockIdx.y); }
+
+// One launch for a block of jobs (fnssl_rir_ism_batch).  The records travel by value in the kernel arguments, as
+// TrajParams does; blockIdx.z is the job, the grid is sized for the block's largest job.
+constexpr int kBatchJobs = FNSSL_RIR_BATCH_JOBS;
+
+struct IsmJob {
+  IsmParams p;
+  int nchunks, nrir;
+};
+struct IsmBatchParams {
+  IsmJob job[kBatchJobs];
+};
+static_assert(sizeof(IsmBatchParams) <= 4096, "the block's descriptors travel in the kernel arguments");
+
+__global__ void __launch_bounds__(kIsmThreads) rir_ism_batch_kernel(const IsmBatchParams P) {
+  const IsmJob& j = P.job[blockIdx.z];
+  if ((int)blockIdx.x >= j.nchunks || (int)blockIdx.y >= j.nrir) return;     // (uniform) past the job's extent
+  ism_body(j.p, blockIdx.x, blockIdx.y);
+}
+
 // rir[r][t] = sum over chunks c, in order, of part[c][r][t]
-__global__ void __launch_bounds__(256) rir_sum_kernel(const float* __restrict__ part, int nchunks, int nrir, int nism,
-                                                      float* __restrict__ rir, long long rir_stride) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  const int r = blockIdx.y;
+__device__ __forceinline__ void sum_body(const float* __restrict__ part, int nchunks, int nrir, int nism, float* __restrict__ rir,
+                                         long long rir_stride, const int t, const int r) {
   if (t >= nism) return;
   float v = 0.f;
   for (int c = 0; c < nchunks; ++c) v += part[((size_t)c * nrir + r) * nism + t];
   rir[(long long)r * rir_stride + t] = v;
+}
+
+__global__ void __launch_bounds__(256) rir_sum_kernel(const float* __restrict__ part, int nchunks, int nrir, int nism,
+                                                      float* __restrict__ rir, long long rir_stride) {
+  sum_body(part, nchunks, nrir, nism, rir, rir_stride, blockIdx.x * 256 + threadIdx.x, blockIdx.y);
+}
+
+struct SumJob {
+  const float* part;                                     // the job's own slice of the workspace
+  float* rir;
+  long long rir_stride;
+  int nchunks, nrir, nism;
+};
+struct SumBatchParams {
+  SumJob job[kBatchJobs];
+};
+static_assert(sizeof(SumBatchParams) <= 4096, "the block's descriptors travel in the kernel arguments");
+
+__global__ void __launch_bounds__(256) rir_sum_batch_kernel(const SumBatchParams P) {
+  const SumJob& j = P.job[blockIdx.z];
+  if ((int)blockIdx.y >= j.nrir) return;                 // (uniform); samples past nism leave in the body
+  sum_body(j.part, j.nchunks, j.nrir, j.nism, j.rir, j.rir_stride, blockIdx.x * 256 + threadIdx.x, blockIdx.y);
 }
 
 struct IsmPlan {
@@ -218,12 +264,12 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-__global__ void __launch_bounds__(kTailThreads) rir_tail_kernel(const TailParams p) {
+// The body of both forms: workgroup `tile` of RIR `rir` of the record `p`.
+__device__ __forceinline__ void tail_body(const TailParams& p, const int tile, const int rir) {
   __shared__ float e[kTailMaxSeg];
   __shared__ float part[kTailThreads / 64];
   __shared__ float line[2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int rir = blockIdx.y;
   const int src = rir / p.m_rcv, rcv = rir - src * p.m_rcv;
   float* const h = p.rir + (size_t)rir * p.nsamples;
 
@@ -288,7 +334,7 @@ __global__ void __launch_bounds__(kTailThreads) rir_tail_kernel(const TailParams
   __syncthreads();
   const float a = line[0], b = line[1];
   // four samples per Philox call: counter (t / 4, rcv, src, 0), word t % 4 — whatever the launch geometry
-  const int q0 = (p.nism >> 2) + blockIdx.x * (kTailTile / 4);
+  const int q0 = (p.nism >> 2) + tile * (kTailTile / 4);
   for (int q = q0 + tid; q < q0 + kTailTile / 4; q += kTailThreads) {
     if (4 * q >= p.nsamples) break;
     unsigned w[4];
@@ -303,6 +349,23 @@ __global__ void __launch_bounds__(kTailThreads) rir_tail_kernel(const TailParams
       }
     }
   }
+}
+
+__global__ void __launch_bounds__(kTailThreads) rir_tail_kernel(const TailParams p) { tail_body(p, blockIdx.x, blockIdx.y); }
+
+struct TailJob {
+  TailParams p;
+  int tiles, nrir;
+};
+struct TailBatchParams {
+  TailJob job[kBatchJobs];
+};
+static_assert(sizeof(TailBatchParams) <= 4096, "the block's descriptors travel in the kernel arguments");
+
+__global__ void __launch_bounds__(kTailThreads) rir_tail_batch_kernel(const TailBatchParams P) {
+  const TailJob& j = P.job[blockIdx.z];
+  if ((int)blockIdx.x >= j.tiles || (int)blockIdx.y >= j.nrir) return;       // (uniform) past the job's extent
+  tail_body(j.p, blockIdx.x, blockIdx.y);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -396,6 +459,78 @@ int check_geometry(const char* who, const float* room, const float* beta, const 
   return FNSSL_OK;
 }
 
+// The checks of fnssl_rir_ism and the record of its launch for a single-chunk plan (the RIR is the output); `who` names the
+// call, and for a batch the job.  cus <= 0 asks the current device.
+int prepare_ism(const char* who, const float* room_sz, const float* beta, const float* pos_src, int m_src, const float* pos_rcv,
+                int m_rcv, const int* nb_img, int nism, int nsamples, double fs, double c, float* rir, int cus, IsmParams* out,
+                IsmPlan* pl) {
+  FNSSL_TRY(check_geometry(who, room_sz, beta, pos_src, pos_rcv, fs, c));
+  FNSSL_REQUIRE(rir, "%s: null pointer", who);
+  FNSSL_TRY(plan_ism(who, m_src, m_rcv, nb_img, nism, cus, pl));
+  FNSSL_REQUIRE(nsamples >= nism, "%s: nSamples %d < nISM %d", who, nsamples, nism);
+  const double tw = 8e-3 * fs;
+  FNSSL_REQUIRE(tw >= 2.0 && tw + 1.0 <= 64.0 * kIsmWinRounds, "%s: a window of %g samples (2 .. %d: fs from 250 Hz to 63.8 kHz)", who,
+                tw, 64 * kIsmWinRounds - 1);
+  IsmParams p{};
+  p.pos_src = pos_src;
+  p.pos_rcv = pos_rcv;
+  for (int a = 0; a < 3; ++a) p.room[a] = room_sz[a], p.n[a] = nb_img[a];
+  for (int w = 0; w < 6; ++w) p.beta[w] = beta[w];
+  p.m_rcv = m_rcv;
+  p.nism = nism;
+  p.chunk = pl->chunk;
+  p.total = pl->total;
+  p.fs_over_c = (float)(fs / c);
+  p.tw = (float)tw;
+  p.out = rir;
+  p.rir_stride = nsamples;
+  p.chunk_stride = 0;
+  *out = p;
+  return FNSSL_OK;
+}
+
+// several chunks: the partial tiles go to part [chunk][rir][nism]
+void ism_to_workspace(IsmParams* p, float* part, int nrir) {
+  p->out = part;
+  p->rir_stride = p->nism;
+  p->chunk_stride = (long long)nrir * p->nism;
+}
+
+// The checks of fnssl_rir_tail, its record and its grid's x (unused when nsamples == nism: there is no tail).
+int prepare_tail(const char* who, const float* room_sz, const float* beta, const float* pos_src, int m_src, const float* pos_rcv,
+                 int m_rcv, int nism, int nsamples, double fs, double c, unsigned long long seed, float* rir, TailParams* out,
+                 unsigned* gx) {
+  FNSSL_TRY(check_geometry(who, room_sz, beta, pos_src, pos_rcv, fs, c));
+  FNSSL_REQUIRE(rir, "%s: null pointer", who);
+  FNSSL_REQUIRE(m_src >= 1 && m_rcv >= 1 && (long long)m_src * m_rcv <= 65535, "%s: %d sources x %d receivers (1 .. 65535 RIRs)", who,
+                m_src, m_rcv);
+  FNSSL_REQUIRE(nism >= 2 && nism % 2 == 0 && nism <= kIsmMaxSamples, "%s: nISM = %d samples (even, 2 .. %d)", who, nism, kIsmMaxSamples);
+  FNSSL_REQUIRE(nsamples >= nism && nsamples % 2 == 0 && nsamples < (1 << 30), "%s: nSamples = %d (even, nISM %d .. 2^30)", who,
+                nsamples, nism);
+  const int ls = (int)std::lround(8e-3 * fs);
+  FNSSL_REQUIRE(ls >= kTailMinSeg, "%s: a segment of %d samples (at least %d: fs >= 1 kHz)", who, ls, kTailMinSeg);
+  const double vol = (double)room_sz[0] * room_sz[1] * room_sz[2];
+  const double area[3] = {(double)room_sz[1] * room_sz[2], (double)room_sz[0] * room_sz[2], (double)room_sz[0] * room_sz[1]};
+  double absorb = 0.0;
+  for (int w = 0; w < 6; ++w) absorb += area[w / 2] * (1.0 - (double)beta[w] * beta[w]);
+  TailParams p{};
+  p.rir = rir;
+  p.pos_src = pos_src;
+  p.pos_rcv = pos_rcv;
+  p.m_rcv = m_rcv;
+  p.nism = nism;
+  p.nsamples = nsamples;
+  p.ls = ls;
+  p.fs_over_c = (float)(fs / c);
+  p.b_sabine = absorb > 0.0 ? (float)(-std::log(1e6) / (0.161 * vol / absorb * fs)) : 0.f;
+  p.seed_lo = (unsigned)(seed & 0xffffffffull);
+  p.seed_hi = (unsigned)(seed >> 32);
+  const int quads = ((nsamples + 3) >> 2) - (nism >> 2);
+  *gx = (unsigned)((quads + kTailTile / 4 - 1) / (kTailTile / 4));
+  *out = p;
+  return FNSSL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -424,36 +559,14 @@ size_t fnssl_rir_workspace_bytes(int m_src, int m_rcv, const int* nb_img, int ni
 int fnssl_rir_ism(const float* room_sz, const float* beta, const float* pos_src, int m_src, const float* pos_rcv, int m_rcv,
                   const int* nb_img, int nism, int nsamples, double fs, double c, float* rir, void* workspace,
                   size_t workspace_bytes, void* stream) {
-  FNSSL_TRY(check_geometry("rir_ism", room_sz, beta, pos_src, pos_rcv, fs, c));
-  FNSSL_REQUIRE(rir, "rir_ism: null pointer");
-  IsmPlan pl;
-  FNSSL_TRY(plan_ism("rir_ism", m_src, m_rcv, nb_img, nism, 0, &pl));
-  FNSSL_REQUIRE(nsamples >= nism, "rir_ism: nSamples %d < nISM %d", nsamples, nism);
-  const double tw = 8e-3 * fs;
-  FNSSL_REQUIRE(tw >= 2.0 && tw + 1.0 <= 64.0 * kIsmWinRounds, "rir_ism: a window of %g samples (2 .. %d: fs from 250 Hz to 63.8 kHz)",
-                tw, 64 * kIsmWinRounds - 1);
-  const int nrir = m_src * m_rcv;
   IsmParams p{};
-  p.pos_src = pos_src;
-  p.pos_rcv = pos_rcv;
-  for (int a = 0; a < 3; ++a) p.room[a] = room_sz[a], p.n[a] = nb_img[a];
-  for (int w = 0; w < 6; ++w) p.beta[w] = beta[w];
-  p.m_rcv = m_rcv;
-  p.nism = nism;
-  p.chunk = pl.chunk;
-  p.total = pl.total;
-  p.fs_over_c = (float)(fs / c);
-  p.tw = (float)tw;
+  IsmPlan pl;
+  FNSSL_TRY(prepare_ism("rir_ism", room_sz, beta, pos_src, m_src, pos_rcv, m_rcv, nb_img, nism, nsamples, fs, c, rir, 0, &p, &pl));
+  const int nrir = m_src * m_rcv;
   if (pl.nchunks > 1) {
     const size_t need = (size_t)pl.nchunks * nrir * nism * sizeof(float);
     FNSSL_TRY(fnssl::check_workspace("rir_ism", workspace, workspace_bytes, need));
-    p.out = static_cast<float*>(workspace);
-    p.rir_stride = nism;
-    p.chunk_stride = (long long)nrir * nism;
-  } else {
-    p.out = rir;
-    p.rir_stride = nsamples;
-    p.chunk_stride = 0;
+    ism_to_workspace(&p, static_cast<float*>(workspace), nrir);
   }
   hipStream_t s = fnssl::as_stream(stream);
   {
@@ -470,37 +583,139 @@ int fnssl_rir_ism(const float* room_sz, const float* beta, const float* pos_src,
 
 int fnssl_rir_tail(const float* room_sz, const float* beta, const float* pos_src, int m_src, const float* pos_rcv, int m_rcv,
                    int nism, int nsamples, double fs, double c, unsigned long long seed, float* rir, void* stream) {
-  FNSSL_TRY(check_geometry("rir_tail", room_sz, beta, pos_src, pos_rcv, fs, c));
-  FNSSL_REQUIRE(rir, "rir_tail: null pointer");
-  FNSSL_REQUIRE(m_src >= 1 && m_rcv >= 1 && (long long)m_src * m_rcv <= 65535, "rir_tail: %d sources x %d receivers (1 .. 65535 RIRs)",
-                m_src, m_rcv);
-  FNSSL_REQUIRE(nism >= 2 && nism % 2 == 0 && nism <= kIsmMaxSamples, "rir_tail: nISM = %d samples (even, 2 .. %d)", nism, kIsmMaxSamples);
-  FNSSL_REQUIRE(nsamples >= nism && nsamples % 2 == 0 && nsamples < (1 << 30), "rir_tail: nSamples = %d (even, nISM %d .. 2^30)",
-                nsamples, nism);
-  const int ls = (int)std::lround(8e-3 * fs);
-  FNSSL_REQUIRE(ls >= kTailMinSeg, "rir_tail: a segment of %d samples (at least %d: fs >= 1 kHz)", ls, kTailMinSeg);
-  if (nsamples == nism) return FNSSL_OK;
-  const double vol = (double)room_sz[0] * room_sz[1] * room_sz[2];
-  const double area[3] = {(double)room_sz[1] * room_sz[2], (double)room_sz[0] * room_sz[2], (double)room_sz[0] * room_sz[1]};
-  double absorb = 0.0;
-  for (int w = 0; w < 6; ++w) absorb += area[w / 2] * (1.0 - (double)beta[w] * beta[w]);
   TailParams p{};
-  p.rir = rir;
-  p.pos_src = pos_src;
-  p.pos_rcv = pos_rcv;
-  p.m_rcv = m_rcv;
-  p.nism = nism;
-  p.nsamples = nsamples;
-  p.ls = ls;
-  p.fs_over_c = (float)(fs / c);
-  p.b_sabine = absorb > 0.0 ? (float)(-std::log(1e6) / (0.161 * vol / absorb * fs)) : 0.f;
-  p.seed_lo = (unsigned)(seed & 0xffffffffull);
-  p.seed_hi = (unsigned)(seed >> 32);
-  const int quads = ((nsamples + 3) >> 2) - (nism >> 2);
-  const unsigned gx = (unsigned)((quads + kTailTile / 4 - 1) / (kTailTile / 4));
+  unsigned gx = 0;
+  FNSSL_TRY(prepare_tail("rir_tail", room_sz, beta, pos_src, m_src, pos_rcv, m_rcv, nism, nsamples, fs, c, seed, rir, &p, &gx));
+  if (nsamples == nism) return FNSSL_OK;
   hipStream_t s = fnssl::as_stream(stream);
   fnssl::TimedLaunch tl("rir_tail", s);
   return enqueue(s, Kernel{rir_tail_kernel, kTailThreads, 0, "rir_tail_kernel"}, dim3(gx, (unsigned)(m_src * m_rcv)), p);
+}
+
+// ---- a batch of jobs: every job is checked and planned first, then ceil(njobs / FNSSL_RIR_BATCH_JOBS) launch sets ----------
+int fnssl_rir_batch_plan(const fnssl_rir_job* jobs, int njobs, int cus, fnssl_rir_job_plan* out) {
+  FNSSL_REQUIRE(jobs && out && njobs >= 1, "rir_batch_plan: null pointer / no job");
+  if (cus <= 0) cus = fnssl::device_cus();               // once: every job is planned for the same device
+  size_t off = 0;
+  for (int k = 0; k < njobs; ++k) {
+    const fnssl_rir_job& j = jobs[k];
+    char who[48];
+    std::snprintf(who, sizeof who, "rir_batch_plan: job %d", k);
+    IsmPlan pl;
+    FNSSL_TRY(plan_ism(who, j.m_src, j.m_rcv, j.nb_img, j.nism, cus, &pl));
+    fnssl_rir_plan_info& pi = out[k].plan;
+    pi.images = pl.total;
+    pi.chunk_images = pl.chunk;
+    pi.nchunks = pl.nchunks;
+    pi.last_chunk_images = pl.last;
+    pi.grid_x = pl.nchunks;
+    pi.grid_y = j.m_src * j.m_rcv;
+    pi.threads = kIsmThreads;
+    pi.lds_bytes = (int)pl.lds;
+    pi.workspace_bytes = pl.nchunks > 1 ? (size_t)pl.nchunks * j.m_src * j.m_rcv * j.nism * sizeof(float) : 0;
+    out[k].workspace_offset = off;
+    off += pi.workspace_bytes;
+  }
+  return FNSSL_OK;
+}
+
+size_t fnssl_rir_batch_workspace_bytes(const fnssl_rir_job* jobs, int njobs, int cus) {
+  if (!jobs || njobs < 1) return 0;
+  if (cus <= 0) cus = fnssl::device_cus();
+  size_t total = 0;
+  for (int k = 0; k < njobs; ++k) {
+    const fnssl_rir_job& j = jobs[k];
+    total += fnssl_rir_workspace_bytes(j.m_src, j.m_rcv, j.nb_img, j.nism, cus);
+  }
+  return total;
+}
+
+int fnssl_rir_ism_batch(const fnssl_rir_job* jobs, int njobs, void* workspace, size_t workspace_bytes, void* stream) {
+  FNSSL_REQUIRE(jobs && njobs >= 1, "rir_ism_batch: null pointer / no job");
+  std::vector<IsmJob> ij((size_t)njobs);
+  std::vector<IsmPlan> pls((size_t)njobs);
+  std::vector<size_t> offs((size_t)njobs);
+  const int cus = fnssl::device_cus();
+  size_t need = 0;
+  for (int k = 0; k < njobs; ++k) {                      // every check of every job before the first launch
+    const fnssl_rir_job& j = jobs[k];
+    char who[48];
+    std::snprintf(who, sizeof who, "rir_ism_batch: job %d", k);
+    FNSSL_TRY(prepare_ism(who, j.room_sz, j.beta, j.pos_src, j.m_src, j.pos_rcv, j.m_rcv, j.nb_img, j.nism, j.nsamples, j.fs,
+                          j.c, j.rir, cus, &ij[k].p, &pls[k]));
+    ij[k].nchunks = pls[k].nchunks;
+    ij[k].nrir = j.m_src * j.m_rcv;
+    offs[k] = need;
+    if (pls[k].nchunks > 1) need += (size_t)pls[k].nchunks * ij[k].nrir * j.nism * sizeof(float);
+  }
+  if (need) FNSSL_TRY(fnssl::check_workspace("rir_ism_batch", workspace, workspace_bytes, need));
+  for (int k = 0; k < njobs; ++k)
+    if (pls[k].nchunks > 1) ism_to_workspace(&ij[k].p, reinterpret_cast<float*>(static_cast<char*>(workspace) + offs[k]), ij[k].nrir);
+
+  hipStream_t s = fnssl::as_stream(stream);
+  for (int k0 = 0; k0 < njobs; k0 += kBatchJobs) {
+    const int nb = std::min(kBatchJobs, njobs - k0);
+    IsmBatchParams P{};
+    SumBatchParams S{};
+    dim3 grid(1, 1, (unsigned)nb), sgrid(1, 1, 0);
+    size_t lds = 0;                                      // dynamic LDS is per launch: the block's largest tile
+    for (int k = 0; k < nb; ++k) {
+      const IsmJob& j = ij[k0 + k];
+      P.job[k] = j;
+      grid.x = std::max(grid.x, (unsigned)j.nchunks);
+      grid.y = std::max(grid.y, (unsigned)j.nrir);
+      lds = std::max(lds, pls[k0 + k].lds);
+      if (j.nchunks > 1) {
+        const fnssl_rir_job& job = jobs[k0 + k];
+        S.job[sgrid.z++] = SumJob{j.p.out, job.rir, (long long)job.nsamples, j.nchunks, j.nrir, job.nism};
+        sgrid.x = std::max(sgrid.x, (unsigned)((job.nism + 255) / 256));
+        sgrid.y = std::max(sgrid.y, (unsigned)j.nrir);
+      }
+    }
+    {
+      fnssl::TimedLaunch tl("rir_ism_batch", s);
+      FNSSL_TRY(enqueue(s, Kernel{rir_ism_batch_kernel, kIsmThreads, lds, "rir_ism_batch_kernel"}, grid, P));
+    }
+    if (sgrid.z) {
+      fnssl::TimedLaunch tl("rir_sum_batch", s);
+      FNSSL_TRY(enqueue(s, Kernel{rir_sum_batch_kernel, 256, 0, "rir_sum_batch_kernel"}, sgrid, S));
+    }
+  }
+  return FNSSL_OK;
+}
+
+int fnssl_rir_tail_batch(const fnssl_rir_job* jobs, int njobs, void* stream) {
+  FNSSL_REQUIRE(jobs && njobs >= 1, "rir_tail_batch: null pointer / no job");
+  std::vector<TailJob> tj;
+  tj.reserve((size_t)njobs);
+  for (int k = 0; k < njobs; ++k) {                      // every check of every job before the first launch
+    const fnssl_rir_job& j = jobs[k];
+    char who[48];
+    std::snprintf(who, sizeof who, "rir_tail_batch: job %d", k);
+    TailJob t{};
+    unsigned gx = 0;
+    FNSSL_TRY(prepare_tail(who, j.room_sz, j.beta, j.pos_src, j.m_src, j.pos_rcv, j.m_rcv, j.nism, j.nsamples, j.fs, j.c, j.seed,
+                           j.rir, &t.p, &gx));
+    if (j.nsamples == j.nism) continue;                  // no tail: the job takes no slot
+    t.tiles = (int)gx;
+    t.nrir = j.m_src * j.m_rcv;
+    tj.push_back(t);
+  }
+  hipStream_t s = fnssl::as_stream(stream);
+  const int n = (int)tj.size();
+  for (int k0 = 0; k0 < n; k0 += kBatchJobs) {
+    const int nb = std::min(kBatchJobs, n - k0);
+    TailBatchParams P{};
+    dim3 grid(1, 1, (unsigned)nb);
+    for (int k = 0; k < nb; ++k) {
+      P.job[k] = tj[k0 + k];
+      grid.x = std::max(grid.x, (unsigned)P.job[k].tiles);
+      grid.y = std::max(grid.y, (unsigned)P.job[k].nrir);
+    }
+    fnssl::TimedLaunch tl("rir_tail_batch", s);
+    FNSSL_TRY(enqueue(s, Kernel{rir_tail_batch_kernel, kTailThreads, 0, "rir_tail_batch_kernel"}, grid, P));
+  }
+  return FNSSL_OK;
 }
 
 int fnssl_rir_trajectory(const fnssl_rir_traj_item* items, int nitems, void* stream) {

@@ -6,6 +6,7 @@
 //   fnssl_anf_mix         STFT -> triangular per-bin mix -> iSTFT -> overlap-add, one kernel, no spectrum in HBM
 //   fnssl_scene_power     acoustic_power of every channel of a sum of signals
 //   fnssl_scene_finish    SNR gain on the device, mic = sum of sources + g noise, per-source VAD
+//   fnssl_scene_power_batch / fnssl_scene_finish_batch   the last two for a batch of scenes in one launch set
 //
 // Determinism.  No float atomics.  Mix: a workgroup is ONE wave; it owns a run of output hops and walks the frames that reach
 // them in frame order, three frames early from a zero accumulator, so every output hop is ((0 + f0) + f1) + f2) + f3 whatever
@@ -14,6 +15,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
+#include <vector>
 
 #include "frontend_core.h"
 #include "host.h"
@@ -299,10 +302,10 @@ struct SumPtrs {
 };
 
 // grid (n / 256), 256 threads: blocks[c][j] = sum over the 256 samples of block j of (sum_s a_s[t][c])^2
-__global__ void __launch_bounds__(256) scene_block_sums_kernel(const SumPtrs P, int nsum, int m, int nblk, float* __restrict__ blocks) {
+__device__ __forceinline__ void block_sums_body(const SumPtrs& P, int nsum, int m, int nblk, float* __restrict__ blocks, const int j) {
 #pragma clang fp contract(off)
   __shared__ float part[4];
-  const int tid = threadIdx.x, j = blockIdx.x;
+  const int tid = threadIdx.x;
   const size_t row = ((size_t)j * 256 + tid) * m;
   for (int c = 0; c < m; ++c) {
     float v = P.a[0][row + c];
@@ -315,12 +318,37 @@ __global__ void __launch_bounds__(256) scene_block_sums_kernel(const SumPtrs P, 
   }
 }
 
+__global__ void __launch_bounds__(256) scene_block_sums_kernel(const SumPtrs P, int nsum, int m, int nblk, float* __restrict__ blocks) {
+  block_sums_body(P, nsum, m, nblk, blocks, blockIdx.x);
+}
+
+// A batch (fnssl_scene_power_batch): the records travel by value in the kernel arguments, blockIdx.y is the record.  A scene
+// is two records, its direct-path signals over n rows and its noise over its own length.
+constexpr int kBatchScenes = FNSSL_SCENE_BATCH_SCENES;
+
+struct PowerJob {
+  SumPtrs a;
+  float* blocks;                                         // [m][nblk] of this record
+  float* power;                                          // [m]
+  int nsum, nblk;
+};
+struct PowerBatchParams {
+  PowerJob job[2 * kBatchScenes];
+};
+static_assert(sizeof(PowerBatchParams) <= 4096, "the block's descriptors travel in the kernel arguments");
+
+__global__ void __launch_bounds__(256) scene_block_sums_batch_kernel(const PowerBatchParams P, int m) {
+  const PowerJob& j = P.job[blockIdx.y];
+  if ((int)blockIdx.x >= j.nblk) return;                 // (uniform) the grid is sized for the longest record
+  block_sums_body(j.a, j.nsum, m, j.nblk, j.blocks, blockIdx.x);
+}
+
 // grid m, 256 threads: window j = blocks j and j + 1
-__global__ void __launch_bounds__(256) scene_power_kernel(const float* __restrict__ blocks, int nblk, int nwin, float* __restrict__ power) {
+__device__ __forceinline__ void power_body(const float* __restrict__ blocks, int nblk, int nwin, float* __restrict__ power, const int c) {
 #pragma clang fp contract(off)
   __shared__ float part[4], cnt[4];
   const int tid = threadIdx.x;
-  const float* const bs = blocks + (size_t)blockIdx.x * nblk;
+  const float* const bs = blocks + (size_t)c * nblk;
   float mx = 0.f;
   for (int j = tid; j < nwin; j += 256) mx = fmaxf(mx, (bs[j] + bs[j + 1]) * (1.f / 512.f));
   mx = wave_max(mx);
@@ -340,17 +368,26 @@ __global__ void __launch_bounds__(256) scene_power_kernel(const float* __restric
   num = wave_sum(num);
   if ((tid & 63) == 0) part[tid >> 6] = sum, cnt[tid >> 6] = num;
   __syncthreads();
-  if (tid == 0) power[blockIdx.x] = (((part[0] + part[1]) + part[2]) + part[3]) / (((cnt[0] + cnt[1]) + cnt[2]) + cnt[3]);
+  if (tid == 0) power[c] = (((part[0] + part[1]) + part[2]) + part[3]) / (((cnt[0] + cnt[1]) + cnt[2]) + cnt[3]);
+}
+
+__global__ void __launch_bounds__(256) scene_power_kernel(const float* __restrict__ blocks, int nblk, int nwin, float* __restrict__ power) {
+  power_body(blocks, nblk, nwin, power, blockIdx.x);
+}
+
+__global__ void __launch_bounds__(256) scene_power_batch_kernel(const PowerBatchParams P) {
+  const PowerJob& j = P.job[blockIdx.y];
+  power_body(j.blocks, j.nblk, j.nblk - 1, j.power, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // finish
 // ---------------------------------------------------------------------------------------------------------------------------
 // grid ns, 1024 threads: vmax[s] = max of vad_in[s][0 .. n)[0 .. m)
-__global__ void __launch_bounds__(1024) scene_vmax_kernel(const SumPtrs V, long long count, float* __restrict__ vmax) {
+__device__ __forceinline__ void vmax_body(const SumPtrs& V, long long count, float* __restrict__ vmax, const int s) {
   __shared__ float part[16];
   const int tid = threadIdx.x;
-  const float* const v = V.a[blockIdx.x];
+  const float* const v = V.a[s];
   float mx = -INFINITY;
   for (long long i = tid; i < count; i += 1024) mx = fmaxf(mx, v[i]);
   mx = wave_max(mx);
@@ -359,8 +396,12 @@ __global__ void __launch_bounds__(1024) scene_vmax_kernel(const SumPtrs V, long 
   if (tid == 0) {
     float r = part[0];
     for (int w = 1; w < 16; ++w) r = fmaxf(r, part[w]);
-    vmax[blockIdx.x] = r;
+    vmax[s] = r;
   }
+}
+
+__global__ void __launch_bounds__(1024) scene_vmax_kernel(const SumPtrs V, long long count, float* __restrict__ vmax) {
+  vmax_body(V, count, vmax, blockIdx.x);
 }
 
 struct FinishParams {
@@ -378,9 +419,8 @@ struct FinishParams {
 };
 
 // one thread per sample t: its m channels, then its VADs
-__global__ void __launch_bounds__(256) scene_finish_kernel(const FinishParams P) {
+__device__ __forceinline__ void finish_body(const FinishParams& P, const int t) {
 #pragma clang fp contract(off)
-  const int t = blockIdx.x * 256 + threadIdx.x;
   float sp = P.p[0], sn = P.pn[0];
   for (int c = 1; c < P.m; ++c) sp += P.p[c], sn += P.pn[c];
   const float g = sqrtf((sp / (float)P.m) / P.snr_lin) / sqrtf(sn / (float)P.m);
@@ -405,10 +445,83 @@ __global__ void __launch_bounds__(256) scene_finish_kernel(const FinishParams P)
   }
 }
 
+__global__ void __launch_bounds__(256) scene_finish_kernel(const FinishParams P) { finish_body(P, blockIdx.x * 256 + threadIdx.x); }
+
+// A batch (fnssl_scene_finish_batch): one record per scene, blockIdx.y is the scene.
+struct FinishBatchParams {
+  FinishParams job[kBatchScenes];
+};
+static_assert(sizeof(FinishBatchParams) <= 4096, "the block's descriptors travel in the kernel arguments");
+
+// grid (FNSSL_SCENE_MAX_SOURCES, scenes)
+__global__ void __launch_bounds__(1024) scene_vmax_batch_kernel(const FinishBatchParams P) {
+  const FinishParams& j = P.job[blockIdx.y];
+  if (!j.with_vad || (int)blockIdx.x >= j.ns) return;    // (uniform)
+  vmax_body(j.vad_in, (long long)j.n * j.m, const_cast<float*>(j.vmax), blockIdx.x);
+}
+
+__global__ void __launch_bounds__(256) scene_finish_batch_kernel(const FinishBatchParams P) {
+  finish_body(P.job[blockIdx.y], blockIdx.x * 256 + threadIdx.x);
+}
+
 int check_anf(const char* who, int nb, int m, int nfft) {
   FNSSL_REQUIRE(nfft == FNSSL_ANF_NFFT, "%s: nfft = %d (only %d is built)", who, nfft, FNSSL_ANF_NFFT);
   FNSSL_REQUIRE(m >= 1 && m <= kMaxMics, "%s: %d microphones (1 .. %d)", who, m, kMaxMics);
   FNSSL_REQUIRE(nb >= 1 && nb <= 65535, "%s: %d items (1 .. 65535)", who, nb);
+  return FNSSL_OK;
+}
+
+// The checks of fnssl_scene_power and its record; `who` names the call, and for a batch the scene.
+int prepare_power(const char* who, const float* const* a, int nsum, int n, int m, float* blocks, size_t blocks_floats, float* power,
+                  PowerJob* out) {
+  FNSSL_REQUIRE(a && blocks && power, "%s: null pointer", who);
+  FNSSL_REQUIRE(nsum >= 1 && nsum <= FNSSL_SCENE_MAX_SOURCES, "%s: %d summands (1 .. %d)", who, nsum, FNSSL_SCENE_MAX_SOURCES);
+  FNSSL_REQUIRE(n >= 512, "%s: %d samples (acoustic_power needs one window of 512)", who, n);
+  FNSSL_REQUIRE(n < (1 << 30) && m >= 1 && m <= 65535, "%s: %d samples, %d channels", who, n, m);
+  const int nblk = n / 256;                              // windows: ceil((n - 511) / 256) = floor(n / 256) - 1 for n >= 512
+  FNSSL_REQUIRE(blocks_floats >= (size_t)m * nblk, "%s: %zu floats of scratch, %zu needed", who, blocks_floats, (size_t)m * nblk);
+  PowerJob j{};
+  for (int s = 0; s < nsum; ++s) {
+    FNSSL_REQUIRE(a[s], "%s: summand %d is null", who, s);
+    j.a.a[s] = a[s];
+  }
+  j.blocks = blocks;
+  j.power = power;
+  j.nsum = nsum;
+  j.nblk = nblk;
+  *out = j;
+  return FNSSL_OK;
+}
+
+// The checks of fnssl_scene_finish and its record.
+int prepare_finish(const char* who, const float* const* sig, int ns, const float* noise, const float* const* vad_in, int n, int m,
+                   const float* p, const float* pn, double snr_lin, float* mic, float* g, float* vmax, unsigned char* vad_sources,
+                   unsigned char* vad, FinishParams* out) {
+  FNSSL_REQUIRE(sig && noise && p && pn && mic && g, "%s: null pointer", who);
+  FNSSL_REQUIRE(ns >= 1 && ns <= FNSSL_SCENE_MAX_SOURCES, "%s: %d sources (1 .. %d)", who, ns, FNSSL_SCENE_MAX_SOURCES);
+  FNSSL_REQUIRE(n >= 1 && n < (1 << 30) && m >= 1 && m <= 65535, "%s: %d samples, %d channels", who, n, m);
+  FNSSL_REQUIRE(snr_lin > 0.0 && std::isfinite(snr_lin), "%s: SNR ratio %g", who, snr_lin);
+  FNSSL_REQUIRE(!vad_in || (vmax && vad_sources && vad), "%s: VAD inputs without VAD outputs", who);
+  FinishParams P{};
+  for (int s = 0; s < ns; ++s) {
+    FNSSL_REQUIRE(sig[s] && (!vad_in || vad_in[s]), "%s: source %d is null", who, s);
+    P.sig.a[s] = sig[s];
+    if (vad_in) P.vad_in.a[s] = vad_in[s];
+  }
+  P.noise = noise;
+  P.p = p;
+  P.pn = pn;
+  P.vmax = vmax;
+  P.mic = mic;
+  P.g = g;
+  P.vad_sources = vad_sources;
+  P.vad = vad;
+  P.snr_lin = (float)snr_lin;
+  P.ns = ns;
+  P.n = n;
+  P.m = m;
+  P.with_vad = vad_in ? 1 : 0;
+  *out = P;
   return FNSSL_OK;
 }
 
@@ -497,56 +610,78 @@ int fnssl_anf_mix(const float* x, long long stride_b, long long stride_n, long l
 
 int fnssl_scene_power(const float* const* a, int nsum, int n, int m, float* blocks, size_t blocks_floats, float* power,
                       void* stream) {
-  FNSSL_REQUIRE(a && blocks && power, "scene_power: null pointer");
-  FNSSL_REQUIRE(nsum >= 1 && nsum <= FNSSL_SCENE_MAX_SOURCES, "scene_power: %d summands (1 .. %d)", nsum, FNSSL_SCENE_MAX_SOURCES);
-  FNSSL_REQUIRE(n >= 512, "scene_power: %d samples (acoustic_power needs one window of 512)", n);
-  FNSSL_REQUIRE(n < (1 << 30) && m >= 1 && m <= 65535, "scene_power: %d samples, %d channels", n, m);
-  const int nblk = n / 256, nwin = nblk - 1;             // ceil((n - 511) / 256) = floor(n / 256) - 1 for n >= 512
-  FNSSL_REQUIRE(blocks_floats >= (size_t)m * nblk, "scene_power: %zu floats of scratch, %zu needed", blocks_floats, (size_t)m * nblk);
-  SumPtrs P{};
-  for (int s = 0; s < nsum; ++s) {
-    FNSSL_REQUIRE(a[s], "scene_power: summand %d is null", s);
-    P.a[s] = a[s];
-  }
+  PowerJob j{};
+  FNSSL_TRY(prepare_power("scene_power", a, nsum, n, m, blocks, blocks_floats, power, &j));
   hipStream_t s = fnssl::as_stream(stream);
   fnssl::TimedLaunch tl("scene_power", s);
-  FNSSL_TRY(enqueue(s, Kernel{scene_block_sums_kernel, 256, 0, "scene_block_sums_kernel"}, dim3((unsigned)nblk), P, nsum, m, nblk, blocks));
-  return enqueue(s, Kernel{scene_power_kernel, 256, 0, "scene_power_kernel"}, dim3((unsigned)m), static_cast<const float*>(blocks), nblk,
-                 nwin, power);
+  FNSSL_TRY(enqueue(s, Kernel{scene_block_sums_kernel, 256, 0, "scene_block_sums_kernel"}, dim3((unsigned)j.nblk), j.a, nsum, m, j.nblk, blocks));
+  return enqueue(s, Kernel{scene_power_kernel, 256, 0, "scene_power_kernel"}, dim3((unsigned)m), static_cast<const float*>(blocks), j.nblk,
+                 j.nblk - 1, power);
 }
 
 int fnssl_scene_finish(const float* const* sig, int ns, const float* noise, const float* const* vad_in, int n, int m,
                        const float* p, const float* pn, double snr_lin, float* mic, float* g, float* vmax,
                        unsigned char* vad_sources, unsigned char* vad, void* stream) {
-  FNSSL_REQUIRE(sig && noise && p && pn && mic && g, "scene_finish: null pointer");
-  FNSSL_REQUIRE(ns >= 1 && ns <= FNSSL_SCENE_MAX_SOURCES, "scene_finish: %d sources (1 .. %d)", ns, FNSSL_SCENE_MAX_SOURCES);
-  FNSSL_REQUIRE(n >= 1 && n < (1 << 30) && m >= 1 && m <= 65535, "scene_finish: %d samples, %d channels", n, m);
-  FNSSL_REQUIRE(snr_lin > 0.0 && std::isfinite(snr_lin), "scene_finish: SNR ratio %g", snr_lin);
-  FNSSL_REQUIRE(!vad_in || (vmax && vad_sources && vad), "scene_finish: VAD inputs without VAD outputs");
   FinishParams P{};
-  for (int s = 0; s < ns; ++s) {
-    FNSSL_REQUIRE(sig[s] && (!vad_in || vad_in[s]), "scene_finish: source %d is null", s);
-    P.sig.a[s] = sig[s];
-    if (vad_in) P.vad_in.a[s] = vad_in[s];
-  }
-  P.noise = noise;
-  P.p = p;
-  P.pn = pn;
-  P.vmax = vmax;
-  P.mic = mic;
-  P.g = g;
-  P.vad_sources = vad_sources;
-  P.vad = vad;
-  P.snr_lin = (float)snr_lin;
-  P.ns = ns;
-  P.n = n;
-  P.m = m;
-  P.with_vad = vad_in ? 1 : 0;
+  FNSSL_TRY(prepare_finish("scene_finish", sig, ns, noise, vad_in, n, m, p, pn, snr_lin, mic, g, vmax, vad_sources, vad, &P));
   hipStream_t s = fnssl::as_stream(stream);
   fnssl::TimedLaunch tl("scene_finish", s);
   if (vad_in)
     FNSSL_TRY(enqueue(s, Kernel{scene_vmax_kernel, 1024, 0, "scene_vmax_kernel"}, dim3((unsigned)ns), P.vad_in, (long long)n * m, vmax));
   return enqueue(s, Kernel{scene_finish_kernel, 256, 0, "scene_finish_kernel"}, dim3((unsigned)((n + 255) / 256)), P);
+}
+
+// ---- a batch of scenes: every scene is checked first, then ceil(nscenes / FNSSL_SCENE_BATCH_SCENES) launch sets ------------
+int fnssl_scene_power_batch(const fnssl_scene_desc* scenes, int nscenes, int n, int m, void* stream) {
+  FNSSL_REQUIRE(scenes && nscenes >= 1, "scene_power_batch: null pointer / no scene");
+  std::vector<PowerJob> jobs((size_t)2 * nscenes);
+  for (int b = 0; b < nscenes; ++b) {
+    const fnssl_scene_desc& d = scenes[b];
+    char who[56];
+    std::snprintf(who, sizeof who, "scene_power_batch: scene %d", b);
+    FNSSL_TRY(prepare_power(who, d.dp, d.ns, n, m, d.blocks, d.blocks_floats, d.power, &jobs[2 * b]));
+    std::snprintf(who, sizeof who, "scene_power_batch: scene %d (noise)", b);
+    const float* const one[1] = {d.noise};
+    FNSSL_REQUIRE(d.noise_len >= n, "%s: %d samples of noise for %d", who, d.noise_len, n);
+    FNSSL_TRY(prepare_power(who, one, 1, d.noise_len, m, d.blocks_noise, d.blocks_noise_floats, d.power_noise, &jobs[2 * b + 1]));
+  }
+  hipStream_t s = fnssl::as_stream(stream);
+  for (int k0 = 0; k0 < 2 * nscenes; k0 += 2 * kBatchScenes) {
+    const int nb = std::min(2 * kBatchScenes, 2 * nscenes - k0);
+    PowerBatchParams P{};
+    int nblk = 0;
+    for (int k = 0; k < nb; ++k) P.job[k] = jobs[k0 + k], nblk = std::max(nblk, P.job[k].nblk);
+    fnssl::TimedLaunch tl("scene_power_batch", s);
+    FNSSL_TRY(enqueue(s, Kernel{scene_block_sums_batch_kernel, 256, 0, "scene_block_sums_batch_kernel"}, dim3((unsigned)nblk, (unsigned)nb), P, m));
+    FNSSL_TRY(enqueue(s, Kernel{scene_power_batch_kernel, 256, 0, "scene_power_batch_kernel"}, dim3((unsigned)m, (unsigned)nb), P));
+  }
+  return FNSSL_OK;
+}
+
+int fnssl_scene_finish_batch(const fnssl_scene_desc* scenes, int nscenes, int n, int m, void* stream) {
+  FNSSL_REQUIRE(scenes && nscenes >= 1, "scene_finish_batch: null pointer / no scene");
+  std::vector<FinishParams> jobs((size_t)nscenes);
+  bool any_vad = false;
+  for (int b = 0; b < nscenes; ++b) {
+    const fnssl_scene_desc& d = scenes[b];
+    char who[56];
+    std::snprintf(who, sizeof who, "scene_finish_batch: scene %d", b);
+    FNSSL_REQUIRE(d.noise_len >= n, "%s: %d samples of noise for %d", who, d.noise_len, n);
+    FNSSL_TRY(prepare_finish(who, d.sig, d.ns, d.noise, d.with_vad ? d.vad_in : nullptr, n, m, d.power, d.power_noise, d.snr_lin, d.mic,
+                             d.g, d.vmax, d.vad_sources, d.vad, &jobs[b]));
+    any_vad = any_vad || d.with_vad;
+  }
+  hipStream_t s = fnssl::as_stream(stream);
+  for (int b0 = 0; b0 < nscenes; b0 += kBatchScenes) {
+    const int nb = std::min(kBatchScenes, nscenes - b0);
+    FinishBatchParams P{};
+    for (int b = 0; b < nb; ++b) P.job[b] = jobs[b0 + b];
+    fnssl::TimedLaunch tl("scene_finish_batch", s);
+    if (any_vad)
+      FNSSL_TRY(enqueue(s, Kernel{scene_vmax_batch_kernel, 1024, 0, "scene_vmax_batch_kernel"}, dim3(FNSSL_SCENE_MAX_SOURCES, (unsigned)nb), P));
+    FNSSL_TRY(enqueue(s, Kernel{scene_finish_batch_kernel, 256, 0, "scene_finish_batch_kernel"}, dim3((unsigned)((n + 255) / 256), (unsigned)nb), P));
+  }
+  return FNSSL_OK;
 }
 
 }  // extern "C"

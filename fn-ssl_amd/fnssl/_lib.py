@@ -77,6 +77,8 @@ SYMBOLS = [
     "fnssl_rir_plan", "fnssl_rir_workspace_bytes", "fnssl_rir_ism", "fnssl_rir_tail", "fnssl_rir_trajectory",
     "fnssl_anf_coherence", "fnssl_anf_factor", "fnssl_anf_status", "fnssl_anf_mean", "fnssl_anf_mix", "fnssl_scene_power",
     "fnssl_scene_finish",
+    "fnssl_rir_batch_plan", "fnssl_rir_batch_workspace_bytes", "fnssl_rir_ism_batch", "fnssl_rir_tail_batch",
+    "fnssl_scene_power_batch", "fnssl_scene_finish_batch",
 ]
 
 
@@ -173,6 +175,32 @@ class RirTrajItem(C.Structure):
     """include/fnssl.h: fnssl_rir_traj_item, one (signal, RIR set) pair of a fnssl_rir_trajectory call (48 bytes)."""
     _fields_ = [("x", C.c_void_p), ("rirs", C.c_void_p), ("w_ini", C.c_void_p), ("y", C.c_void_p),
                 ("ns", C.c_int), ("len", C.c_int), ("npts", C.c_int), ("m", C.c_int)]
+
+
+RIR_BATCH_JOBS = 32                         # include/fnssl.h: FNSSL_RIR_BATCH_JOBS (jobs of one launch)
+SCENE_BATCH_SCENES = 24                     # include/fnssl.h: FNSSL_SCENE_BATCH_SCENES (scenes of one launch)
+
+
+class RirJob(C.Structure):
+    """include/fnssl.h: fnssl_rir_job, the arguments of one fnssl_rir_ism + fnssl_rir_tail call."""
+    _fields_ = [("room_sz", C.c_float * 3), ("beta", C.c_float * 6), ("pos_src", C.c_void_p), ("pos_rcv", C.c_void_p),
+                ("m_src", C.c_int), ("m_rcv", C.c_int), ("nb_img", C.c_int * 3), ("nism", C.c_int), ("nsamples", C.c_int),
+                ("fs", C.c_double), ("c", C.c_double), ("seed", C.c_ulonglong), ("rir", C.c_void_p)]
+
+
+class RirJobPlan(C.Structure):
+    """include/fnssl.h: fnssl_rir_job_plan, fnssl_rir_plan of the job alone and its slice of the batch's workspace."""
+    _fields_ = [("plan", RirPlanInfo), ("workspace_offset", C.c_size_t)]
+
+
+class SceneDesc(C.Structure):
+    """include/fnssl.h: fnssl_scene_desc, one scene of a fnssl_scene_power_batch / fnssl_scene_finish_batch call."""
+    _fields_ = [("dp", C.c_void_p * SCENE_MAX_SOURCES), ("sig", C.c_void_p * SCENE_MAX_SOURCES),
+                ("vad_in", C.c_void_p * SCENE_MAX_SOURCES), ("noise", C.c_void_p),
+                ("ns", C.c_int), ("noise_len", C.c_int), ("with_vad", C.c_int), ("snr_lin", C.c_double),
+                ("blocks", C.c_void_p), ("blocks_floats", C.c_size_t), ("blocks_noise", C.c_void_p),
+                ("blocks_noise_floats", C.c_size_t), ("power", C.c_void_p), ("power_noise", C.c_void_p), ("mic", C.c_void_p),
+                ("g", C.c_void_p), ("vmax", C.c_void_p), ("vad_sources", C.c_void_p), ("vad", C.c_void_p)]
 
 
 class BtfView(C.Structure):
@@ -299,6 +327,13 @@ def load():
     lib.fnssl_rir_ism.argtypes = [f3, f6, vp, i, vp, i, i3, i, i, C.c_double, C.c_double, vp, vp, sz, vp]
     lib.fnssl_rir_tail.argtypes = [f3, f6, vp, i, vp, i, i, i, C.c_double, C.c_double, C.c_ulonglong, vp, vp]
     lib.fnssl_rir_trajectory.argtypes = [C.POINTER(RirTrajItem), i, vp]
+    lib.fnssl_rir_batch_plan.argtypes = [C.POINTER(RirJob), i, i, C.POINTER(RirJobPlan)]
+    lib.fnssl_rir_batch_workspace_bytes.argtypes = [C.POINTER(RirJob), i, i]
+    lib.fnssl_rir_batch_workspace_bytes.restype = sz
+    lib.fnssl_rir_ism_batch.argtypes = [C.POINTER(RirJob), i, vp, sz, vp]
+    lib.fnssl_rir_tail_batch.argtypes = [C.POINTER(RirJob), i, vp]
+    lib.fnssl_scene_power_batch.argtypes = [C.POINTER(SceneDesc), i, i, i, vp]
+    lib.fnssl_scene_finish_batch.argtypes = [C.POINTER(SceneDesc), i, i, i, vp]
     p4 = C.POINTER(vp)                                         # const float* const[<= FNSSL_SCENE_MAX_SOURCES], or NULL
     lib.fnssl_anf_coherence.argtypes = [vp, i, i, C.c_double, i, C.c_double, vp, vp]
     lib.fnssl_anf_factor.argtypes = [vp, i, i, i, vp, vp, vp]

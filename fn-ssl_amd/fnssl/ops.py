@@ -1164,6 +1164,102 @@ def rir_trajectory_batch(signals, rirs, w_inis):
     return outs
 
 
+def _rir_jobs(jobs, outs, who, need_device=True):
+    """The fnssl_rir_job array of ``jobs``: dicts with ``rir_ism``'s arguments under their names (pos_src, pos_rcv, room_sz,
+    beta, nb_img, nism, nsamples, fs and optionally c, seed).  Without ``need_device`` (planning) m_src / m_rcv may stand in
+    for the positions."""
+    jobs = list(jobs)
+    if not jobs:
+        raise RuntimeError("fnssl.%s: no job" % who)
+    arr = (_lib.RirJob * len(jobs))()
+    keep = []
+    for k, job in enumerate(jobs):
+        j = arr[k]
+        try:
+            room, bet, nb = _rir_host(job["room_sz"], job.get("beta", [0.0] * 6), job["nb_img"])
+        except ValueError as e:
+            raise ValueError("fnssl.%s: job %d: %s" % (who, k, e)) from None
+        j.room_sz, j.beta, j.nb_img = room, bet, nb
+        if need_device:
+            try:
+                src, rcv = _rir_positions(job["pos_src"], job["pos_rcv"])
+            except RuntimeError as e:
+                raise RuntimeError("fnssl.%s: job %d: %s" % (who, k, e)) from None
+            keep.append((src, rcv))
+            j.pos_src, j.pos_rcv, j.m_src, j.m_rcv = src.data_ptr(), rcv.data_ptr(), src.shape[0], rcv.shape[0]
+        else:
+            j.m_src = int(job["m_src"] if "m_src" in job else job["pos_src"].shape[0])
+            j.m_rcv = int(job["m_rcv"] if "m_rcv" in job else job["pos_rcv"].shape[0])
+        j.nism = int(job["nism"])
+        j.nsamples = int(job.get("nsamples", job["nism"]))
+        j.fs, j.c = float(job.get("fs", 16000.0)), float(job.get("c", 343.0))
+        j.seed = int(job.get("seed", 0)) & (2 ** 64 - 1)
+        if outs is not None:
+            out = outs[k]
+            _need_dev(out)
+            if tuple(out.shape) != (j.m_src, j.m_rcv, j.nsamples) or not out.is_contiguous() or out.device != keep[k][0].device:
+                raise RuntimeError("fnssl.%s: job %d: the RIRs must be a contiguous [%d, %d, %d] on %s, got %s on %s"
+                                   % (who, k, j.m_src, j.m_rcv, j.nsamples, keep[k][0].device, tuple(out.shape), out.device))
+            j.rir = out.data_ptr()
+    return arr, keep
+
+
+def rir_batch_plan(jobs, cus: int = 0):
+    """Host only (fnssl_rir_batch_plan): per job ``rir_plan`` of the job alone plus ``workspace_offset``, its slice of the
+    batch's workspace, and the workspace's size (fnssl_rir_batch_workspace_bytes) -> (list of dicts, bytes)."""
+    arr, _ = _rir_jobs(jobs, None, "rir_batch_plan", need_device=False)
+    lib = _lib.load()
+    plans = (_lib.RirJobPlan * len(arr))()
+    check(lib.fnssl_rir_batch_plan(arr, len(arr), int(cus), plans), "rir_batch_plan")
+    out = []
+    for pl in plans:
+        d = {n: int(getattr(pl.plan, n)) for n, _ in _lib.RirPlanInfo._fields_}
+        d["workspace_offset"] = int(pl.workspace_offset)
+        out.append(d)
+    return out, int(lib.fnssl_rir_batch_workspace_bytes(arr, len(arr), int(cus)))
+
+
+@on_device
+def rir_ism_batch(jobs, outs=None):
+    """Image-source part of several jobs in one launch set (fnssl_rir_ism_batch): ``jobs`` are dicts of ``rir_ism``'s
+    arguments -> list of RIRs [M_src, M_rcv, nsamples], each bit for bit what ``rir_ism`` gives the job alone.  ``outs``:
+    the RIRs to write (samples [nism, nsamples) are left alone), else zeros.  Every job is checked before the first launch;
+    a refused job is named by its index."""
+    jobs = list(jobs)
+    if outs is None:
+        arr, keep = _rir_jobs(jobs, None, "rir_ism_batch")
+        outs = [torch.zeros((j.m_src, j.m_rcv, max(j.nsamples, 0)), dtype=torch.float32, device=keep[k][0].device)
+                for k, j in enumerate(arr)]
+        for k, out in enumerate(outs):
+            arr[k].rir = out.data_ptr()
+    else:
+        outs = list(outs)
+        if len(outs) != len(jobs):
+            raise RuntimeError("fnssl.rir_ism_batch: %d outputs for %d jobs" % (len(outs), len(jobs)))
+        arr, keep = _rir_jobs(jobs, outs, "rir_ism_batch")
+    lib = _lib.load()
+    wsb = lib.fnssl_rir_batch_workspace_bytes(arr, len(arr), 0)
+    ws = torch.empty(max(wsb, 4) // 4, dtype=torch.float32, device=keep[0][0].device)
+    check(lib.fnssl_rir_ism_batch(arr, len(arr), _ptr(ws), ws.numel() * 4, _stream()), "rir_ism_batch")
+    return outs
+
+
+@on_device
+def rir_tail_batch(jobs, rirs):
+    """Diffuse tails of several jobs in one launch set (fnssl_rir_tail_batch), in place: ``rirs[k]`` [M_src, M_rcv, nsamples]
+    of job k (``rir_tail``'s arguments under their names, ``nsamples`` taken from the RIRs).  Jobs with nsamples == nism have
+    no tail and take no slot.  Returns ``rirs``."""
+    jobs, rirs = list(jobs), list(rirs)
+    if len(rirs) != len(jobs):
+        raise RuntimeError("fnssl.rir_tail_batch: %d RIR sets for %d jobs" % (len(rirs), len(jobs)))
+    for k, r in enumerate(rirs):
+        if not isinstance(r, torch.Tensor) or r.ndim != 3:
+            raise RuntimeError("fnssl.rir_tail_batch: job %d: expected a contiguous [M_src, M_rcv, nSamples]" % k)
+    arr, keep = _rir_jobs([dict(j, nsamples=int(r.shape[2])) for j, r in zip(jobs, rirs)], rirs, "rir_tail_batch")
+    check(_lib.load().fnssl_rir_tail_batch(arr, len(arr), _stream()), "rir_tail_batch")
+    return rirs
+
+
 # --------------------------------------------------------------------------- #
 # scene finish (csrc/scene.hip; the reference-named surface is fnssl/scene.py)
 # --------------------------------------------------------------------------- #
@@ -1315,4 +1411,71 @@ def scene_finish(sigs, noise, p, pn, snr_db: float, n: int, vads=None):
     check(_lib.load().fnssl_scene_finish(arr, ns, _ptr(noise), varr, int(n), m, _ptr(p), _ptr(pn), 10.0 ** (float(snr_db) / 10.0),
                                          _ptr(out["mic"]), _ptr(out["g"]), _ptr(out.get("vmax")), _ptr(out.get("vad_sources")),
                                          _ptr(out.get("vad")), _stream()), "scene_finish")
+    return out
+
+
+@on_device
+def scene_mix_batch(scenes, n: int):
+    """Power and finish of a batch of scenes in one launch set (fnssl_scene_power_batch, fnssl_scene_finish_batch).  ``scenes``:
+    dicts with ``dp`` and ``sig`` (lists of S_b <= 4 signals [>= n, M]), ``noise`` [>= n, M] (its WHOLE length enters its
+    power), ``snr_db`` and optionally ``vads`` (S_b signals).  n and M are shared.  Returns a dict: mic [B, n, M], g [B],
+    power and power_noise [B, M], vad [B, n] and, per scene, vmax [S_b] and vad_sources [n, S_b] (uint8; None without VAD) —
+    every entry bit for bit what ``scene_power`` / ``scene_finish`` give the scene alone.  Nothing is read back."""
+    scenes = list(scenes)
+    nb, n = len(scenes), int(n)
+    if nb < 1:
+        raise RuntimeError("fnssl.scene_mix_batch: no scene")
+    noise0 = scenes[0]["noise"]
+    _need_dev(noise0)
+    if noise0.ndim != 2:
+        raise RuntimeError("fnssl.scene_mix_batch: noise is [>= n, M], got %s" % (tuple(noise0.shape),))
+    m, dev = noise0.shape[1], noise0.device
+    nblk = max(n // 256, 1)
+    nlen = []
+    for b, sc in enumerate(scenes):
+        _need_dev(sc["noise"])
+        if sc["noise"].ndim != 2 or sc["noise"].shape[1] != m or sc["noise"].shape[0] < n:
+            raise RuntimeError("fnssl.scene_mix_batch: scene %d: noise %s for [>= %d, %d]" % (b, tuple(sc["noise"].shape), n, m))
+        nlen.append(int(sc["noise"].shape[0]))
+        if len(sc["dp"]) != len(sc["sig"]) or (sc.get("vads") is not None and len(sc["vads"]) != len(sc["sig"])):
+            raise RuntimeError("fnssl.scene_mix_batch: scene %d: %d direct-path, %d full and %s VAD signals"
+                               % (b, len(sc["dp"]), len(sc["sig"]), "no" if sc.get("vads") is None else len(sc["vads"])))
+    nsrc = [len(sc["sig"]) for sc in scenes]
+    nblk_noise = [max(v // 256, 1) for v in nlen]
+    blocks = torch.empty((m * (nb * nblk + sum(nblk_noise)),), dtype=torch.float32, device=dev)
+    out = {"mic": torch.empty((nb, n, m), dtype=torch.float32, device=dev), "g": torch.empty((nb,), dtype=torch.float32, device=dev),
+           "power": torch.empty((nb, m), dtype=torch.float32, device=dev),
+           "power_noise": torch.empty((nb, m), dtype=torch.float32, device=dev), "vmax": [None] * nb, "vad_sources": [None] * nb}
+    with_vad = [sc.get("vads") is not None for sc in scenes]
+    nv = sum(s for s, w in zip(nsrc, with_vad) if w)
+    vmax = torch.empty((max(nv, 1),), dtype=torch.float32, device=dev)
+    vsrc = torch.empty((max(nv, 1) * n,), dtype=torch.uint8, device=dev)
+    out["vad"] = vany = torch.empty((nb, n), dtype=torch.uint8, device=dev)        # rows of scenes without VAD are not written
+    descs = (_lib.SceneDesc * nb)()
+    keep, boff, voff = [], 0, 0
+    for b, sc in enumerate(scenes):
+        d = descs[b]
+        for name, field in (("dp", d.dp), ("sig", d.sig)) + ((("vads", d.vad_in),) if with_vad[b] else ()):
+            arr, kept = _scene_rows(sc[name], n, m, "scene_mix_batch: scene %d" % b)
+            keep += kept
+            for s in range(min(nsrc[b], _lib.SCENE_MAX_SOURCES)):
+                field[s] = arr[s]
+        noise = sc["noise"].contiguous()
+        keep.append(noise)
+        d.noise, d.ns, d.noise_len, d.with_vad = noise.data_ptr(), nsrc[b], nlen[b], int(with_vad[b])
+        d.snr_lin = 10.0 ** (float(sc["snr_db"]) / 10.0)
+        d.blocks, d.blocks_floats = blocks[boff:].data_ptr(), m * nblk
+        boff += m * nblk
+        d.blocks_noise, d.blocks_noise_floats = blocks[boff:].data_ptr(), m * nblk_noise[b]
+        boff += m * nblk_noise[b]
+        d.power, d.power_noise = out["power"][b].data_ptr(), out["power_noise"][b].data_ptr()
+        d.mic, d.g = out["mic"][b].data_ptr(), out["g"][b:].data_ptr()
+        if with_vad[b]:
+            out["vmax"][b] = vmax[voff:voff + nsrc[b]]
+            out["vad_sources"][b] = vsrc[voff * n:(voff + nsrc[b]) * n].view(n, nsrc[b])
+            d.vmax, d.vad_sources, d.vad = out["vmax"][b].data_ptr(), out["vad_sources"][b].data_ptr(), vany[b].data_ptr()
+            voff += nsrc[b]
+    lib = _lib.load()
+    check(lib.fnssl_scene_power_batch(descs, nb, n, m, _stream()), "scene_power_batch")
+    check(lib.fnssl_scene_finish_batch(descs, nb, n, m, _stream()), "scene_finish_batch")
     return out

@@ -10,6 +10,7 @@ host round trip; CPU tensors are rejected like everywhere else in this package.
 """
 from __future__ import annotations
 
+import inspect
 import math
 
 import numpy as np
@@ -17,7 +18,7 @@ import torch
 
 from . import ops
 
-__all__ = ["att2t_SabineEstimator", "t2n", "beta_SabineEstimation", "simulateRIR", "simulateTrajectory",
+__all__ = ["att2t_SabineEstimator", "t2n", "beta_SabineEstimation", "simulateRIR", "simulateRIRBatch", "simulateTrajectory",
            "simulateTrajectoryBatch", "sample_counts"]
 
 
@@ -64,9 +65,8 @@ def _reject_cpu_tensors(*xs):
                                "got a tensor on %s" % x.device)
 
 
-def _positions(pos, room, what):
-    """Host check (positions are small): [M, 3], strictly inside the room.  Returns an uploader, so that every argument is
-    checked before anything touches the device."""
+def _positions_host(pos, room, what):
+    """The positions on the host in float64 [M, 3], checked: at least one, finite, strictly inside the room."""
     if isinstance(pos, torch.Tensor):
         host = pos.detach().to(torch.float32).reshape(-1, 3).cpu().numpy().astype(np.float64)
     else:
@@ -75,6 +75,13 @@ def _positions(pos, room, what):
         raise ValueError("simulateRIR: no %s position" % what)
     if not (np.isfinite(host).all() and (host > 0).all() and (host < room[None, :]).all()):
         raise ValueError("simulateRIR: every %s position must lie strictly inside the room %s" % (what, room.tolist()))
+    return host
+
+
+def _positions(pos, room, what):
+    """Host check (positions are small): [M, 3], strictly inside the room.  Returns an uploader, so that every argument is
+    checked before anything touches the device."""
+    host = _positions_host(pos, room, what)
     if isinstance(pos, torch.Tensor):
         return lambda dev: pos.detach().to(torch.float32).reshape(-1, 3)
     return lambda dev: torch.from_numpy(host.astype(np.float32)).to(dev)
@@ -85,12 +92,28 @@ def simulateRIR(room_sz, beta, pos_src, pos_rcv, nb_img, Tmax, fs, Tdiff=None, s
     """RIRs [M_src, M_rcv, nSamples] float32 between every source and receiver position: the image-source method up to
     ``Tdiff`` (``nb_img`` images per axis), this project's diffuse tail from there to ``Tmax``, its noise
     drawn from ``seed``.  Only the ``"omni"`` patterns exist; ``orV_*`` are accepted and ignored under them."""
+    _check_patterns(spkr_pattern, mic_pattern, pos_src, pos_rcv)
+    as_numpy = not (isinstance(pos_src, torch.Tensor) or isinstance(pos_rcv, torch.Tensor))
+    dev = next((p.device for p in (pos_src, pos_rcv) if isinstance(p, torch.Tensor)), torch.device("cuda:0"))
+    room, bet, nb, nism, ns = _check_room(room_sz, beta, nb_img, Tmax, fs, Tdiff, c)
+    src = _positions(pos_src, room, "source")
+    rcv = _positions(pos_rcv, room, "receiver")
+    src, rcv = src(dev), rcv(dev)
+    rir = ops.rir_ism(src, rcv, room, bet, nb, nism, ns, fs, c)
+    if ns > nism:
+        ops.rir_tail(rir, src, rcv, room, bet, nism, fs, c, seed)
+    return rir.cpu().numpy() if as_numpy else rir
+
+
+def _check_patterns(spkr_pattern, mic_pattern, pos_src, pos_rcv):
     for name, pat in (("spkr_pattern", spkr_pattern), ("mic_pattern", mic_pattern)):
         if pat != "omni":
             raise NotImplementedError("simulateRIR: %s %r is not built (only 'omni')" % (name, pat))
     _reject_cpu_tensors(pos_src, pos_rcv)
-    as_numpy = not (isinstance(pos_src, torch.Tensor) or isinstance(pos_rcv, torch.Tensor))
-    dev = next((p.device for p in (pos_src, pos_rcv) if isinstance(p, torch.Tensor)), torch.device("cuda:0"))
+
+
+def _check_room(room_sz, beta, nb_img, Tmax, fs, Tdiff, c):
+    """simulateRIR's host checks of everything but the positions -> (room, beta, nb_img, nISM, nSamples)."""
     room = np.asarray(room_sz, dtype=np.float64).reshape(-1)
     bet = np.asarray(beta, dtype=np.float64).reshape(-1)
     if room.shape != (3,) or bet.shape != (6,) or not (room > 0).all() or (bet < 0).any() or (bet > 1).any():
@@ -101,13 +124,74 @@ def simulateRIR(room_sz, beta, pos_src, pos_rcv, nb_img, Tmax, fs, Tdiff=None, s
     if not (Tmax > 0 and fs > 0 and c > 0 and (Tdiff is None or Tdiff > 0)):
         raise ValueError("simulateRIR: Tmax, Tdiff, fs and c must be positive")
     nism, ns = sample_counts(Tdiff, Tmax, fs)
-    src = _positions(pos_src, room, "source")
-    rcv = _positions(pos_rcv, room, "receiver")
-    src, rcv = src(dev), rcv(dev)
-    rir = ops.rir_ism(src, rcv, room, bet, nb, nism, ns, fs, c)
-    if ns > nism:
-        ops.rir_tail(rir, src, rcv, room, bet, nism, fs, c, seed)
-    return rir.cpu().numpy() if as_numpy else rir
+    return room, bet, nb, nism, ns
+
+
+def _upload_packed(arrays, dtype, dev):
+    """Several small host arrays in ONE pinned buffer and one asynchronous copy -> their device views, in order."""
+    flat = [np.ascontiguousarray(a, dtype=dtype).reshape(-1) for a in arrays]
+    host = torch.from_numpy(np.concatenate(flat) if flat else np.zeros(0, dtype=dtype))
+    if dev.type == "cuda":
+        host = host.pin_memory()
+    whole = host.to(dev, non_blocking=True)
+    views, off = [], 0
+    for a, f in zip(arrays, flat):
+        views.append(whole[off:off + f.size].view(np.shape(a)))
+        off += f.size
+    return views
+
+
+_RIR_SIGNATURE = inspect.signature(simulateRIR)
+
+
+def simulateRIRBatch(jobs, out=None, *, _device=None):
+    """``simulateRIR`` for several independent jobs in one launch set (fnssl_rir_ism_batch, fnssl_rir_tail_batch): ``jobs`` is a
+    list of dicts or tuples of ``simulateRIR``'s arguments -> list of RIRs [M_src, M_rcv, nSamples], each bit for bit what
+    ``simulateRIR`` gives the job alone, whatever else is in the batch.  Every host check of every job comes first (a refused
+    job is named by its index and nothing has touched the device); then every position of every job goes up in one pinned
+    buffer and one copy.  numpy in every job gives numpy out.  ``out``: the device tensors to write, one per job.
+    ``_device`` (fnssl.scene): compute there and return device tensors whatever the positions are."""
+    jobs = list(jobs)
+    if not jobs:
+        raise ValueError("simulateRIRBatch: no job")
+    if out is not None and len(out) != len(jobs):
+        raise ValueError("simulateRIRBatch: %d outputs for %d jobs" % (len(out), len(jobs)))
+    recs, hosts, any_tensor, dev = [], [], False, None
+    for k, job in enumerate(jobs):
+        try:
+            a = (_RIR_SIGNATURE.bind(**job) if isinstance(job, dict) else _RIR_SIGNATURE.bind(*job))
+            a.apply_defaults()
+            a = a.arguments
+            _check_patterns(a["spkr_pattern"], a["mic_pattern"], a["pos_src"], a["pos_rcv"])
+            room, bet, nb, nism, ns = _check_room(a["room_sz"], a["beta"], a["nb_img"], a["Tmax"], a["fs"], a["Tdiff"], a["c"])
+            if nism > ops._lib.RIR_MAX_ISM_SAMPLES:
+                raise ValueError("simulateRIR: nISM = %d samples (at most %d: the image-source part of one RIR is one LDS tile; "
+                                 "use a shorter Tdiff)" % (nism, ops._lib.RIR_MAX_ISM_SAMPLES))
+            src = _positions_host(a["pos_src"], room, "source")
+            rcv = _positions_host(a["pos_rcv"], room, "receiver")
+        except (ValueError, NotImplementedError, RuntimeError, TypeError) as e:
+            err = type(e)("simulateRIRBatch: job %d: %s" % (k, e))
+            err.job = k
+            raise err from None
+        for p in (a["pos_src"], a["pos_rcv"]):
+            if isinstance(p, torch.Tensor):
+                any_tensor, dev = True, dev or p.device
+        hosts += [src, rcv]
+        recs.append(dict(room_sz=room, beta=bet, nb_img=nb, nism=nism, nsamples=ns, fs=a["fs"], c=a["c"], seed=a["seed"]))
+    dev = _device or dev or torch.device("cuda:0")
+    views = _upload_packed(hosts, np.float32, dev)
+    for k, rec in enumerate(recs):
+        rec["pos_src"], rec["pos_rcv"] = views[2 * k], views[2 * k + 1]
+    if out is None:
+        sizes = [r["pos_src"].shape[0] * r["pos_rcv"].shape[0] * r["nsamples"] for r in recs]
+        flat = torch.empty((sum(sizes),), dtype=torch.float32, device=dev)      # every sample is written: ISM part, then tail
+        out, off = [], 0
+        for r, size in zip(recs, sizes):
+            out.append(flat[off:off + size].view(r["pos_src"].shape[0], r["pos_rcv"].shape[0], r["nsamples"]))
+            off += size
+    rirs = ops.rir_ism_batch(recs, list(out))
+    ops.rir_tail_batch(recs, rirs)
+    return rirs if any_tensor or _device is not None else [r.cpu().numpy() for r in rirs]
 
 
 def _w_ini(npts, nsamples, timestamps, fs):
@@ -124,8 +208,9 @@ def _w_ini(npts, nsamples, timestamps, fs):
 
 
 def simulateTrajectoryBatch(source_signals, RIRs, timestamps=None, fs=None):
-    """``simulateTrajectory`` for several independent (signal, RIR set) pairs in one launch (a scene: 2 sources x {full,
-    direct path, VAD}); ``timestamps`` is None, one array for all, or a list with one entry per pair."""
+    """``simulateTrajectory`` for several independent (signal, RIR set) pairs, FNSSL_RIR_TRAJ_MAX_BATCH (16) per launch (a
+    scene: 2 sources x {full, direct path, VAD}; a batch of scenes: as many groups of 16 as it takes, in order);
+    ``timestamps`` is None, one array for all, or a list with one entry per pair."""
     n = len(source_signals)
     if n != len(RIRs) or n < 1:
         raise ValueError("simulateTrajectoryBatch: %d signals and %d RIR sets" % (n, len(RIRs)))
@@ -144,8 +229,9 @@ def simulateTrajectoryBatch(source_signals, RIRs, timestamps=None, fs=None):
         w = _w_ini(r.shape[0], x.numel(), timestamps[k] if per_item else timestamps, fs)
         xs.append(x)
         rs.append(r.to(torch.float32))
-        ws.append(torch.from_numpy(w).to(dev))
-    ys = ops.rir_trajectory_batch(xs, rs, ws)
+        ws.append(w)
+    ws = _upload_packed(ws, np.int32, dev)                                 # every w_ini in one copy
+    ys = ops.rir_trajectory_batch(xs, rs, ws)                              # groups of FNSSL_RIR_TRAJ_MAX_BATCH, in order
     return [y.cpu().numpy() for y in ys] if as_numpy else ys
 
 

@@ -7,6 +7,10 @@
     Dataset.NoiseDataset.gen_diffuse_noise = staticmethod(fnssl.scene.gen_diffuse_noise)
     Dataset.NoiseDataset.mix_signals = staticmethod(fnssl.scene.mix_signals)
 
+and for whole training batches in one launch set (INTEGRATION.md §4f, DESIGN.md §19)::
+
+    Dataset.RandomTrajectoryDataset.get_batch = fnssl.scene.get_batch
+
 numpy in gives numpy out, float32 (computed on ``cuda:0``, one host copy each way); ROCm tensors in give tensors out on their
 device with no host round trip; CPU tensors are rejected like everywhere else in this package.  Built: the ``'spherical'``
 field, the ``'cholesky'`` method, ``'omni'`` patterns, ``nfft = 256``, at most 16 microphones and 4 sources.
@@ -19,7 +23,7 @@ import torch
 from . import _lib, ops, rir
 from .rir import _reject_cpu_tensors
 
-__all__ = ["acoustic_power", "gen_diffuse_noise", "mix_signals", "simulate"]
+__all__ = ["acoustic_power", "gen_diffuse_noise", "mix_signals", "simulate", "simulate_batch", "get_batch"]
 
 
 def _is_t(a):
@@ -116,6 +120,17 @@ def gen_diffuse_noise(noise, T, fs, mic_pos, nfft=256, c=343.0, type_nf="spheric
     return y.cpu().numpy() if as_numpy else y
 
 
+def _rir_times(scene):
+    """(Tdiff, Tmax, nb_img) of a scene's full RIRs, as the reference's simulate() chooses them."""
+    if scene.T60 == 0:
+        return 0.1, 0.1, [1, 1, 1]
+    Tdiff = rir.att2t_SabineEstimator(12, scene.T60)                  # image sources until the RIRs have decayed 12 dB
+    Tmax = rir.att2t_SabineEstimator(40, scene.T60)                   # the diffuse model until 40 dB
+    if scene.T60 < 0.15:
+        Tdiff = Tmax
+    return Tdiff, Tmax, rir.t2n(Tdiff, scene.room_sz)
+
+
 def simulate(scene, *, seed=None, keep=False):
     """``AcousticScene.simulate`` on any object with its attributes (room_sz, T60, beta, noise_signal, SNR, source_signal, fs,
     array_setup, mic_pos, timestamps, traj_pts, t and optionally source_vad): the microphone signals [len(t), M].  Sets
@@ -143,14 +158,7 @@ def simulate(scene, *, seed=None, keep=False):
         raise ValueError("simulate: %d sources (1 .. %d)" % (nsrc, _lib.SCENE_MAX_SOURCES))
     if n < 512:
         raise ValueError("simulate: %d samples (acoustic_power needs one window of 512)" % n)
-    if scene.T60 == 0:
-        Tdiff, Tmax, nb_img = 0.1, 0.1, [1, 1, 1]
-    else:
-        Tdiff = rir.att2t_SabineEstimator(12, scene.T60)              # image sources until the RIRs have decayed 12 dB
-        Tmax = rir.att2t_SabineEstimator(40, scene.T60)               # the diffuse model until 40 dB
-        if scene.T60 < 0.15:
-            Tdiff = Tmax
-        nb_img = rir.t2n(Tdiff, scene.room_sz)
+    Tdiff, Tmax, nb_img = _rir_times(scene)
     if seed is None:
         seed = int(np.random.randint(0, 2 ** 31 - 1))
     src = _up(scene.source_signal, dev)
@@ -204,3 +212,154 @@ def simulate(scene, *, seed=None, keep=False):
     if has_vad:
         parts.update(vad_signals=vads, vad_max=fin["vmax"])
     return mic, parts
+
+
+def _host_f32(a):
+    """A small array (positions) on the host in float32, the values ``simulate`` uploads."""
+    if _is_t(a):
+        return a.detach().to(torch.float32).cpu().numpy()
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _scene_shape(scene):
+    """The host checks ``simulate`` makes on one scene before it touches the device -> its facts."""
+    pattern = getattr(scene.array_setup, "mic_pattern", "omni")
+    if pattern != "omni":
+        raise NotImplementedError("mic_pattern %r is not built (only 'omni')" % (pattern,))
+    has_vad = hasattr(scene, "source_vad")
+    ins = [scene.source_signal, scene.traj_pts, scene.mic_pos, scene.noise_signal] + ([scene.source_vad] if has_vad else [])
+    _reject_cpu_tensors(*ins)
+    n, nsrc, m = len(scene.t), int(scene.traj_pts.shape[-1]), int(scene.mic_pos.shape[0])
+    if not 1 <= nsrc <= _lib.SCENE_MAX_SOURCES:
+        raise ValueError("%d sources (1 .. %d)" % (nsrc, _lib.SCENE_MAX_SOURCES))
+    if n < 512:
+        raise ValueError("%d samples (acoustic_power needs one window of 512)" % n)
+    noise = scene.noise_signal
+    if noise is not None and (noise.ndim != 2 or noise.shape[1] != m or noise.shape[0] < n):
+        raise ValueError("noise_signal %s for [>= %d, %d]" % (tuple(noise.shape), n, m))
+    return {"pattern": pattern, "has_vad": has_vad, "n": n, "nsrc": nsrc, "m": m, "fs": float(scene.fs),
+            "tensors": any(_is_t(a) for a in ins), "device": next((a.device for a in ins if _is_t(a)), None)}
+
+
+def simulate_batch(scenes, *, seeds=None, keep=False):
+    """``simulate`` for a batch of independent scenes in ONE launch set whose size does not grow with the batch (until a
+    descriptor block is full) -> the microphone signals [B, n, M], every scene bit for bit what
+    ``simulate(scene, seed=seeds[b])`` gives it alone.  Sets ``dp_mic_signals_sources``, ``mic_vad_sources``, ``mic_vad`` and
+    a drawn ``noise_signal`` on every scene as ``simulate`` does (``mic_vad`` and ``mic_vad_sources`` from the batch's VAD
+    tensors, ``dp_mic_signals_sources`` stacked per scene from its direct-path signals, as ``simulate`` stacks them).
+
+    Scenes may differ in room, beta, T60, SNR, source count, trajectory points, timestamps and noise length; they share fs,
+    M, len(t) and the presence of ``source_vad`` (a mixed batch raises ``ValueError`` naming the first offending scene before
+    anything touches the device).  ``seeds=None`` draws as B ``simulate`` calls in order would: per scene first the seed,
+    then its noise if None.  numpy in every scene gives numpy out.  ``keep=True`` returns (mic, [parts of scene b])."""
+    scenes = list(scenes)
+    if not scenes:
+        raise ValueError("simulate_batch: no scene")
+    facts = []
+    for b, sc in enumerate(scenes):
+        try:
+            facts.append(_scene_shape(sc))
+        except (ValueError, NotImplementedError, RuntimeError) as e:
+            raise type(e)("simulate_batch: scene %d: %s" % (b, e)) from None
+        for key, what in (("m", "microphones"), ("fs", "Hz"), ("n", "samples (len(t))")):
+            if facts[b][key] != facts[0][key]:
+                raise ValueError("simulate_batch: scene %d: %g %s, scene 0 has %g (a batch shares M, fs and len(t))"
+                                 % (b, facts[b][key], what, facts[0][key]))
+        if facts[b]["has_vad"] != facts[0]["has_vad"]:
+            raise ValueError("simulate_batch: scene %d: source_vad is %s, in scene 0 it is %s (a batch shares its presence)"
+                             % (b, *("present" if f["has_vad"] else "absent" for f in (facts[b], facts[0]))))
+    if seeds is not None and len(seeds) != len(scenes):
+        raise ValueError("simulate_batch: %d seeds for %d scenes" % (len(seeds), len(scenes)))
+    n, m, has_vad, fs = facts[0]["n"], facts[0]["m"], facts[0]["has_vad"], scenes[0].fs
+    as_numpy = not any(f["tensors"] for f in facts)
+    dev = next((f["device"] for f in facts if f["device"] is not None), torch.device("cuda:0"))
+
+    # numpy's stream, as B simulate() calls in order consume it
+    seed_of, drawn = [], []
+    for b, sc in enumerate(scenes):
+        seed_of.append(int(np.random.randint(0, 2 ** 31 - 1)) if seeds is None else int(seeds[b]))
+        drawn.append(np.random.standard_normal((n, m)) if sc.noise_signal is None else None)
+
+    # every RIR of the batch: per source the full RIRs and the direct-path RIRs
+    jobs, scene_of_job = [], []
+    for b, sc in enumerate(scenes):
+        Tdiff, Tmax, nb_img = _rir_times(sc)
+        scene_of_job += [b] * (2 * facts[b]["nsrc"])
+        pts, mic_pos, orv = _host_f32(sc.traj_pts), _host_f32(sc.mic_pos), sc.array_setup.mic_orV
+        for s in range(facts[b]["nsrc"]):
+            common = dict(room_sz=sc.room_sz, beta=sc.beta, pos_src=pts[:, :, s], pos_rcv=mic_pos, fs=sc.fs, orV_rcv=orv,
+                          mic_pattern=facts[b]["pattern"])
+            jobs.append(dict(common, nb_img=nb_img, Tmax=Tmax, Tdiff=Tdiff, seed=seed_of[b] + s))
+            jobs.append(dict(common, nb_img=[1, 1, 1], Tmax=0.1))
+    try:
+        all_rirs = rir.simulateRIRBatch(jobs, _device=dev)
+    except (ValueError, NotImplementedError) as e:
+        raise type(e)("simulate_batch: scene %d: %s" % (scene_of_job[e.job], e)) from None
+
+    # every mixing of the batch: per scene 2 S (with VAD 3 S) pairs, in groups of 16
+    sigs, rirs, stamps, first, k = [], [], [], [], 0
+    for b, sc in enumerate(scenes):
+        nsrc = facts[b]["nsrc"]
+        src = _up(sc.source_signal, dev)
+        first.append(len(sigs))
+        for s in range(nsrc):
+            x = src[:, s].contiguous()
+            sigs += [x, x]
+            rirs += [all_rirs[k + 2 * s], all_rirs[k + 2 * s + 1]]
+        if has_vad:
+            vad_in = _up(sc.source_vad, dev)
+            for s in range(nsrc):
+                sigs.append(vad_in[:, s].contiguous())
+                rirs.append(all_rirs[k + 2 * s + 1])
+        stamps += [sc.timestamps] * (len(sigs) - first[b])
+        k += 2 * nsrc
+    ys = rir.simulateTrajectoryBatch(sigs, rirs, timestamps=stamps, fs=fs)
+    short = min(y.shape[0] for y in ys)
+    if short < n:
+        raise ValueError("simulate_batch: the source signals give %d samples, len(t) = %d" % (short, n))
+
+    descs, noises = [], []
+    for b, sc in enumerate(scenes):
+        nsrc, y = facts[b]["nsrc"], ys[first[b]:]
+        if drawn[b] is not None:
+            noise = _up(drawn[b], dev)
+            sc.noise_signal = drawn[b] if as_numpy else noise
+        else:
+            noise = _up(sc.noise_signal, dev)
+        noises.append(noise)
+        descs.append({"sig": y[0:2 * nsrc:2], "dp": y[1:2 * nsrc:2], "noise": noise, "snr_db": float(sc.SNR),
+                      "vads": y[2 * nsrc:3 * nsrc] if has_vad else None})
+    fin = ops.scene_mix_batch(descs, n)
+
+    host = (lambda a: a.cpu().numpy()) if as_numpy else (lambda a: a)
+    vad_all = host(fin["vad"].bool()) if has_vad else None
+    parts, k = [], 0
+    for b, sc in enumerate(scenes):
+        nsrc, d = facts[b]["nsrc"], descs[b]
+        sc.dp_mic_signals_sources = host(torch.stack([a[:n] for a in d["dp"]], dim=2))
+        if has_vad:
+            sc.mic_vad_sources = host(fin["vad_sources"][b].bool())
+            sc.mic_vad = vad_all[b]
+        part = {"mic_signals_sources": d["sig"], "dp_mic_signals_sources": d["dp"], "noise": noises[b], "power": fin["power"][b],
+                "power_noise": fin["power_noise"][b], "g": fin["g"][b:b + 1], "seed": seed_of[b],
+                "rirs": all_rirs[k:k + 2 * nsrc:2], "dp_rirs": all_rirs[k + 1:k + 2 * nsrc:2]}
+        if has_vad:
+            part.update(vad_signals=d["vads"], vad_max=fin["vmax"][b])
+        parts.append(part)
+        k += 2 * nsrc
+    mic = host(fin["mic"])
+    return (mic, parts) if keep else mic
+
+
+def get_batch(dataset, idx1, idx2):
+    """The reference's ``RandomTrajectoryDataset.get_batch`` with one ``simulate_batch`` call for the whole batch:
+    ``dataset.getRandomScene(idx)`` for idx1 <= idx < idx2, the simulation, ``dataset.transforms`` per scene if any ->
+    (the stacked signals, the list of scenes)."""
+    scenes = [dataset.getRandomScene(idx) for idx in range(idx1, idx2)]
+    mics = simulate_batch(scenes)
+    sigs = []
+    for b, mic in enumerate(mics):
+        for t in getattr(dataset, "transforms", None) or ():
+            mic, scenes[b] = t(mic, scenes[b])
+        sigs.append(mic)
+    return (torch.stack(sigs) if _is_t(sigs[0]) else np.stack(sigs)), scenes

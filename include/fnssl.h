@@ -1335,6 +1335,45 @@ typedef struct {
 } fnssl_rir_traj_item;
 int fnssl_rir_trajectory(const fnssl_rir_traj_item* items, int nitems, void* stream);
 
+/* ---- RIR jobs: several fnssl_rir_ism / fnssl_rir_tail calls in one launch set (additive: FNSSL_ABI_VERSION stays 19) ----------
+ * A job is one fnssl_rir_ism + fnssl_rir_tail call: its arguments, under their names (a two-source scene is four jobs: per
+ * source the full RIRs and the direct-path RIRs).  `jobs` is a HOST array; pos_src, pos_rcv and rir are DEVICE arrays as above.
+ * Every job's rir gets exactly the bits the single calls give it: the kernels share the per-image and per-sample code, and a
+ * job's image chunks are those fnssl_rir_plan gives the job alone, so they depend on the job and the device's CU count only,
+ * never on the rest of the batch or the job's place in it.
+ *
+ * Launches: the jobs' records travel by value in the kernel arguments, FNSSL_RIR_BATCH_JOBS per launch (a workgroup takes its
+ * record by blockIdx.z and leaves at once when it lies past its job's extent): per block of jobs one image-source launch,
+ * one chunk-sum launch if a job of the block has several chunks, and one tail launch per block of jobs that HAVE a tail
+ * (nsamples > nism).  Dynamic LDS is per launch: a block takes its largest job's tile.  Jobs of one chunk write straight into
+ * their rir; the others go through their own slice of `workspace` (fnssl_rir_batch_plan reports the slices, in job order;
+ * fnssl_rir_batch_workspace_bytes is their sum).
+ *
+ * Every check fnssl_rir_ism / fnssl_rir_tail make is made for every job before the first launch; a refused job is named by
+ * its index ("rir_ism_batch: job 2: ...") and nothing is enqueued.  fnssl_rir_batch_plan is host only (no pointer of a job is
+ * read); `cus` as in fnssl_rir_plan. */
+#define FNSSL_RIR_BATCH_JOBS 32
+typedef struct {
+  float room_sz[3];
+  float beta[6];
+  const float* pos_src;    /* [m_src][3] */
+  const float* pos_rcv;    /* [m_rcv][3] */
+  int m_src, m_rcv;
+  int nb_img[3];
+  int nism, nsamples;
+  double fs, c;
+  unsigned long long seed; /* of the tail */
+  float* rir;              /* [m_src][m_rcv][nsamples] */
+} fnssl_rir_job;
+typedef struct {
+  fnssl_rir_plan_info plan;     /* what fnssl_rir_plan gives the job alone */
+  size_t workspace_offset;      /* bytes from the workspace's start; the slice is plan.workspace_bytes long */
+} fnssl_rir_job_plan;
+int fnssl_rir_batch_plan(const fnssl_rir_job* jobs, int njobs, int cus, fnssl_rir_job_plan* out);
+size_t fnssl_rir_batch_workspace_bytes(const fnssl_rir_job* jobs, int njobs, int cus);
+int fnssl_rir_ism_batch(const fnssl_rir_job* jobs, int njobs, void* workspace, size_t workspace_bytes, void* stream);
+int fnssl_rir_tail_batch(const fnssl_rir_job* jobs, int njobs, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* Scene finish (csrc/scene.hip): diffuse noise field, SNR mix, source VAD   */
 /* ------------------------------------------------------------------------- */
@@ -1385,6 +1424,39 @@ int fnssl_scene_power(const float* const* a, int nsum, int n, int m, float* bloc
 int fnssl_scene_finish(const float* const* sig, int ns, const float* noise, const float* const* vad_in, int n, int m,
                        const float* p, const float* pn, double snr_lin, float* mic, float* g, float* vmax,
                        unsigned char* vad_sources, unsigned char* vad, void* stream);
+
+/* ---- a batch of scenes: power and finish in one launch set (additive: FNSSL_ABI_VERSION stays 19) --------------------------
+ * `scenes` is a HOST array of per-scene records; n (samples) and m (channels) are shared, the scene is a grid dimension.
+ * The records travel by value in the kernel arguments, FNSSL_SCENE_BATCH_SCENES per launch.
+ * fnssl_scene_power_batch: per scene power[m] = fnssl_scene_power(dp[0 .. ns), n) and power_noise[m] =
+ *   fnssl_scene_power(noise, noise_len) (over the WHOLE noise, as the reference does), two launches per block of scenes.
+ * fnssl_scene_finish_batch: per scene fnssl_scene_finish(sig, ns, noise, with_vad ? vad_in : NULL, n, m, power, power_noise,
+ *   snr_lin, ...): g is computed and stays on the device, nothing is read back.  Two launches per block (one without VAD).
+ * The kernels share their code with the single entry points and the order of every sum is fixed per scene: the bits are
+ * those of the single calls.  Every check of the single calls is made for every scene before the first launch; a refused
+ * scene is named by its index. */
+#define FNSSL_SCENE_BATCH_SCENES 24
+typedef struct {
+  const float* dp[FNSSL_SCENE_MAX_SOURCES];      /* direct-path signals [>= n][m]: the power */
+  const float* sig[FNSSL_SCENE_MAX_SOURCES];     /* full signals [>= n][m]: the mix */
+  const float* vad_in[FNSSL_SCENE_MAX_SOURCES];  /* VAD trajectories [>= n][m] (with_vad) */
+  const float* noise;                            /* [noise_len][m], noise_len >= n */
+  int ns, noise_len, with_vad;
+  double snr_lin;
+  float* blocks;                                 /* scratch, >= m * (n / 256) floats */
+  size_t blocks_floats;
+  float* blocks_noise;                           /* scratch, >= m * (noise_len / 256) floats */
+  size_t blocks_noise_floats;
+  float* power;                                  /* [m] */
+  float* power_noise;                            /* [m] */
+  float* mic;                                    /* [n][m] */
+  float* g;                                      /* [1] */
+  float* vmax;                                   /* [ns]       (with_vad) */
+  unsigned char* vad_sources;                    /* [n][ns]    (with_vad) */
+  unsigned char* vad;                            /* [n]        (with_vad) */
+} fnssl_scene_desc;
+int fnssl_scene_power_batch(const fnssl_scene_desc* scenes, int nscenes, int n, int m, void* stream);
+int fnssl_scene_finish_batch(const fnssl_scene_desc* scenes, int nscenes, int n, int m, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Measurement hooks (bench.py: per-kernel HIP-event timing on the launch stream) */
