@@ -79,6 +79,7 @@ SYMBOLS = [
     "fnssl_scene_finish",
     "fnssl_rir_batch_plan", "fnssl_rir_batch_workspace_bytes", "fnssl_rir_ism_batch", "fnssl_rir_tail_batch",
     "fnssl_scene_power_batch", "fnssl_scene_finish_batch",
+    "fnssl_scene_doa_batch", "fnssl_scene_segment_batch", "fnssl_scene_pack_batch",
 ]
 
 
@@ -201,6 +202,23 @@ class SceneDesc(C.Structure):
                 ("blocks", C.c_void_p), ("blocks_floats", C.c_size_t), ("blocks_noise", C.c_void_p),
                 ("blocks_noise_floats", C.c_size_t), ("power", C.c_void_p), ("power_noise", C.c_void_p), ("mic", C.c_void_p),
                 ("g", C.c_void_p), ("vmax", C.c_void_p), ("vad_sources", C.c_void_p), ("vad", C.c_void_p)]
+
+
+class SceneDoaDesc(C.Structure):
+    """include/fnssl.h: fnssl_scene_doa_desc, one scene of a fnssl_scene_doa_batch call."""
+    _fields_ = [("traj_pts", C.c_void_p), ("timestamps", C.c_void_p), ("array_pos", C.c_double * 3), ("fs", C.c_double),
+                ("npts", C.c_int), ("ns", C.c_int), ("n", C.c_int), ("trajectory", C.c_void_p), ("doa", C.c_void_p)]
+
+
+class SceneSegmentDesc(C.Structure):
+    """include/fnssl.h: fnssl_scene_segment_desc, one scene of a fnssl_scene_segment_batch call."""
+    _fields_ = [("doa", C.c_void_p), ("vad_sources", C.c_void_p), ("vad", C.c_void_p), ("ns", C.c_int), ("doa_len", C.c_int),
+                ("vad_len", C.c_int)]
+
+
+class ScenePackDesc(C.Structure):
+    """include/fnssl.h: fnssl_scene_pack_desc, one scene of a fnssl_scene_pack_batch call."""
+    _fields_ = [("dp", C.c_void_p * SCENE_MAX_SOURCES), ("stride_t", C.c_longlong), ("stride_c", C.c_longlong), ("ns", C.c_int)]
 
 
 class BtfView(C.Structure):
@@ -334,6 +352,9 @@ def load():
     lib.fnssl_rir_tail_batch.argtypes = [C.POINTER(RirJob), i, vp]
     lib.fnssl_scene_power_batch.argtypes = [C.POINTER(SceneDesc), i, i, i, vp]
     lib.fnssl_scene_finish_batch.argtypes = [C.POINTER(SceneDesc), i, i, i, vp]
+    lib.fnssl_scene_doa_batch.argtypes = [C.POINTER(SceneDoaDesc), i, vp]
+    lib.fnssl_scene_segment_batch.argtypes = [C.POINTER(SceneSegmentDesc), i, i, i, i, i, i, vp, vp, vp, vp, vp]
+    lib.fnssl_scene_pack_batch.argtypes = [C.POINTER(ScenePackDesc), i, i, i, i, vp, vp]
     p4 = C.POINTER(vp)                                         # const float* const[<= FNSSL_SCENE_MAX_SOURCES], or NULL
     lib.fnssl_anf_coherence.argtypes = [vp, i, i, C.c_double, i, C.c_double, vp, vp]
     lib.fnssl_anf_factor.argtypes = [vp, i, i, i, vp, vp, vp]

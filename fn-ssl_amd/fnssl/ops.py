@@ -1479,3 +1479,150 @@ def scene_mix_batch(scenes, n: int):
     check(lib.fnssl_scene_power_batch(descs, nb, n, m, _stream()), "scene_power_batch")
     check(lib.fnssl_scene_finish_batch(descs, nb, n, m, _stream()), "scene_finish_batch")
     return out
+
+
+# --------------------------------------------------------------------------- #
+# training labels of a batch of scenes (csrc/labels.hip)
+# --------------------------------------------------------------------------- #
+def _need_dev_as(t, dtype, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("fnssl: expected a ROCm device tensor (this path has no CPU implementation), got %s"
+                           % (t.device if isinstance(t, torch.Tensor) else type(t)))
+    if t.dtype != dtype:
+        raise RuntimeError("fnssl.%s: expected %s, got %s" % (what, dtype, t.dtype))
+
+
+@on_device
+def scene_doa_batch(items):
+    """Trajectory and DOA of every scene in one launch set (fnssl_scene_doa_batch).  ``items``: dicts with ``traj_pts``
+    [P, 3, S] and ``timestamps`` [P] (float64 device tensors), ``n``, ``fs`` and ``array_pos`` (three host numbers) -> a list of
+    (trajectory [n, 3, S], DOA [n, 2, S]) float64 tensors, views of two batch allocations."""
+    items = list(items)
+    if not items:
+        raise RuntimeError("fnssl.scene_doa_batch: no scene")
+    descs = (_lib.SceneDoaDesc * len(items))()
+    keep, rows = [], []
+    for b, it in enumerate(items):
+        pts, ts = it["traj_pts"], it["timestamps"]
+        _need_dev_as(pts, torch.float64, "scene_doa_batch")
+        _need_dev_as(ts, torch.float64, "scene_doa_batch")
+        if pts.ndim != 3 or pts.shape[1] != 3 or ts.ndim != 1 or ts.shape[0] != pts.shape[0] or pts.shape[0] < 1:
+            raise RuntimeError("fnssl.scene_doa_batch: scene %d: traj_pts is [P, 3, S] and timestamps [P], got %s and %s"
+                               % (b, tuple(pts.shape), tuple(ts.shape)))
+        pts, ts = pts.contiguous(), ts.contiguous()
+        keep += [pts, ts]
+        rows.append(int(it["n"]) * int(pts.shape[2]))
+        d = descs[b]
+        d.traj_pts, d.timestamps, d.fs = pts.data_ptr(), ts.data_ptr(), float(it["fs"])
+        d.npts, d.ns, d.n = int(pts.shape[0]), int(pts.shape[2]), int(it["n"])
+        for i in range(3):
+            d.array_pos[i] = float(it["array_pos"][i])
+    dev = items[0]["traj_pts"].device
+    traj = torch.empty((3 * max(sum(rows), 1),), dtype=torch.float64, device=dev)
+    doa = torch.empty((2 * max(sum(rows), 1),), dtype=torch.float64, device=dev)
+    out, off = [], 0
+    for b, it in enumerate(items):
+        n, s = descs[b].n, descs[b].ns
+        t, a = traj[3 * off:3 * (off + rows[b])], doa[2 * off:2 * (off + rows[b])]
+        descs[b].trajectory, descs[b].doa = t.data_ptr(), a.data_ptr()
+        out.append((t.view(n, 3, s), a.view(n, 2, s)))
+        off += rows[b]
+    check(_lib.load().fnssl_scene_doa_batch(descs, len(items), _stream()), "scene_doa_batch")
+    return out
+
+
+@on_device
+def scene_segment_batch(items, length: int, K: int, step: int, nw: int, smax: int, with_doa: bool = True, with_vad: bool = True):
+    """The windows of every scene in one launch set (fnssl_scene_segment_batch).  ``items``: dicts with ``doa`` [>= (nw - 1) step
+    + K, 2, S_b] float64 (needed with ``with_doa``), ``vad_sources`` [Lv, S_b] and ``vad`` [Lv] uint8 / bool (or None: zeros), Lv <= length, and
+    ``ns`` = S_b.  Returns a dict: doa [B, nw, 2, smax] float64 (``with_doa``), vad_sources [B, nw, K, smax] and vad [B, nw, K]
+    uint8 and vad_count [B, nw, smax] int32 (``with_vad``)."""
+    items = list(items)
+    nb = len(items)
+    if nb < 1:
+        raise RuntimeError("fnssl.scene_segment_batch: no scene")
+    descs = (_lib.SceneSegmentDesc * nb)()
+    keep, dev = [], None
+    for b, it in enumerate(items):
+        d = descs[b]
+        d.ns = int(it["ns"])
+        doa = it.get("doa") if with_doa else None
+        if with_doa and doa is None:
+            raise RuntimeError("fnssl.scene_segment_batch: scene %d: no DOA (its rows of the output would stay unwritten)" % b)
+        if doa is not None:
+            _need_dev_as(doa, torch.float64, "scene_segment_batch")
+            if doa.ndim != 3 or doa.shape[1] != 2 or doa.shape[2] != d.ns:
+                raise RuntimeError("fnssl.scene_segment_batch: scene %d: DOA is [n, 2, %d], got %s" % (b, d.ns, tuple(doa.shape)))
+            doa = doa.contiguous()
+            keep.append(doa)
+            d.doa, d.doa_len, dev = doa.data_ptr(), int(doa.shape[0]), doa.device
+        lens = []
+        for name, shape in (("vad_sources", (d.ns,)), ("vad", ())):
+            v = it.get(name) if with_vad else None
+            if v is None:
+                continue
+            if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype not in (torch.uint8, torch.bool):
+                raise RuntimeError("fnssl.scene_segment_batch: scene %d: %s must be a uint8 / bool ROCm tensor" % (b, name))
+            if tuple(v.shape[1:]) != shape:
+                raise RuntimeError("fnssl.scene_segment_batch: scene %d: %s is %s, got %s"
+                                   % (b, name, "[n, %d]" % d.ns if shape else "[n]", tuple(v.shape)))
+            v = v.contiguous().view(torch.uint8)
+            keep.append(v)
+            setattr(d, name, v.data_ptr())
+            lens.append(int(v.shape[0]))
+            dev = v.device
+        if len(set(lens)) > 1:
+            raise RuntimeError("fnssl.scene_segment_batch: scene %d: vad_sources has %d rows, vad %d" % (b, lens[0], lens[1]))
+        d.vad_len = lens[0] if lens else 0
+    if dev is None:
+        raise RuntimeError("fnssl.scene_segment_batch: no device tensor in the batch")
+    out = {}
+    if with_doa:
+        out["doa"] = torch.empty((nb, nw, 2, smax), dtype=torch.float64, device=dev)
+    if with_vad:
+        out["vad_sources"] = torch.empty((nb, nw, K, smax), dtype=torch.uint8, device=dev)
+        out["vad"] = torch.empty((nb, nw, K), dtype=torch.uint8, device=dev)
+        out["vad_count"] = torch.empty((nb, nw, smax), dtype=torch.int32, device=dev)
+    check(_lib.load().fnssl_scene_segment_batch(descs, nb, int(length), int(K), int(step), int(nw), int(smax), _ptr(out.get("doa")),
+                                                _ptr(out.get("vad_sources")), _ptr(out.get("vad")), _ptr(out.get("vad_count")),
+                                                _stream()), "scene_segment_batch")
+    return out
+
+
+@on_device
+def scene_pack_batch(scenes, n: int, m: int, smax: int):
+    """``scenes``: per scene its S_b <= smax direct-path signals, a list of [>= n, M] tensors or ONE tensor [>= n, M, S_b] of any
+    strides (what ``simulate_batch`` leaves on a scene; read in place) -> dp_signal [B, n, M, smax], absent sources zero
+    (fnssl_scene_pack_batch)."""
+    scenes = list(scenes)
+    nb = len(scenes)
+    if nb < 1:
+        raise RuntimeError("fnssl.scene_pack_batch: no scene")
+    descs = (_lib.ScenePackDesc * nb)()
+    keep = []
+    for b, sigs in enumerate(scenes):
+        d = descs[b]
+        stacked = isinstance(sigs, torch.Tensor)
+        ns = int(sigs.shape[2]) if stacked and sigs.ndim == 3 else -1 if stacked else len(sigs)
+        if not 1 <= ns <= min(smax, _lib.SCENE_MAX_SOURCES):
+            raise RuntimeError("fnssl.scene_pack_batch: scene %d: %d sources (1 .. max_source = %d)" % (b, ns, smax))
+        d.ns = ns
+        if stacked:
+            _need_dev(sigs)
+            if sigs.shape[0] < n or sigs.shape[1] != m:
+                raise RuntimeError("fnssl.scene_pack_batch: scene %d: signals %s, expected at least [%d, %d, S]" % (b, tuple(sigs.shape), n, m))
+            if min(sigs.stride()) < 1:
+                sigs = sigs.contiguous()
+            keep.append(sigs)
+            d.stride_t, d.stride_c = sigs.stride(0), sigs.stride(1)
+            for s in range(ns):
+                d.dp[s] = sigs.data_ptr() + 4 * s * sigs.stride(2)
+        else:
+            arr, kept = _scene_rows(sigs, n, m, "scene_pack_batch: scene %d" % b)
+            keep += kept
+            d.stride_t, d.stride_c = m, 1
+            for s in range(ns):
+                d.dp[s] = arr[s]
+    out = torch.empty((nb, n, m, smax), dtype=torch.float32, device=keep[0].device)
+    check(_lib.load().fnssl_scene_pack_batch(descs, nb, int(n), int(m), int(smax), _ptr(out), _stream()), "scene_pack_batch")
+    return out

@@ -14,6 +14,11 @@ and for whole training batches in one launch set (DESIGN.md
 numpy in gives numpy out, float32 (computed on ``cuda:0``, one host copy each way); ROCm tensors in give tensors out on their
 device with no host round trip; CPU tensors are rejected like everywhere else in this package.  Built: the ``'spherical'``
 field, the ``'cholesky'`` method, ``'omni'`` patterns, ``nfft = 256``, at most 16 microphones and 4 sources.
+
+The labels of a training batch (csrc/labels.hip): ``trajectory_doa`` (the interpolation and
+``cart2sph`` of ``getRandomScene``), ``Segmenting_SRPDNN`` (the reference's transform, usable in ``dataset.transforms``),
+``segment_batch`` (the transform and the padded ``gts`` dict for a whole batch in one launch set) and ``training_batch``
+(draw, simulate, segment -> ``(mic, gts)`` for ``training_step``).
 """
 from __future__ import annotations
 
@@ -23,7 +28,8 @@ import torch
 from . import _lib, ops, rir
 from .rir import _reject_cpu_tensors
 
-__all__ = ["acoustic_power", "gen_diffuse_noise", "mix_signals", "simulate", "simulate_batch", "get_batch"]
+__all__ = ["acoustic_power", "gen_diffuse_noise", "mix_signals", "simulate", "simulate_batch", "get_batch", "trajectory_doa",
+           "Segmenting_SRPDNN", "segment_batch", "training_batch"]
 
 
 def _is_t(a):
@@ -363,3 +369,242 @@ def get_batch(dataset, idx1, idx2):
             mic, scenes[b] = t(mic, scenes[b])
         sigs.append(mic)
     return (torch.stack(sigs) if _is_t(sigs[0]) else np.stack(sigs)), scenes
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# labels: trajectory -> DOA, the Segmenting_SRPDNN transform, the padded gts dict
+# ------------------------------------------------------------------------------------------------------------------------
+def num_windows(L, K, step):
+    """The reference's ``N_w = floor(L / step - K / step + 1)``, evaluated in float64 as it does (where ``step`` divides
+    ``L - K`` the two rounded quotients may give one window fewer than ``(L - K) // step + 1``; never one more)."""
+    return int(np.floor(L / step - K / step + 1))
+
+
+def window_times(L, K, step, fs):
+    """The reference's ``tw = arange(0, L - K, step) / fs``: ``N_w`` entries, ``N_w - 1`` where ``step`` divides ``L - K``."""
+    return np.arange(0, (L - K), step) / fs
+
+
+def _host_timestamps(ts, who):
+    """The timestamps as given, checked on the host: [P], finite, increasing (a device tensor's P numbers are copied down for
+    it: np.interp's bisection means nothing otherwise, and the kernel would give wrong labels silently)."""
+    host = ts.detach().cpu().numpy() if _is_t(ts) else ts
+    host = np.asarray(host, dtype=np.float64)
+    if host.ndim != 1 or host.size < 1 or not np.all(np.isfinite(host)) or np.any(np.diff(host) <= 0):
+        raise ValueError("%s: timestamps must be [P] finite and increasing" % who)
+    return ts if _is_t(ts) else host
+
+
+def trajectory_doa(traj_pts, timestamps, n, fs, array_pos):
+    """What ``getRandomScene`` does after drawing its trajectory points: ``trajectory[:, i, s] = np.interp(arange(n) / fs,
+    timestamps, traj_pts[:, i, s])`` and ``DOA[:, :, s] = cart2sph(trajectory[:, :, s] - array_pos)[:, 1:3]`` (elevation from
+    the z axis, azimuth) -> (trajectory [n, 3, S], DOA [n, 2, S]), float64, computed on the device in double."""
+    _reject_cpu_tensors(traj_pts, timestamps, array_pos)
+    as_numpy = not (_is_t(traj_pts) or _is_t(timestamps))
+    dev = _device(traj_pts, timestamps)
+    pos = np.asarray(array_pos.detach().cpu().numpy() if _is_t(array_pos) else array_pos, dtype=np.float64).reshape(-1)
+    if pos.shape != (3,) or tuple(traj_pts.shape[1:2]) != (3,) or len(traj_pts.shape) != 3:
+        raise ValueError("trajectory_doa: traj_pts is [P, 3, S] and array_pos [3], got %s and %s" % (tuple(traj_pts.shape), pos.shape))
+    if not 1 <= traj_pts.shape[2] <= _lib.SCENE_MAX_SOURCES:
+        raise ValueError("trajectory_doa: %d sources (1 .. %d)" % (traj_pts.shape[2], _lib.SCENE_MAX_SOURCES))
+    if int(n) < 1:
+        raise ValueError("trajectory_doa: %d samples" % int(n))
+    ts = _host_timestamps(timestamps, "trajectory_doa")
+    item = {"traj_pts": _up(traj_pts, dev, torch.float64), "timestamps": _up(ts, dev, torch.float64), "n": int(n), "fs": float(fs),
+            "array_pos": pos}
+    traj, doa = ops.scene_doa_batch([item])[0]
+    return (traj.cpu().numpy(), doa.cpu().numpy()) if as_numpy else (traj, doa)
+
+
+def _vad_u8(v, dev):
+    """A VAD (bool / 0-1 numbers) as a uint8 device tensor."""
+    if _is_t(v):
+        return v if v.dtype in (torch.uint8, torch.bool) else (v != 0)
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(v) != 0).view(np.uint8)).to(dev)
+
+
+class Segmenting_SRPDNN(object):
+    """The reference's segmenting transform (``Dataset.py``), on the device: ``__call__(x, acoustic_scene)`` cuts the scene's
+    ``DOA`` [L, 2, S] into ``N_w = floor(L / step - K / step + 1)`` windows of ``K`` every ``step`` and sets ``DOAw`` [N_w, 2, S]
+    (the window means, unwrapped where the azimuth jumps by more than pi inside a window and folded back into (-pi, pi]),
+    ``mic_vad`` [N_w, K] and ``mic_vad_sources`` [N_w, K, S] (zero-extended to ``L``; only if the scene has them) and ``tw``
+    (numpy, as the reference computes it).  A scene held in ROCm tensors keeps tensors (``DOAw`` float64, the VADs uint8); a
+    scene held in numpy gets numpy float64, the reference's dtypes.  ``window`` is stored and, as in the reference, never
+    applied."""
+
+    BAD_WINDOW = 'window must be a NumPy window function or a Numpy vector with length K'      # the reference's message
+
+    def __init__(self, K, step, window=None):
+        self.K, self.step = K, step
+        self.w = self._window(K, window)
+
+    @classmethod
+    def _window(cls, K, window):
+        """None -> ones; a function of K -> its value; a vector of length K -> itself; anything else raises."""
+        if window is None:
+            return np.ones(K)
+        try:
+            w = window(K) if callable(window) else window if len(window) == K else None
+        except Exception:
+            w = None
+        if w is None:
+            raise Exception(cls.BAD_WINDOW)
+        return w
+
+    def __call__(self, x, acoustic_scene):
+        sc = acoustic_scene
+        L = int(x.shape[0])
+        if self.K > L:
+            raise Exception('The window size can not be larger than the signal length ({})'.format(L))
+        elif self.step > L:
+            raise Exception('The window step can not be larger than the signal length ({})'.format(L))
+        vads = [getattr(sc, name) for name in ("mic_vad_sources", "mic_vad") if hasattr(sc, name)]
+        _reject_cpu_tensors(x, sc.DOA, *vads)
+        as_numpy = not any(_is_t(a) for a in [sc.DOA] + vads)
+        dev = _device(sc.DOA, *vads, x)
+        nsrc = int(sc.DOA.shape[2])
+        nw = num_windows(L, self.K, self.step)
+        if not 1 <= nsrc <= _lib.SCENE_MAX_SOURCES:
+            raise ValueError("Segmenting_SRPDNN: %d sources (1 .. %d)" % (nsrc, _lib.SCENE_MAX_SOURCES))
+        for name in ("mic_vad_sources", "mic_vad"):
+            if hasattr(sc, name) and getattr(sc, name).shape[0] > L:
+                raise ValueError("Segmenting_SRPDNN: %s has %d samples, the signal %d" % (name, getattr(sc, name).shape[0], L))
+        if hasattr(sc, "mic_vad_sources") and tuple(sc.mic_vad_sources.shape[1:]) != (nsrc,):
+            raise ValueError("Segmenting_SRPDNN: mic_vad_sources %s for %d sources" % (tuple(sc.mic_vad_sources.shape), nsrc))
+        if len(vads) == 2 and vads[0].shape[0] != vads[1].shape[0]:
+            raise ValueError("Segmenting_SRPDNN: mic_vad_sources has %d samples, mic_vad %d" % (vads[0].shape[0], vads[1].shape[0]))
+        item = {"ns": nsrc, "doa": _up(sc.DOA, dev, torch.float64)}
+        for name, key in (("mic_vad_sources", "vad_sources"), ("mic_vad", "vad")):
+            if hasattr(sc, name):
+                item[key] = _vad_u8(getattr(sc, name), dev)
+        out = ops.scene_segment_batch([item], L, self.K, self.step, nw, nsrc, with_vad=len(vads) > 0)
+        host = (lambda a: a.cpu().numpy().astype(np.float64)) if as_numpy else (lambda a: a)
+        sc.DOAw = host(out["doa"][0])
+        if hasattr(sc, "mic_vad"):
+            sc.mic_vad = host(out["vad"][0])
+        if hasattr(sc, "mic_vad_sources"):
+            sc.mic_vad_sources = host(out["vad_sources"][0])
+        sc.tw = window_times(L, self.K, self.step, sc.fs)
+        return x, sc
+
+
+def _label_facts(b, sc, mic, K, step, with_pos):
+    """The host checks of one scene of ``segment_batch`` -> its facts; nothing touches the device."""
+    dp, vs, v = sc.dp_mic_signals_sources, sc.mic_vad_sources, sc.mic_vad
+    ins = [mic, dp, vs, v] + ([sc.traj_pts] if with_pos else [sc.DOA])
+    try:
+        _reject_cpu_tensors(*ins)
+    except RuntimeError as e:
+        raise RuntimeError("segment_batch: scene %d: %s" % (b, e)) from None
+    if len(mic.shape) != 2 or len(dp.shape) != 3 or len(vs.shape) != 2 or len(v.shape) != 1:
+        raise ValueError("segment_batch: scene %d: signals %s, dp_mic_signals_sources %s, mic_vad_sources %s, mic_vad %s for [L, M], "
+                         "[L, M, S], [n, S], [n]" % (b, tuple(mic.shape), tuple(dp.shape), tuple(vs.shape), tuple(v.shape)))
+    L, m, nsrc = int(mic.shape[0]), int(mic.shape[1]), int(vs.shape[1])
+    if K > L:
+        raise ValueError("segment_batch: scene %d: the window size %d is larger than the signal length %d" % (b, K, L))
+    if step > L:
+        raise ValueError("segment_batch: scene %d: the window step %d is larger than the signal length %d" % (b, step, L))
+    if vs.shape[0] > L or v.shape[0] > L:
+        raise ValueError("segment_batch: scene %d: a VAD of %d samples for a signal of %d" % (b, max(vs.shape[0], v.shape[0]), L))
+    if v.shape[0] != vs.shape[0]:
+        raise ValueError("segment_batch: scene %d: mic_vad_sources has %d samples, mic_vad %d" % (b, vs.shape[0], v.shape[0]))
+    if tuple(dp.shape) != (L, m, nsrc):
+        raise ValueError("segment_batch: scene %d: dp_mic_signals_sources %s for [%d, %d, %d]" % (b, tuple(dp.shape), L, m, nsrc))
+    need = (num_windows(L, K, step) - 1) * step + K
+    if with_pos:
+        pts = sc.traj_pts
+        if len(pts.shape) != 3 or pts.shape[1] != 3 or pts.shape[2] != nsrc or len(sc.t) < need:
+            raise ValueError("segment_batch: scene %d: traj_pts %s, len(t) = %d for %d sources and %d samples"
+                             % (b, tuple(pts.shape), len(sc.t), nsrc, need))
+        _host_timestamps(sc.timestamps, "segment_batch: scene %d" % b)
+    elif sc.DOA is None or len(sc.DOA.shape) != 3 or tuple(sc.DOA.shape[1:]) != (2, nsrc) or sc.DOA.shape[0] < need:
+        raise ValueError("segment_batch: scene %d: DOA %s for [>= %d, 2, %d] (pass array_pos to compute it on the device)"
+                         % (b, None if sc.DOA is None else tuple(sc.DOA.shape), need, nsrc))
+    return {"L": L, "m": m, "nsrc": nsrc, "fs": float(sc.fs), "tensors": any(_is_t(a) for a in ins),
+            "device": next((a.device for a in ins if _is_t(a)), None)}
+
+
+def segment_batch(mics, scenes, K, step, max_source=None, array_pos=None):
+    """``Segmenting_SRPDNN(K, step)`` on every scene and the ``gts`` dict of ``FixTrajectoryDataset.__getitem__``, zero-padded to
+    ``max_source`` sources and stacked, for the whole batch in one launch set.  ``mics`` [B, L, M] (or B signals
+    [L, M]); ``scenes``: objects with ``DOA`` [L, 2, S_b], ``mic_vad_sources`` [n, S_b], ``mic_vad`` [n], ``dp_mic_signals_sources``
+    [L, M, S_b] and ``fs`` — what ``simulate_batch`` leaves behind; the scenes are not modified.  Returns ``gts``::
+
+        doa [B, N_w, 2, Smax] float64      vad_sources [B, N_w, K, Smax] uint8      vad_count [B, N_w, Smax] int32 (ones per window)
+        dp_signal [B, L, M, Smax] float32  mic_vad [B, N_w, K] uint8                num_source [B]
+        array_setup [B, M, 3] (the scenes' ``array_setup.mic_pos``; None if a scene has none)
+
+    With ``array_pos`` (one [3] per scene) the DOA is computed on the device from ``traj_pts`` / ``timestamps`` / ``len(t)`` as
+    ``trajectory_doa`` does and ``scene.DOA`` is not read (it may be None).  ``max_source`` defaults to the batch's largest
+    source count; a scene with more raises ``ValueError`` naming it, as do scenes that differ in L, M or fs, a VAD longer than
+    L, ``K`` or ``step`` > L, and a CPU tensor (``RuntimeError``) — all before anything touches the device.  numpy in every
+    scene gives numpy out."""
+    scenes = list(scenes)
+    if not scenes:
+        raise ValueError("segment_batch: no scene")
+    if len(mics) != len(scenes):
+        raise ValueError("segment_batch: %d signals for %d scenes" % (len(mics), len(scenes)))
+    if array_pos is not None and len(array_pos) != len(scenes):
+        raise ValueError("segment_batch: %d array positions for %d scenes" % (len(array_pos), len(scenes)))
+    K, step = int(K), int(step)
+    if K < 1 or step < 1:
+        raise ValueError("segment_batch: K = %d, step = %d" % (K, step))
+    facts = []
+    for b, sc in enumerate(scenes):
+        facts.append(_label_facts(b, sc, mics[b], K, step, array_pos is not None))
+        for key, what in (("L", "samples"), ("m", "microphones"), ("fs", "Hz")):
+            if facts[b][key] != facts[0][key]:
+                raise ValueError("segment_batch: scene %d: %g %s, scene 0 has %g (a batch shares L, M and fs)"
+                                 % (b, facts[b][key], what, facts[0][key]))
+    smax = max(f["nsrc"] for f in facts) if max_source is None else int(max_source)
+    if not 1 <= smax <= _lib.SCENE_MAX_SOURCES:
+        raise ValueError("segment_batch: max_source = %d (1 .. %d)" % (smax, _lib.SCENE_MAX_SOURCES))
+    for b, f in enumerate(facts):
+        if not 1 <= f["nsrc"] <= smax:
+            raise ValueError("segment_batch: scene %d: %d sources (1 .. max_source = %d)" % (b, f["nsrc"], smax))
+    poss = None
+    if array_pos is not None:
+        poss = [np.asarray(p.detach().cpu().numpy() if _is_t(p) else p, dtype=np.float64).reshape(-1) for p in array_pos]
+        for b, p in enumerate(poss):
+            if p.shape != (3,) or not np.all(np.isfinite(p)):
+                raise ValueError("segment_batch: scene %d: array_pos must be three finite numbers" % b)
+    L, m = facts[0]["L"], facts[0]["m"]
+    nw = num_windows(L, K, step)
+    as_numpy = not any(f["tensors"] for f in facts) and not _is_t(mics)
+    dev = next((f["device"] for f in facts if f["device"] is not None), mics.device if _is_t(mics) else torch.device("cuda:0"))
+
+    if poss is not None:
+        doas = [d for _, d in ops.scene_doa_batch(
+            [{"traj_pts": _up(sc.traj_pts, dev, torch.float64), "timestamps": _up(sc.timestamps, dev, torch.float64),
+              "n": len(sc.t), "fs": sc.fs, "array_pos": poss[b]} for b, sc in enumerate(scenes)])]
+    else:
+        doas = [_up(sc.DOA, dev, torch.float64) for sc in scenes]
+    items = [{"ns": facts[b]["nsrc"], "doa": doas[b], "vad_sources": _vad_u8(sc.mic_vad_sources, dev), "vad": _vad_u8(sc.mic_vad, dev)}
+             for b, sc in enumerate(scenes)]
+    out = ops.scene_segment_batch(items, L, K, step, nw, smax)
+    dp = ops.scene_pack_batch([_up(sc.dp_mic_signals_sources, dev) for sc in scenes], L, m, smax)
+    setups = [getattr(getattr(sc, "array_setup", None), "mic_pos", None) for sc in scenes]
+    if any(a is None for a in setups):
+        setup = None
+    elif any(_is_t(a) for a in setups):
+        setup = torch.stack([a if _is_t(a) else torch.from_numpy(np.asarray(a)).to(dev) for a in setups])
+    else:
+        setup = np.stack([np.asarray(a) for a in setups])
+        setup = setup if as_numpy else torch.from_numpy(setup).to(dev)
+    nums = np.array([f["nsrc"] for f in facts], dtype=np.int64)
+    host = (lambda a: a.cpu().numpy()) if as_numpy else (lambda a: a)
+    return {"doa": host(out["doa"]), "vad_sources": host(out["vad_sources"]), "vad_count": host(out["vad_count"]),
+            "dp_signal": host(dp), "mic_vad": host(out["vad"]), "num_source": nums if as_numpy else torch.from_numpy(nums).to(dev),
+            "array_setup": setup}
+
+
+def training_batch(dataset, idx1, idx2, K=3328, step=3072, max_source=2):
+    """One training batch without a host round trip of the signals: ``dataset.getRandomScene(idx)`` for idx1 <= idx < idx2,
+    ``simulate_batch``, ``segment_batch`` -> (mic [B, n, M], gts), ready to be the ``batch`` of ``IPDnet.train_step.MyModel.
+    training_step`` and of ``predict_step.MyModel.data_preprocess``.  ``K`` and ``step`` default to the reference's training
+    setting (``seg_fra_ratio = 12`` frames of hop 256 with a 512 window).  Scenes that carry ``array_pos`` get their DOA
+    computed on the device from the trajectory points; otherwise ``scene.DOA`` is used."""
+    scenes = [dataset.getRandomScene(idx) for idx in range(idx1, idx2)]
+    mic = simulate_batch(scenes)
+    poss = [getattr(sc, "array_pos", None) for sc in scenes]
+    return mic, segment_batch(mic, scenes, K, step, max_source, None if any(p is None for p in poss) else poss)

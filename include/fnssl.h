@@ -1458,6 +1458,55 @@ typedef struct {
 int fnssl_scene_power_batch(const fnssl_scene_desc* scenes, int nscenes, int n, int m, void* stream);
 int fnssl_scene_finish_batch(const fnssl_scene_desc* scenes, int nscenes, int n, int m, void* stream);
 
+/* ---- training labels of a batch of scenes (csrc/labels.hip; additive: FNSSL_ABI_VERSION stays 19) -----------------------------
+ * What the reference's getRandomScene, Segmenting_SRPDNN and the padded gts dict do between simulate() and a training
+ * step.  `scenes` is a HOST array of per-scene records that travel by value in the kernel arguments,
+ * FNSSL_SCENE_BATCH_SCENES per launch (more scenes: more launches); every scene is checked before the first launch and a
+ * refused scene is named by its index.  Angles are double, unfused; every sum has a fixed order; no atomics; a scene's
+ * bits do not depend on the rest of the batch.
+ *
+ * fnssl_scene_doa_batch: per scene trajectory[k][i][s] = np.interp(k / fs, timestamps, traj_pts[:, i, s]) (numpy's slope form,
+ *   clamped to the first / last point outside the timestamps, which must be finite and increase: the caller checks that) and, with c = trajectory - array_pos,
+ *   doa[k][0][s] = atan2(sqrt(cx^2 + cy^2), cz) (elevation), doa[k][1][s] = atan2(cy, cx) (azimuth).  One launch per block. */
+typedef struct {
+  const double* traj_pts;                        /* [npts][3][ns] */
+  const double* timestamps;                      /* [npts] */
+  double array_pos[3];
+  double fs;
+  int npts, ns, n;
+  double* trajectory;                            /* [n][3][ns] */
+  double* doa;                                   /* [n][2][ns] */
+} fnssl_scene_doa_desc;
+int fnssl_scene_doa_batch(const fnssl_scene_doa_desc* scenes, int nscenes, void* stream);
+
+/* fnssl_scene_segment_batch: nw windows of K samples every step over signals of len samples, (nw - 1) step + K <= len (the
+ *   caller passes the reference's nw = floor(len / step - K / step + 1), evaluated in double as the reference does).  Per
+ *   scene, source s < ns and window w over doa[w step .. w step + K): if max |diff(azimuth)| > pi, 2 pi is added to the
+ *   window's negative azimuths; doaw[b][w][0 / 1][s] = the window's mean elevation / azimuth; a mean azimuth > pi has 2 pi
+ *   subtracted.  vad_sources[b][w][i][s] = the scene's vad_sources[w step + i][s] and vad[b][w][i] = its vad[w step + i],
+ *   zero past vad_len (<= len); vad_count[b][w][s] = the ones of that window.  Sources s >= ns are zeros everywhere.
+ *   One workgroup per (window, source, scene), one launch per block.  Output halves may be NULL (doaw; vad_sources with
+ *   vad_count; vad), and so may a scene's inputs (doa: its doaw rows are not written; a VAD: zeros). */
+typedef struct {
+  const double* doa;                             /* [doa_len][2][ns] */
+  const unsigned char* vad_sources;              /* [vad_len][ns], 0 / 1 */
+  const unsigned char* vad;                      /* [vad_len], 0 / 1 */
+  int ns, doa_len, vad_len;
+} fnssl_scene_segment_desc;
+int fnssl_scene_segment_batch(const fnssl_scene_segment_desc* scenes, int nscenes, int len, int K, int step, int nw, int smax,
+                              double* doaw, unsigned char* vad_sources, unsigned char* vad, int* vad_count, void* stream);
+
+/* fnssl_scene_pack_batch: out[b][t][c][s] = dp[s][t stride_t + c stride_c] of scene b for s < ns, 0 for ns <= s < smax; out is
+ *   [nscenes][n][m][smax].  Separate signals [>= n][m] have strides (m, 1); sources stacked as [n][m][ns] have dp[s] = base + s and
+ *   strides (m ns, ns).  float4 stores when smax is 1, 2 or 4, n m smax is a multiple of 4 and out is 16-byte aligned.
+ *   One launch per block. */
+typedef struct {
+  const float* dp[FNSSL_SCENE_MAX_SOURCES];      /* direct-path signals, t < n and c < m readable */
+  long long stride_t, stride_c;                  /* in floats, >= 1 */
+  int ns;
+} fnssl_scene_pack_desc;
+int fnssl_scene_pack_batch(const fnssl_scene_pack_desc* scenes, int nscenes, int n, int m, int smax, float* out, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* Measurement hooks (bench.py: per-kernel HIP-event timing on the launch stream) */
 /* ------------------------------------------------------------------------- */
